@@ -6,14 +6,20 @@ step(params, graph) on one 640x480-derived Delaunay graph per GPU (BASELINE.json
 --gpus N each rank owns an independent frame = configs[3], results gathered with RCCL).  Inputs are
 resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-  python bench.py                         # 1 GPU, defaults finish in about a minute
+  python bench.py                         # 1 GPU: set-up, warmup, the timed steps, the line
+  python bench.py --full                  # ... and every side measurement and check below (a few minutes)
+  python bench.py --dump-outputs DIR      # ... and the state of the timed context as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Extra keys beyond the driver contract: "roofline" (dominant kernel vs the 8 TB/s HBM peak, from the
-algorithmic byte count 64*V+40*E per step), "cpu_baseline" (the CPU checker in the reference's
-node-based layout, 1 thread, timed here on the box's host cores), "parity" (this run's result vs the
-checker), "batched" (aggregate rate with many frames resident on one GPU), "other_configs".
+A plain run measures only the headline: "value", "ms_per_step" and a "roofline" (dominant kernel vs the
+8 TB/s HBM peak, from the algorithmic byte count 64*V+40*E per step and this run's HIP events).  With
+--full the line also carries "parity" (this run's result and the timed context vs the CPU checker),
+"cpu_baseline" (the CPU checker in the reference's node-based layout, 1 thread, timed here on the box's
+host cores), the roofline's "step_cycles" and "floor", "batched" (aggregate rate with many frames
+resident on one GPU), "other_configs", the host-boundary / sync / Delaunay / raster / feature-update
+figures, "open_run", and for N > 1 the result gather's overlap check, latency and row check;
+--no-extras and --no-cpu-baseline leave parts of that out again.
 """
 from __future__ import annotations
 
@@ -44,8 +50,12 @@ def parse():
     ap.add_argument("--iters", type=int, default=200, help="primal-dual iterations per step (BASELINE: 200)")
     ap.add_argument("--config", default="640x480")
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU in the extra 'batched' measurement (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip batched / other-config measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks (parity, CPU baseline, extras, result-gather checks)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed context's state after the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip step cycles / floor / batched / other-config measurements")
     ap.add_argument("--cpu-iters", type=int, default=20000)
     ap.add_argument("--persistent", type=int, default=1, help="0: one launch per step; 1: persistent single launch (form by size); 3 / 4 / 6: the vertex-per-lane / patch-per-wave / two-half-edges form by name")
     return ap.parse_args()
@@ -152,7 +162,11 @@ def main():
         from flame_amd.frames import IdepthGather
 
         ig = IdepthGather(dist, [g["V"]], world, torch.device("cuda", local_rank), stream=solver_stream)
-        ig.check_overlap(reg, params)  # (warns if the collective does not run beside the solver)
+        if a.full:
+            ig.check_overlap(reg, params)  # (warns if the collective does not run beside the solver)
+        else:  # the communicator's first collective, outside the timed steps (check_overlap's first loop does it with --full)
+            ig.local_row(0)
+            ig.gather(async_op=False)
         reg.upload_graph(g)
 
 
@@ -170,6 +184,15 @@ def main():
     gather_ok = None
     if dist is not None:
         regathered = ig.settle([reg])
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step: the timed context's state (and, N > 1, the gathered block)
+        dumped = reg.download_state()
+        if dist is not None:
+            dumped["gathered_x"] = torch.cat([ig.frame(r) for r in range(world)]).cpu().numpy()
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    if dist is not None and a.full:
         # the last gathered block against this rank's own state: row `rank` must be x * 1.0 of the timed context
         mine = ig.frame(rank).cpu().numpy()
         gather_ok = bool(np.array_equal(mine, reg.download_state(("x",))["x"]))
@@ -242,12 +265,12 @@ def main():
             # (--no-extras leaves both out: they launch the dominant kernel with other lengths and graphs, and the rocprofv3 statistics of that
             #  command -- tools/profile.sh, profiles/r06_kernel_stats_bench.csv -- are to hold the headline's launches only)
             try:
-                if not a.no_extras:
+                if a.full and not a.no_extras:
                     roofline["step_cycles"] = pv_step_cycles(flame_amd, g, params, a.iters, local_rank)
             except Exception as e:  # noqa: BLE001
                 roofline["step_cycles"] = f"{type(e).__name__}: {e}"
             try:  # what `frac` has to be read against: the physical floor of one iteration of ONE small frame, measured by this run
-                if not a.no_extras:
+                if a.full and not a.no_extras:
                     roofline["floor"] = latency_floor(flame_amd, synth, params, a.iters, local_rank, B_iter, roofline)
             except Exception as e:  # noqa: BLE001
                 roofline["floor"] = f"{type(e).__name__}: {e}"
@@ -263,71 +286,73 @@ def main():
             "device": {"name": info["device_name"], "arch": info["gcn_arch"], "cus": info["compute_units"]},
             "run_path": run_path,
         }
+        if dist is not None:
+            out["result_gather"] = {"bytes_per_rank": int(g["V"]) * 4, "ranks": world, "backend": backend, "regathered_after_replay": int(regathered)}
         if gather_us is not None:
-            out["result_gather"] = {"overlap": getattr(ig, "overlap", None), "all_gather_us": round(gather_us, 1), "bytes_per_rank": int(g["V"]) * 4, "ranks": world, "backend": backend,
-                                    "last_row_matches_state": gather_ok, "regathered_after_replay": int(regathered),
-                                    "note": "blocking all_gather_into_tensor of x*graph_scale incl. host launch + sync; in the "
-                                            "step loop it is asynchronous and overlaps the next solve"}
-        # ---- parity of THIS run's input against the CPU checker (same seeded input, same iteration count)
-        from oracle import capi as oracle
+            out["result_gather"].update({"overlap": getattr(ig, "overlap", None), "all_gather_us": round(gather_us, 1), "last_row_matches_state": gather_ok,
+                                         "note": "blocking all_gather_into_tensor of x*graph_scale incl. host launch + sync; in the "
+                                                 "step loop it is asynchronous and overlaps the next solve"})
+        if a.full:
+            # ---- parity of THIS run's input against the CPU checker (same seeded input, same iteration count)
+            from oracle import capi as oracle
 
-        chk = flame_amd.Regularizer(local_rank)
-        chk.upload_graph(g)
-        chk.run(params, a.iters)
-        got = chk.download_state(("x", "w1", "w2"))
-        chk.close()
-        ref = synth.copy_graph(g)
-        oracle.run(ref, a.iters)
-        d = got["x"].astype(np.float64) - ref["x"].astype(np.float64)
-        out["parity"] = {"depth_rms_vs_cpu": float(np.sqrt(np.mean(d * d))), "max_abs": float(np.abs(d).max()),
-                         "bit_identical": bool(all(np.array_equal(got[k], ref[k]) for k in got)),
-                         "iters": a.iters, "tolerance_rms": 1e-4}
-        # ... and the TIMED context itself: `reg` has by now done (warmup + steps) x iters iterations from the uploaded input
-        # on the solver's stream (the launches `value` was measured on); its whole state must be what the checker has after as many
-        total_run = (a.warmup + a.steps) * a.iters
-        state_keys = ("x", "w1", "w2", "x_bar", "w1_bar", "w2_bar", "q1", "q2", "q3")
-        timed_state = reg.download_state(state_keys)
-        ref_t = synth.copy_graph(g)
-        t_chk = time.perf_counter()
-        threads = min(16, os.cpu_count() or 1)
-        if threads >= 4:   # the OpenMP two-phase form of the checker: bit-identical to the sequential one for any thread count
-            oracle.omp_run(ref_t, total_run, threads)
-        else:
-            oracle.run(ref_t, total_run)
-        dt = timed_state["x"].astype(np.float64) - ref_t["x"].astype(np.float64)
-        out["parity"]["timed_context_bit_identical"] = bool(all(np.array_equal(timed_state[k], ref_t[k]) for k in state_keys))
-        out["parity"]["timed_context"] = {"iters": total_run, "depth_rms_vs_cpu": float(np.sqrt(np.mean(dt * dt))),
-                                          "arrays_compared": list(state_keys), "checker_s": round(time.perf_counter() - t_chk, 2),
-                                          "timeouts_recovered": int(reg.info()["timeouts_recovered"])}
-        # ---- CPU baseline on this box's host cores: reference-layout restatement, 1 thread (the
-        # reference runs its solver on exactly one thread, flame.cc:99-112)
-        if not a.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N=1 only
-            secs = oracle.reflayout_run_timed(synth.copy_graph(g), a.cpu_iters)
-            flat = oracle.run_timed(synth.copy_graph(g), max(200, a.cpu_iters // 4))
-            out["cpu_baseline"] = {
-                "value": round(a.cpu_iters / secs, 1), "unit": "iters/s", "cores": 1, "kind": "port",
-                "sample": f"{a.cpu_iters} iterations of the same {a.config} graph (V={g['V']} E={g['E']}), "
-                          f"node-based (BGL-like) layout, 1 thread, {secs:.1f} s",
-                "flat_soa_1thread_iters_per_s": round(max(200, a.cpu_iters // 4) / flat, 1),
-                "host_cores": os.cpu_count(),
-            }
-            out["speedup_vs_cpu_baseline"] = round(value / world / out["cpu_baseline"]["value"], 1)
-            # the strongest fair CPU number: OpenMP two-phase form over the host cores, bit-identical
-            # to the sequential restatement; the reference itself runs the solver on one thread
-            best = None
-            for t in (8, 16, 32, 64, 128):
-                if t > (os.cpu_count() or 1):
-                    break
-                s_omp = oracle.omp_run_timed(synth.copy_graph(g), 2000, t)
-                if best is None or 2000 / s_omp > best[0]:
-                    best = (2000 / s_omp, t)
-            if best:
-                out["cpu_baseline"]["openmp_all_cores"] = {
-                    "value": round(best[0], 1), "unit": "iters/s", "threads": best[1],
-                    "sample": "2000 iterations per thread count in (8,16,32,64,128), best reported; flat SoA arrays, "
-                              "edge-parallel dual + vertex-gather primal",
-                    "gpu_over_this": round(value / world / best[0], 1)}
-    if not a.no_extras and world == 1:
+            chk = flame_amd.Regularizer(local_rank)
+            chk.upload_graph(g)
+            chk.run(params, a.iters)
+            got = chk.download_state(("x", "w1", "w2"))
+            chk.close()
+            ref = synth.copy_graph(g)
+            oracle.run(ref, a.iters)
+            d = got["x"].astype(np.float64) - ref["x"].astype(np.float64)
+            out["parity"] = {"depth_rms_vs_cpu": float(np.sqrt(np.mean(d * d))), "max_abs": float(np.abs(d).max()),
+                             "bit_identical": bool(all(np.array_equal(got[k], ref[k]) for k in got)),
+                             "iters": a.iters, "tolerance_rms": 1e-4}
+            # ... and the TIMED context itself: `reg` has by now done (warmup + steps) x iters iterations from the uploaded input
+            # on the solver's stream (the launches `value` was measured on); its whole state must be what the checker has after as many
+            total_run = (a.warmup + a.steps) * a.iters
+            state_keys = ("x", "w1", "w2", "x_bar", "w1_bar", "w2_bar", "q1", "q2", "q3")
+            timed_state = reg.download_state(state_keys)
+            ref_t = synth.copy_graph(g)
+            t_chk = time.perf_counter()
+            threads = min(16, os.cpu_count() or 1)
+            if threads >= 4:   # the OpenMP two-phase form of the checker: bit-identical to the sequential one for any thread count
+                oracle.omp_run(ref_t, total_run, threads)
+            else:
+                oracle.run(ref_t, total_run)
+            dt = timed_state["x"].astype(np.float64) - ref_t["x"].astype(np.float64)
+            out["parity"]["timed_context_bit_identical"] = bool(all(np.array_equal(timed_state[k], ref_t[k]) for k in state_keys))
+            out["parity"]["timed_context"] = {"iters": total_run, "depth_rms_vs_cpu": float(np.sqrt(np.mean(dt * dt))),
+                                              "arrays_compared": list(state_keys), "checker_s": round(time.perf_counter() - t_chk, 2),
+                                              "timeouts_recovered": int(reg.info()["timeouts_recovered"])}
+            # ---- CPU baseline on this box's host cores: reference-layout restatement, 1 thread (the
+            # reference runs its solver on exactly one thread, flame.cc:99-112)
+            if not a.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N=1 only
+                secs = oracle.reflayout_run_timed(synth.copy_graph(g), a.cpu_iters)
+                flat = oracle.run_timed(synth.copy_graph(g), max(200, a.cpu_iters // 4))
+                out["cpu_baseline"] = {
+                    "value": round(a.cpu_iters / secs, 1), "unit": "iters/s", "cores": 1, "kind": "port",
+                    "sample": f"{a.cpu_iters} iterations of the same {a.config} graph (V={g['V']} E={g['E']}), "
+                              f"node-based (BGL-like) layout, 1 thread, {secs:.1f} s",
+                    "flat_soa_1thread_iters_per_s": round(max(200, a.cpu_iters // 4) / flat, 1),
+                    "host_cores": os.cpu_count(),
+                }
+                out["speedup_vs_cpu_baseline"] = round(value / world / out["cpu_baseline"]["value"], 1)
+                # the strongest fair CPU number: OpenMP two-phase form over the host cores, bit-identical
+                # to the sequential restatement; the reference itself runs the solver on one thread
+                best = None
+                for t in (8, 16, 32, 64, 128):
+                    if t > (os.cpu_count() or 1):
+                        break
+                    s_omp = oracle.omp_run_timed(synth.copy_graph(g), 2000, t)
+                    if best is None or 2000 / s_omp > best[0]:
+                        best = (2000 / s_omp, t)
+                if best:
+                    out["cpu_baseline"]["openmp_all_cores"] = {
+                        "value": round(best[0], 1), "unit": "iters/s", "threads": best[1],
+                        "sample": "2000 iterations per thread count in (8,16,32,64,128), best reported; flat SoA arrays, "
+                                  "edge-parallel dual + vertex-gather primal",
+                        "gpu_over_this": round(value / world / best[0], 1)}
+    if a.full and not a.no_extras and world == 1:
         try:  # labelled side measurements: never allowed to take the contract line down with them
             extras(a, reg, params, out, flame_amd, synth, sync, info)
         except Exception as e:  # noqa: BLE001

@@ -149,8 +149,9 @@ def test_one_rccl_rank_per_visible_device(side_stream):
 def test_bench_two_ranks_dry_run_with_backend_override():
     env = dict(os.environ)
     env.update({"FLAME_BENCH_BACKEND": "gloo", "FLAME_BENCH_DEVICE": "0", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"]
+    # (--standalone: the launcher binds a port the OS picks; a port picked here first can be taken by another process before it binds)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--nnodes=1", "--nproc-per-node", "2",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -192,10 +193,9 @@ def test_one_rccl_rank_under_torchrun_is_as_fast_as_the_plain_line():
     box, same steps -- whole-job value within 5 % (round 5 measured 1.00; a gather that lands on the solver's queue again, or waits
     for the runs around it, shows up here as 0.9 or less)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "4", "--no-extras", "--no-cpu-baseline"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "4", "--full", "--no-extras", "--no-cpu-baseline"]
     plain = max(_bench_line([sys.executable] + args, env)["value"] for _ in range(2))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port())] + args
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--nnodes=1", "--nproc-per-node", "1"] + args
     outs = [_bench_line(cmd, env) for _ in range(2)]
     best = max(o["value"] for o in outs)
     assert outs[0]["result_gather"]["backend"] == "nccl" and outs[0]["result_gather"]["last_row_matches_state"] is True

@@ -1,5 +1,5 @@
 set -x
-B="bench.py --steps 200 --warmup 20 --no-extras --no-cpu-baseline"
+B="bench.py --steps 200 --warmup 20 --full --no-extras --no-cpu-baseline"
 T="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1"
 python $B 2>/dev/null | tail -1 | python -c "import json,sys; o=json.loads(sys.stdin.read()); print('plain', o['value'], o['ms_per_step'])"
 $T --master-port 29511 $B --gpus 1 2>/dev/null | grep '"metric"' | python -c "import json,sys; o=json.loads(sys.stdin.read()); print('torchrun', o['value'], o['ms_per_step'], o['result_gather'])"

@@ -14,9 +14,9 @@ run() {  # run FILE command...: the command line, then its output
   echo >> $O/$f
 }
 if want bench; then
-  python bench.py > $O/bench_1gpu.json 2> $O/bench_1gpu.err
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 1 2> $O/bench_torchrun.err | grep '"metric"' > $O/bench_torchrun_1rank.json
-  FLAME_BENCH_BACKEND=gloo FLAME_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29522 bench.py --gpus 2 --steps 20 --warmup 3 2> $O/bench_2ranks.err | grep '"metric"' > $O/bench_torchrun_2ranks_gloo_one_device.json
+  python bench.py --full > $O/bench_1gpu.json 2> $O/bench_1gpu.err
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 1 --full 2> $O/bench_torchrun.err | grep '"metric"' > $O/bench_torchrun_1rank.json
+  FLAME_BENCH_BACKEND=gloo FLAME_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29522 bench.py --gpus 2 --steps 20 --warmup 3 --full 2> $O/bench_2ranks.err | grep '"metric"' > $O/bench_torchrun_2ranks_gloo_one_device.json
 fi
 if want loops; then
   for s in 640x480 1280x720 1920x1080; do
