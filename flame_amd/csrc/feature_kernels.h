@@ -1,0 +1,55 @@
+// feature_kernels.h -- launch wrappers of feature_kernels.hip: projectFeatures and detectFeatures on the resident
+// feature set (include/flame_stereo.h's device side).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "stereo_kernels.h"
+
+namespace flame_hip {
+
+// One per pose-frame the resident features may refer to: the geometry of T_ref_to_cur = fcur.pose.inverse() *
+// fref.pose (flame.cc:1786), loaded by the host (load_geometry) from flame_stereo_pose.q/t_ref_to_new.
+struct ProjectPoseEntry {
+  uint32_t frame_id;
+  Geo geo;
+};
+
+// cv::Rect_<float> valid_region(border, border + row_offset, cols - 2 border, rows - 2 border - 2 row_offset)
+// (flame.cc:1772-1774), as the float values the reference's Rect holds.
+struct ProjectRegion {
+  float x, y, w, h;
+};
+
+// The candidate pixels and the cell grid of detectFeatures (flame.cc:1001-1004, 1020-1021).
+struct DetectGrid {
+  int win, hc, wc;
+  int r_lo, r_hi, c_lo, c_hi;  // rows [r_lo, r_hi), cols [c_lo, c_hi)
+  float g2;                    // Params::min_grad_mag^2
+};
+
+// What the detection loop writes into a new FeatureWithIDepth (flame.cc:739-753).
+struct DetectInit {
+  uint32_t first_id, ref_frame_id;
+  float idepth_init, idepth_var_init;
+};
+
+// stats words of both stages: [kFrontAssert] lowest index that hit a reference assert, [kFrontBadFrame] lowest
+// feature index with an unknown frame id (both start at INT_MAX), [kFrontCount] kept / new features.
+constexpr int kFrontAssert = 0, kFrontBadFrame = 1, kFrontCount = 2, kFrontWords = 4;
+
+// k_project_flag + k_project_scatter: `feats` (n) -> stably compacted `feats_out` / `proj_out`; proj_tmp and keep are
+// n-sized scratch, counts (n + 255) / 256 ints.
+hipError_t launch_project_features(const StereoCamera& cam, const ProjectRegion& region, int n_poses,
+                                   const ProjectPoseEntry* poses, uint32_t cur_frame_id, int n, const StereoFeature* feats,
+                                   StereoFeature* proj_tmp, uint8_t* keep, int* counts, StereoFeature* feats_out,
+                                   StereoFeature* proj_out, int* stats, hipStream_t stream);
+// clear + k_detect_mask + k_detect_cells + k_detect_count + k_detect_emit: the new features go to out[0 .. count);
+// `blocked` and `cell_key` hold hc * wc entries, counts (hc * wc + 255) / 256, `out` room for hc * wc records.  mask_xy: n_mask points, `mask_stride` floats apart.
+// idepthmap: width x height floats in device memory, or NULL.
+hipError_t launch_detect_features(const DetectGrid& grid, const Geo& geo, const StereoCamera& cam, const float* gx_pad,
+                                  const float* gy_pad, int n_mask, const float* mask_xy, int mask_stride, uint8_t* blocked,
+                                  unsigned long long* cell_key, int* counts, const DetectInit& init, const float* idepthmap,
+                                  StereoFeature* out, int* stats, hipStream_t stream);
+
+}  // namespace flame_hip

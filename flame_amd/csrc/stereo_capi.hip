@@ -1,8 +1,10 @@
 // stereo_capi.hip -- C-ABI of include/flame_stereo.h: resident frames (padded image + gradients built on the
-// device), the per-launch pose table, and the host/device feature-array entry points of the per-feature epipolar
-// inverse-depth update.  All arithmetic of the path runs in stereo_kernels.hip; this file only moves bytes.
+// device), the per-launch pose table, the host/device feature-array entry points of the per-feature epipolar
+// inverse-depth update, and projectFeatures / detectFeatures on the resident set.  All arithmetic of the path runs in
+// stereo_kernels.hip and feature_kernels.hip; this file only moves bytes.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <new>
@@ -11,6 +13,7 @@
 
 #include "flame_stereo.h"
 #include "stereo_kernels.h"
+#include "feature_kernels.h"
 #include "roctx_ranges.hpp"
 
 using namespace flame_hip;
@@ -51,6 +54,32 @@ struct flame_stereo_ctx {
   size_t res_cap = 0;
   int n_res = 0;
   int lanes_per_feature = 0;  // 0 = by feature count (pick_lanes)
+  // projectFeatures / detectFeatures (feature_kernels.hip)
+  StereoFeature* d_res_alt = nullptr;  // the other buffer of the resident set's ping-pong pair
+  size_t res_alt_cap = 0;
+  StereoFeature* d_proj = nullptr;  // the projected set (Flame::feats_in_curr_) and its other buffer
+  size_t proj_cap = 0;
+  StereoFeature* d_proj_alt = nullptr;
+  size_t proj_alt_cap = 0;
+  int n_proj = 0;
+  StereoFeature* d_proj_tmp = nullptr;  // one projected record per resident feature
+  size_t proj_tmp_cap = 0;
+  uint8_t* d_keep = nullptr;
+  size_t keep_cap = 0;
+  int* d_groups = nullptr;  // per-workgroup counts of the compactions
+  size_t groups_cap = 0;
+  ProjectPoseEntry* d_ppose = nullptr;
+  size_t ppose_cap = 0;
+  unsigned long long* d_cell_key = nullptr;
+  size_t cell_key_cap = 0;
+  uint8_t* d_blocked = nullptr;
+  size_t blocked_cap = 0;
+  float* d_map = nullptr;  // a host idepth map, uploaded
+  size_t map_cap = 0;
+  float* d_mask = nullptr;  // a host mask, uploaded
+  size_t mask_cap = 0;
+  int* d_fstats = nullptr;
+  int* h_fstats = nullptr;  // pinned, kFrontWords ints
 };
 
 namespace {
@@ -174,6 +203,38 @@ int report(flame_stereo_ctx* ctx, flame_stereo_stats* stats) {
   return 0;
 }
 
+// grow() for the resident set when it is appended to: the first `keep` records move to the new buffer.
+int grow_keep(flame_stereo_ctx* ctx, StereoFeature** p, size_t* cap, size_t count, size_t keep) {
+  if (*cap >= count) return 0;
+  const size_t want = count + count / 2 + 16;
+  StereoFeature* np = nullptr;
+  SCHK(ctx, hipMalloc((void**)&np, want * sizeof(StereoFeature)));
+  if (keep > 0) {
+    hipError_t e = hipMemcpyAsync(np, *p, keep * sizeof(StereoFeature), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(np);
+      ctx->last_hip = (int)e;
+      return FLAME_NLTGV2_ERR_HIP;
+    }
+  }
+  if (*p) SCHK(ctx, hipFree(*p));
+  *p = np, *cap = want;
+  return 0;
+}
+
+// `int border = params.rescale_factor_max * params.fparams.win_size / 2 + 1;` (flame.cc:847, 1771): float arithmetic
+int front_border(const flame_stereo_params& P) { return (int)(P.rescale_factor_max * P.win_size / 2 + 1); }
+
+// Enqueues the front-end stats block reset (the two error indices at INT_MAX, the count at 0).
+int reset_front_stats(flame_stereo_ctx* ctx) {
+  ctx->h_fstats[kFrontAssert] = ctx->h_fstats[kFrontBadFrame] = INT_MAX;
+  ctx->h_fstats[kFrontCount] = 0;
+  ctx->h_fstats[3] = 0;
+  SCHK(ctx, hipMemcpyAsync(ctx->d_fstats, ctx->h_fstats, kFrontWords * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -219,7 +280,9 @@ int flame_stereo_create(flame_stereo_ctx** out, int device) {
   if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
       hipMalloc((void**)&ctx->d_stats, kStatWords * sizeof(int)) != hipSuccess ||
-      hipHostMalloc((void**)&ctx->h_stats, kStatWords * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+      hipHostMalloc((void**)&ctx->h_stats, kStatWords * sizeof(int), hipHostMallocDefault) != hipSuccess ||
+      hipMalloc((void**)&ctx->d_fstats, kFrontWords * sizeof(int)) != hipSuccess ||
+      hipHostMalloc((void**)&ctx->h_fstats, kFrontWords * sizeof(int), hipHostMallocDefault) != hipSuccess) {
     flame_stereo_destroy(ctx);
     return FLAME_NLTGV2_ERR_HIP;
   }
@@ -238,6 +301,11 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   if (ctx->h_poses) (void)hipHostFree(ctx->h_poses);
   if (ctx->d_feats) (void)hipFree(ctx->d_feats);
   if (ctx->d_res) (void)hipFree(ctx->d_res);
+  for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
+                  (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
+                  (void*)ctx->d_fstats})
+    if (p) (void)hipFree(p);
+  if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
   if (ctx->d_stats) (void)hipFree(ctx->d_stats);
   if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -409,6 +477,172 @@ int flame_stereo_update_resident(flame_stereo_ctx* ctx, const flame_stereo_param
   if (!stats) return 0;
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
   return report(ctx, stats);
+}
+
+void flame_stereo_default_detect_params(flame_stereo_detect_params* p) {
+  if (!p) return;
+  p->detection_win_size = 16;
+  p->min_grad_mag = 5.0f;
+  p->idepth_init = 0.01f;
+  p->idepth_var_init = 0.5f * 0.5f;
+}
+
+int flame_stereo_project_features(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t cur_frame_id,
+                                  int n_poses, const flame_stereo_pose* poses, flame_stereo_feature_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_project_features");
+  if (int rc = enter(ctx)) return rc;
+  if (stats) stats->num_features = 0, stats->num_examined = 0, stats->error_feature = -1;
+  if (!params || n_poses < 0 || (n_poses > 0 && !poses)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  const int n = ctx->n_res;
+  if (stats) stats->num_examined = n;
+  if (n == 0) {
+    ctx->n_proj = 0;
+    return 0;
+  }
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated; the pinned stats block is reused)
+  if (int rc = grow(ctx, &ctx->d_res_alt, &ctx->res_alt_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_proj_alt, &ctx->proj_alt_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_proj_tmp, &ctx->proj_tmp_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_keep, &ctx->keep_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_groups, &ctx->groups_cap, (size_t)n / 256 + 1)) return rc;
+  if (int rc = grow(ctx, &ctx->d_ppose, &ctx->ppose_cap, (size_t)n_poses + 1)) return rc;
+  std::vector<ProjectPoseEntry> table((size_t)n_poses);
+  for (int k = 0; k < n_poses; ++k) {
+    std::memset(&table[k], 0, sizeof table[k]);
+    table[k].frame_id = poses[k].frame_id;
+    load_geometry(table[k].geo, ctx->cam, poses[k].q_ref_to_new, poses[k].t_ref_to_new);
+  }
+  const int border = front_border(*params);
+  const int row_offset = params->do_letterbox ? ctx->cam.height / 3 : 0;
+  const ProjectRegion region = {(float)border, (float)(border + row_offset), (float)(ctx->cam.width - 2 * border),
+                                (float)(ctx->cam.height - 2 * border - 2 * row_offset)};
+  if (n_poses > 0)
+    SCHK(ctx, hipMemcpyAsync(ctx->d_ppose, table.data(), (size_t)n_poses * sizeof(ProjectPoseEntry), hipMemcpyHostToDevice,
+                             ctx->stream));
+  if (int rc = reset_front_stats(ctx)) return rc;
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, launch_project_features(ctx->cam, region, n_poses, ctx->d_ppose, cur_frame_id, n, ctx->d_res, ctx->d_proj_tmp,
+                                    ctx->d_keep, ctx->d_groups, ctx->d_res_alt, ctx->d_proj_alt, ctx->d_fstats, ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(ctx->h_fstats, ctx->d_fstats, kFrontWords * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const int* s = ctx->h_fstats;
+  if (s[kFrontBadFrame] != INT_MAX) {  // pfs.at() would throw
+    if (stats) stats->error_feature = s[kFrontBadFrame];
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  if (s[kFrontAssert] != INT_MAX) {
+    if (stats) stats->error_feature = s[kFrontAssert];
+    return FLAME_NLTGV2_ERR_ASSERT;
+  }
+  std::swap(ctx->d_res, ctx->d_res_alt);
+  std::swap(ctx->res_cap, ctx->res_alt_cap);
+  std::swap(ctx->d_proj, ctx->d_proj_alt);
+  std::swap(ctx->proj_cap, ctx->proj_alt_cap);
+  ctx->n_res = ctx->n_proj = s[kFrontCount];
+  if (stats) stats->num_features = s[kFrontCount];
+  return 0;
+}
+
+int flame_stereo_get_projected(flame_stereo_ctx* ctx, int max_feats, flame_stereo_feature* feats, int* n_feats) {
+  if (int rc = enter(ctx)) return rc;
+  if (n_feats) *n_feats = ctx->n_proj;
+  if (!feats) return 0;
+  if (max_feats < ctx->n_proj) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->n_proj > 0)
+    SCHK(ctx, hipMemcpy(feats, ctx->d_proj, (size_t)ctx->n_proj * sizeof(StereoFeature), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int flame_stereo_projected_device(flame_stereo_ctx* ctx, void** feats_device, int* n_feats) {
+  if (!ctx) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (feats_device) *feats_device = ctx->d_proj;
+  if (n_feats) *n_feats = ctx->n_proj;
+  return 0;
+}
+
+int flame_stereo_detect_features(flame_stereo_ctx* ctx, const flame_stereo_params* params,
+                                 const flame_stereo_detect_params* dparams, uint32_t ref_frame_id,
+                                 const float q_ref_to_prev[4], const float t_ref_to_prev[3], const float* idepthmap_host,
+                                 const void* idepthmap_device, int n_mask, const float* mask_xy, uint32_t first_id,
+                                 flame_stereo_feature_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_detect_features");
+  if (int rc = enter(ctx)) return rc;
+  if (stats) stats->num_features = 0, stats->num_examined = 0, stats->error_feature = -1;
+  if (!params || !dparams || !q_ref_to_prev || !t_ref_to_prev || (idepthmap_host && idepthmap_device) || n_mask < -1 ||
+      (n_mask > 0 && !mask_xy) || dparams->detection_win_size < 1)
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  auto fr = ctx->frames.find(ref_frame_id);
+  if (fr == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int width = ctx->cam.width, height = ctx->cam.height;
+  const int border = front_border(*params);
+  if (border < 0) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int row_offset = params->do_letterbox ? height / 3 : 0;
+  DetectGrid G;
+  G.win = dparams->detection_win_size;
+  const float fh = (float)height / G.win, fw = (float)width / G.win;  // utils::fast_ceil (image_utils.h:82-85)
+  G.hc = (int)fh < fh ? (int)fh + 1 : (int)fh;
+  G.wc = (int)fw < fw ? (int)fw + 1 : (int)fw;
+  G.r_lo = border + row_offset, G.r_hi = height - border - row_offset;
+  G.c_lo = border, G.c_hi = width - border;
+  G.g2 = dparams->min_grad_mag * dparams->min_grad_mag;
+  const int n_cells = G.hc * G.wc;
+  if (stats) stats->num_examined = n_cells;
+  // the mask: host points are checked here (the reference indexes its cell mask with them unchecked)
+  const int n_pts = n_mask < 0 ? ctx->n_proj : n_mask;
+  for (int i = 0; i < n_mask; ++i) {
+    const float x = mask_xy[2 * i], y = mask_xy[2 * i + 1];
+    if (!(x >= 0.0f && y >= 0.0f && x < (float)width && y < (float)height)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+    if ((uint32_t)(x / (float)G.win) >= (uint32_t)G.wc || (uint32_t)(y / (float)G.win) >= (uint32_t)G.hc)
+      return FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated; the pinned stats block is reused)
+  const int n_res = ctx->n_res;
+  if (int rc = grow_keep(ctx, &ctx->d_res, &ctx->res_cap, (size_t)n_res + (size_t)n_cells + 1, (size_t)n_res)) return rc;
+  if (int rc = grow(ctx, &ctx->d_cell_key, &ctx->cell_key_cap, (size_t)n_cells + 1)) return rc;
+  if (int rc = grow(ctx, &ctx->d_blocked, &ctx->blocked_cap, (size_t)n_cells + 1)) return rc;
+  if (int rc = grow(ctx, &ctx->d_groups, &ctx->groups_cap, (size_t)n_cells / 256 + 1)) return rc;
+  const float* d_map = (const float*)idepthmap_device;
+  if (idepthmap_host) {
+    if (int rc = grow(ctx, &ctx->d_map, &ctx->map_cap, (size_t)width * height)) return rc;
+    SCHK(ctx, hipMemcpyAsync(ctx->d_map, idepthmap_host, (size_t)width * height * sizeof(float), hipMemcpyHostToDevice,
+                             ctx->stream));
+    d_map = ctx->d_map;
+  }
+  const float* d_mask = nullptr;
+  int mask_stride = 2;
+  if (n_mask > 0) {
+    if (int rc = grow(ctx, &ctx->d_mask, &ctx->mask_cap, (size_t)n_mask * 2)) return rc;
+    SCHK(ctx, hipMemcpyAsync(ctx->d_mask, mask_xy, (size_t)n_mask * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    d_mask = ctx->d_mask;
+  } else if (n_mask < 0 && n_pts > 0) {
+    d_mask = &ctx->d_proj->x;
+    mask_stride = (int)(sizeof(StereoFeature) / sizeof(float));
+  }
+  Geo geo;
+  load_geometry(geo, ctx->cam, q_ref_to_prev, t_ref_to_prev);
+  DetectInit init = {first_id, ref_frame_id, dparams->idepth_init, dparams->idepth_var_init};
+  if (int rc = reset_front_stats(ctx)) return rc;
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, launch_detect_features(G, geo, ctx->cam, fr->second.gx_pad, fr->second.gy_pad, n_pts, d_mask, mask_stride,
+                                   ctx->d_blocked, ctx->d_cell_key, ctx->d_groups, init, d_map, ctx->d_res + n_res, ctx->d_fstats,
+                                   ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(ctx->h_fstats, ctx->d_fstats, kFrontWords * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (also: the host map and mask were pageable memory)
+  const int* s = ctx->h_fstats;
+  if (s[kFrontAssert] != INT_MAX) {  // the records written past n_res are not part of the set
+    if (stats) stats->error_feature = s[kFrontAssert];
+    return FLAME_NLTGV2_ERR_ASSERT;
+  }
+  ctx->n_res = n_res + s[kFrontCount];
+  if (stats) stats->num_features = s[kFrontCount];
+  return 0;
 }
 
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx) {

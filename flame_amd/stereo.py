@@ -1,7 +1,8 @@
 """ctypes mirror of include/flame_stereo.h: the per-feature epipolar inverse-depth update on MI355X.
 
 Mirrors the reference interface of /root/reference/src/flame/flame.cc:1280-1752 (Flame::updateFeatureIDepths,
-Flame::trackFeature) and src/flame/utils/frame.cc:33-71 (Frame::create, level 0).  There is no CPU path: every
+Flame::trackFeature), flame.cc:1754-1860 (Flame::projectFeatures), flame.cc:708-773 + 822-1278 (the detection loop
+and Flame::detectFeatures) and src/flame/utils/frame.cc:33-71 (Frame::create, level 0).  There is no CPU path: every
 call fails with NLTGV2Error when the HIP library or a gfx950 device is missing.
 """
 from __future__ import annotations
@@ -46,6 +47,25 @@ class _Pose(C.Structure):
                 ("q_ref_to_pf", C.c_float * 4), ("t_ref_to_pf", C.c_float * 3)]
 
 
+class DetectParams(C.Structure):
+    """flame_stereo_detect_params: the members of flame::Params detection reads beyond StereoParams; defaults are the
+    reference's (flame_stereo_default_detect_params)."""
+    _fields_ = [("detection_win_size", C.c_int32), ("min_grad_mag", C.c_float), ("idepth_init", C.c_float),
+                ("idepth_var_init", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib().flame_stereo_default_detect_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown detect parameter %r" % k)
+            setattr(self, k, v)
+
+
+class _FeatureStats(C.Structure):
+    _fields_ = [("num_features", C.c_int32), ("num_examined", C.c_int32), ("error_feature", C.c_int32)]
+
+
 class _Stats(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_idepth_updates", "num_fail_max_var", "num_fail_max_dropouts",
                                           "num_fail_ref_patch_grad", "num_fail_ambiguous_match", "num_fail_max_cost",
@@ -58,6 +78,8 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_download_frame", "flame_stereo_update_feature_idepths", "flame_stereo_update_feature_idepths_device",
     "flame_stereo_last_kernel_ms", "flame_stereo_last_hip_error", "flame_stereo_set_features",
     "flame_stereo_update_resident", "flame_stereo_get_features", "flame_stereo_features_device", "flame_stereo_set_option",
+    "flame_stereo_default_detect_params", "flame_stereo_project_features", "flame_stereo_get_projected",
+    "flame_stereo_projected_device", "flame_stereo_detect_features",
 )
 OPT_LANES_PER_FEATURE = 1
 
@@ -94,6 +116,13 @@ def _lib():
             "flame_stereo_set_option": (C.c_int, [ctx, C.c_int, C.c_int]),
             "flame_stereo_last_kernel_ms": (C.c_float, [ctx]),
             "flame_stereo_last_hip_error": (C.c_int, [ctx]),
+            "flame_stereo_default_detect_params": (None, [C.POINTER(DetectParams)]),
+            "flame_stereo_project_features": (C.c_int, [ctx, PP, C.c_uint32, C.c_int, C.POINTER(_Pose),
+                                                        C.POINTER(_FeatureStats)]),
+            "flame_stereo_get_projected": (C.c_int, [ctx, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+            "flame_stereo_projected_device": (C.c_int, [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+            "flame_stereo_detect_features": (C.c_int, [ctx, PP, C.POINTER(DetectParams), C.c_uint32, _FP, _FP, _FP,
+                                                       C.c_void_p, C.c_int, _FP, C.c_uint32, C.POINTER(_FeatureStats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -166,7 +195,7 @@ class FeatureTracker:
             arr[i].frame_id = int(p["id"])
             for name, src, n in (("q_ref_to_new", "q_to_new", 4), ("t_ref_to_new", "t_to_new", 3),
                                  ("q_ref_to_pf", "q_to_pf", 4), ("t_ref_to_pf", "t_to_pf", 3)):
-                v = _f32(p[src], n)
+                v = _f32(p[src], n) if src in p else np.zeros(n, np.float32)  # (project_features reads *_to_new only)
                 for k in range(n):
                     getattr(arr[i], name)[k] = float(v[k])
         return arr
@@ -226,6 +255,71 @@ class FeatureTracker:
         p, n = C.c_void_p(), C.c_int(0)
         self._chk(self._L.flame_stereo_features_device(self._ctx, C.byref(p), C.byref(n)), "features_device")
         return p.value or 0, n.value
+
+    # ---- where the resident features come from and where they go ----
+    def project_features(self, params: StereoParams, cur_frame_id: int, poses, raise_on_error: bool = True):
+        """Flame::projectFeatures (flame.cc:1754-1860) on the resident set: drops the features that leave frame
+        `cur_frame_id` and fills the projected set.  `poses`: list of dicts {id, q_to_new, t_to_new} with
+        T_ref_to_cur = fcur.pose.inverse() * pf.pose (q_to_pf / t_to_pf are optional and not read).  Returns the kept
+        count, or (status, stats dict) when raise_on_error is False."""
+        st = _FeatureStats()
+        rc = self._L.flame_stereo_project_features(self._ctx, C.byref(params), cur_frame_id, len(poses),
+                                                   self._poses(poses), C.byref(st))
+        stats = {n: int(getattr(st, n)) for n, _ in _FeatureStats._fields_}
+        if not raise_on_error:
+            return rc, stats
+        if rc != 0:
+            raise NLTGV2Error(rc, "project_features: %s (feature %d)" % (status_string(rc), stats["error_feature"]))
+        return stats["num_features"]
+
+    def get_projected(self) -> np.ndarray:
+        """The projected set (Flame::feats_in_curr_) of the last project_features."""
+        n = C.c_int(0)
+        self._chk(self._L.flame_stereo_get_projected(self._ctx, 0, None, C.byref(n)), "get_projected")
+        out = np.empty(n.value, FEATURE_DTYPE)
+        self._chk(self._L.flame_stereo_get_projected(self._ctx, n.value, out.ctypes.data, C.byref(n)), "get_projected")
+        return out
+
+    def projected_device(self):
+        p, n = C.c_void_p(), C.c_int(0)
+        self._chk(self._L.flame_stereo_projected_device(self._ctx, C.byref(p), C.byref(n)), "projected_device")
+        return p.value or 0, n.value
+
+    def detect_features(self, params: StereoParams, dparams: DetectParams, ref_frame_id: int, q_ref_to_prev,
+                        t_ref_to_prev, idepthmap=None, mask_xy=None, first_id: int = 0, raise_on_error: bool = True):
+        """Flame::detectFeatures + the detection loop's initialisation on resident frame `ref_frame_id`; the new
+        features are appended to the resident set.  idepthmap: None (all NaN), a (height, width) float32 host array,
+        or an int device address of such a map.  mask_xy: None, an (n, 2) host array of (x, y), or "projected" (the
+        projected set of the last project_features).  Returns the number of new features, or (status, stats dict)
+        when raise_on_error is False."""
+        q, t = _f32(q_ref_to_prev, 4), _f32(t_ref_to_prev, 3)
+        host_map, dev_map = None, None
+        if isinstance(idepthmap, (int, np.integer)) and not isinstance(idepthmap, bool):
+            dev_map = C.c_void_p(int(idepthmap))
+        elif idepthmap is not None:
+            host_map = np.ascontiguousarray(idepthmap, dtype=np.float32)
+            if host_map.shape != (self.height, self.width):
+                raise ValueError("idepthmap must be %dx%d" % (self.height, self.width))
+        if isinstance(mask_xy, str):
+            if mask_xy != "projected":
+                raise ValueError("mask_xy must be None, an (n, 2) array or 'projected'")
+            n_mask, mask = -1, None
+        elif mask_xy is None:
+            n_mask, mask = 0, None
+        else:
+            mask = np.ascontiguousarray(mask_xy, dtype=np.float32).reshape(-1, 2)
+            n_mask = mask.shape[0]
+        st = _FeatureStats()
+        rc = self._L.flame_stereo_detect_features(
+            self._ctx, C.byref(params), C.byref(dparams), ref_frame_id, q.ctypes.data_as(_FP), t.ctypes.data_as(_FP),
+            host_map.ctypes.data_as(_FP) if host_map is not None else None, dev_map,
+            n_mask, mask.ctypes.data_as(_FP) if mask is not None and n_mask > 0 else None, first_id, C.byref(st))
+        stats = {n: int(getattr(st, n)) for n, _ in _FeatureStats._fields_}
+        if not raise_on_error:
+            return rc, stats
+        if rc != 0:
+            raise NLTGV2Error(rc, "detect_features: %s (pixel %d)" % (status_string(rc), stats["error_feature"]))
+        return stats["num_features"]
 
     def set_lanes_per_feature(self, lanes: int):
         self._chk(self._L.flame_stereo_set_option(self._ctx, OPT_LANES_PER_FEATURE, int(lanes)), "set_option")

@@ -7,6 +7,15 @@
 //              tracker.addFrame(frame->id, frame->img[0].data, frame->img[0].step);   // where Frame::create ran
 //              bool ok = tracker.updateFeatureIDepths(params, pfs, *fnew_, *curr_pf_, &feats_, &stats);
 //
+//   reference  Flame::projectFeatures(params, K, Kinv, pfs, fcur, &feats, &feats_in_curr, &stats)  (flame.cc:1754, call
+//              sites flame.cc:222 and 277)
+//   here       tracker.projectFeatures(params, pfs, *fcur, &feats_, &feats_in_curr_);
+//   reference  Flame::detectFeatures(params, K, Kinv, fref, fprev, fcmp, idepthmap, curr_feats, ...) + the feature
+//              initialisation of Flame::detectionLoop (flame.cc:708-773)
+//   here       tracker.detectFeatures(params, fref, fprev, idepthmap, curr_feats, &feat_count_, &new_feats);
+//   (and the resident-set forms projectFeatures(params, pfs, fcur) / detectFeaturesResident(...), which keep the
+//   features on the device)
+//
 // Works with the reference's own types through templates (no Eigen/Sophus/OpenCV headers are needed here):
 //   Matrix3    anything with operator()(row, col)                      (Eigen::Matrix3f)
 //   SE3        .inverse(), operator*, .unit_quaternion().{w,x,y,z}(), .translation()(i)   (Sophus::SE3f)
@@ -63,6 +72,19 @@ inline flame_stereo_params toStereoParams(const FlameParams& p) {
   o.z_win_size = p.zparams.win_size;
   o.pixel_var = p.zparams.pixel_var;
   o.epipolar_line_var = p.zparams.epipolar_line_var;
+  return o;
+}
+
+// flame::Params -> flame_stereo_detect_params (the members detectFeatures and detectionLoop read beyond
+// toStereoParams: params.h:39, 48, 60, 61).  Note: Params::min_grad_mag, not fparams.min_grad_mag.
+template <class FlameParams>
+inline flame_stereo_detect_params toDetectParams(const FlameParams& p) {
+  flame_stereo_detect_params o;
+  flame_stereo_default_detect_params(&o);
+  o.detection_win_size = p.detection_win_size;
+  o.min_grad_mag = p.min_grad_mag;
+  o.idepth_init = p.idepth_init;
+  o.idepth_var_init = p.idepth_var_init;
   return o;
 }
 
@@ -153,9 +175,81 @@ class FeatureTracker {
                                 feats->empty() ? nullptr : adoptFeatures(feats->data()), (int)feats->size(), stats);
   }
 
+  // ---- projectFeatures / detectFeatures ----
+  // Resident forms: on the resident set (flame_stereo_set_features / update_resident), which stays on the device.
+  // == Flame::projectFeatures on feats_; the projected set (feats_in_curr_) stays resident too (projected()).  Returns
+  // the number of features kept.
+  template <class FlameParams, class FrameMap, class Frame>
+  int projectFeatures(const FlameParams& params, const FrameMap& pfs, const Frame& fcur) {
+    std::vector<flame_stereo_pose> poses;
+    for (typename FrameMap::const_iterator it = pfs.begin(); it != pfs.end(); ++it)
+      poses.push_back(makePose(*it->second, fcur, fcur));  // (only the *_to_new half is read)
+    const flame_stereo_params sp = toStereoParams(params);
+    flame_stereo_feature_stats st;
+    const int rc = flame_stereo_project_features(ctx_, &sp, fcur.id, (int)poses.size(), poses.empty() ? nullptr : poses.data(),
+                                                 &st);
+    check(rc, st.error_feature, "flame_stereo_project_features");
+    return st.num_features;
+  }
+  // == Flame::detectFeatures + detectionLoop's initialisation; the new features are appended to the resident set with
+  // ids *feat_count, *feat_count + 1, ... (feat_count_++).  idepthmap_device: width x height floats on the device, or
+  // NULL; mask_with_projected: the projected set of the last projectFeatures as curr_feats (else no mask).  Returns the
+  // number of new features.
+  template <class FlameParams, class Frame>
+  int detectFeaturesResident(const FlameParams& params, const Frame& fref, const Frame& fprev, const void* idepthmap_device,
+                             bool mask_with_projected, uint32_t* feat_count) {
+    return detect(params, fref, fprev, nullptr, idepthmap_device, mask_with_projected ? -1 : 0, nullptr, feat_count);
+  }
+
+  // Host forms, in the reference's argument shape (they use the resident set as their working storage: it holds `feats`
+  // after projectFeatures and the new features after detectFeatures).
+  template <class FlameParams, class FrameMap, class Frame, class Feature>
+  void projectFeatures(const FlameParams& params, const FrameMap& pfs, const Frame& fcur, std::vector<Feature>* feats,
+                       std::vector<Feature>* feats_in_curr) {
+    check(flame_stereo_set_features(ctx_, (int)feats->size(), feats->empty() ? nullptr : adoptFeatures(feats->data())), -1,
+          "flame_stereo_set_features");
+    const int n = projectFeatures(params, pfs, fcur);
+    feats->resize(n);
+    feats_in_curr->resize(n);
+    int got = 0;
+    check(flame_stereo_get_features(ctx_, n, n ? adoptFeatures(feats->data()) : nullptr, &got), -1, "flame_stereo_get_features");
+    check(flame_stereo_get_projected(ctx_, n, n ? adoptFeatures(feats_in_curr->data()) : nullptr, &got), -1,
+          "flame_stereo_get_projected");
+  }
+  // idepthmap: width x height floats in host memory (the reference's fref.idepthmap[0]), or NULL (all NaN).
+  // curr_feats: anything with .x / .y per element (std::vector<cv::Point2f>).  new_feats receives the
+  // FeatureWithIDepth's the detection loop would push into new_feats_.
+  template <class FlameParams, class Frame, class Point, class Feature>
+  void detectFeatures(const FlameParams& params, const Frame& fref, const Frame& fprev, const float* idepthmap,
+                      const std::vector<Point>& curr_feats, uint32_t* feat_count, std::vector<Feature>* new_feats) {
+    std::vector<float> mask(2 * curr_feats.size());
+    for (size_t i = 0; i < curr_feats.size(); ++i) mask[2 * i] = curr_feats[i].x, mask[2 * i + 1] = curr_feats[i].y;
+    check(flame_stereo_set_features(ctx_, 0, nullptr), -1, "flame_stereo_set_features");
+    const int n = detect(params, fref, fprev, idepthmap, nullptr, (int)curr_feats.size(), mask.empty() ? nullptr : mask.data(),
+                         feat_count);
+    new_feats->resize(n);
+    int got = 0;
+    check(flame_stereo_get_features(ctx_, n, n ? adoptFeatures(new_feats->data()) : nullptr, &got), -1,
+          "flame_stereo_get_features");
+  }
+
   flame_stereo_ctx* handle() const { return ctx_; }
 
  private:
+  template <class FlameParams, class Frame>
+  int detect(const FlameParams& params, const Frame& fref, const Frame& fprev, const float* map_host, const void* map_device,
+             int n_mask, const float* mask, uint32_t* feat_count) {
+    float q[4], t[3];
+    toQuatTrans(fprev.pose.inverse() * fref.pose, q, t);  // T_ref_to_prev (flame.cc:1012)
+    const flame_stereo_params sp = toStereoParams(params);
+    const flame_stereo_detect_params dp = toDetectParams(params);
+    flame_stereo_feature_stats st;
+    const int rc = flame_stereo_detect_features(ctx_, &sp, &dp, fref.id, q, t, map_host, map_device, n_mask, mask, *feat_count,
+                                                &st);
+    check(rc, st.error_feature, "flame_stereo_detect_features");
+    *feat_count += (uint32_t)st.num_features;
+    return st.num_features;
+  }
   static void check(int rc, int feature, const char* what) {
     if (rc != 0) throw StereoError(rc, feature, what);
   }

@@ -142,12 +142,74 @@ int flame_stereo_update_feature_idepths_device(flame_stereo_ctx* ctx, const flam
  *   set_features     replaces the resident set (host array of n_feats records);
  *   update_resident  Flame::updateFeatureIDepths on it; `stats` NULL = enqueue only (results are ordered on the stream);
  *   get_features     copies it back (feats may be NULL to query the count);
- *   features_device  its device address and count (valid until the next set_features). */
+ *   features_device  its device address and count (valid until the next set_features, project_features or
+ *                    detect_features). */
 int flame_stereo_set_features(flame_stereo_ctx* ctx, int n_feats, const flame_stereo_feature* feats);
 int flame_stereo_update_resident(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t new_frame_id,
                                  uint32_t curr_pf_id, int n_poses, const flame_stereo_pose* poses, flame_stereo_stats* stats);
 int flame_stereo_get_features(flame_stereo_ctx* ctx, int max_feats, flame_stereo_feature* feats, int* n_feats);
 int flame_stereo_features_device(flame_stereo_ctx* ctx, void** feats_device, int* n_feats);
+
+/* ---- Where the resident features come from and where they go ----------------------------------------------------
+ * Flame::projectFeatures (flame.cc:1754-1860) and Flame::detectFeatures + the feature initialisation of
+ * Flame::detectionLoop (flame.cc:822-1278, the live single-pass part; flame.cc:736-757), on the resident set.  Both
+ * calls enqueue on the context's stream and wait once, to return the new counts (the host needs them for the next
+ * update_resident); there is no enqueue-only form.  Both leave the resident set and the projected set unchanged when
+ * they fail.  Both may move the resident set: the address from flame_stereo_features_device is valid until the next
+ * set_features, project_features or detect_features (and flame_stereo_projected_device's until the next
+ * project_features). */
+
+/* The members of flame::Params detection reads beyond flame_stereo_params (whose do_letterbox, rescale_factor_max and
+ * win_size it also reads), with the reference's defaults (flame_stereo_default_detect_params). */
+typedef struct flame_stereo_detect_params {
+  int32_t detection_win_size; /* Params::detection_win_size  16    (params.h:48): cells are win x win pixels */
+  float min_grad_mag;         /* Params::min_grad_mag        5     (params.h:39) -- not fparams.min_grad_mag */
+  float idepth_init;          /* Params::idepth_init         0.01  (params.h:60) */
+  float idepth_var_init;      /* Params::idepth_var_init     0.25  (params.h:61) */
+} flame_stereo_detect_params;
+void flame_stereo_default_detect_params(flame_stereo_detect_params* p);
+
+typedef struct flame_stereo_feature_stats {
+  int32_t num_features;  /* project: features kept; detect: new features appended */
+  int32_t num_examined;  /* project: resident features examined; detect: cells of the grid (hc x wc) */
+  int32_t error_feature; /* -1; project: the lowest feature index that hit a reference assert or names an unknown
+                            frame; detect: the lowest row-major pixel index (row * width + col) whose
+                            referenceEpiline asserted */
+} flame_stereo_feature_stats;
+
+/* Flame::projectFeatures(params, K, Kinv, pfs, fcur, &feats_, &feats_in_curr_) on the resident set.  `poses` holds one
+ * entry per pose-frame the features may refer to, with q/t_ref_to_new = fcur.pose.inverse() * pf.pose (the *_to_pf
+ * members are not read).  Every feature, valid or not, must name a pose (pfs.at(), flame.cc:1784), else
+ * FLAME_NLTGV2_ERR_INVALID_ARG; a valid feature whose projection asserts in the reference (negative or NaN idepth_mu)
+ * gives FLAME_NLTGV2_ERR_ASSERT.  The features that stay inside the valid region in front of the camera are kept, in
+ * order, in the resident set (unchanged records) and in the projected set (feats_in_curr: valid = 1, the same id and
+ * num_updates, frame_id = cur_frame_id, the projected xy and idepth_mu, idepth_var scaled by (cur/ref)^4;
+ * num_dropouts = search_status = 0, where the reference leaves the vector's previous contents).  The frames need not
+ * be resident.  `stats` may be NULL. */
+int flame_stereo_project_features(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t cur_frame_id,
+                                  int n_poses, const flame_stereo_pose* poses, flame_stereo_feature_stats* stats);
+/* The projected set of the last project_features (empty before the first): copy back (feats NULL = count only), or its
+ * device address and count. */
+int flame_stereo_get_projected(flame_stereo_ctx* ctx, int max_feats, flame_stereo_feature* feats, int* n_feats);
+int flame_stereo_projected_device(flame_stereo_ctx* ctx, void** feats_device, int* n_feats);
+
+/* Flame::detectFeatures on resident frame `ref_frame_id` (its gradients, built by add_frame) with the geometry of
+ * T_ref_to_prev = fprev.pose.inverse() * fref.pose, then the detection loop's initialisation of every new feature:
+ * id = first_id + k (k-th new feature, in row-major cell order), frame_id = ref_frame_id, xy = the cell's best pixel,
+ * idepth_mu = idepthmap(y, x) unless NaN, else idepth_init, idepth_var = idepth_var_init, valid = 1, counters 0.
+ * The new features are appended to the resident set (feats_.insert(feats_.end(), new_feats_) at the next update()).
+ *   idepthmap   width x height floats, row-major: in host memory (idepthmap_host), in device memory
+ *               (idepthmap_device, e.g. the rasteriser's map), or neither (all NaN: every feature gets idepth_init).
+ *   mask        the points whose cells get no new feature (curr_feats): n_mask (x, y) pairs in host memory, or
+ *               n_mask = -1 for the projected set of the last project_features (data.ref_xy, flame.cc:474-477).  A
+ *               host point outside the image is FLAME_NLTGV2_ERR_INVALID_ARG.
+ * A pixel that passes the gradient test where the reference's referenceEpiline asserts (zero translation) gives
+ * FLAME_NLTGV2_ERR_ASSERT and appends nothing.  `stats` may be NULL. */
+int flame_stereo_detect_features(flame_stereo_ctx* ctx, const flame_stereo_params* params,
+                                 const flame_stereo_detect_params* dparams, uint32_t ref_frame_id,
+                                 const float q_ref_to_prev[4], const float t_ref_to_prev[3], const float* idepthmap_host,
+                                 const void* idepthmap_device, int n_mask, const float* mask_xy, uint32_t first_id,
+                                 flame_stereo_feature_stats* stats);
 
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
@@ -155,7 +217,8 @@ int flame_stereo_features_device(flame_stereo_ctx* ctx, void** feats_device, int
 enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1 };
 int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value);
 
-/* Device time of the last update kernel in milliseconds (HIP events on the context's stream); < 0 if none. */
+/* Device time of the last update kernel (or of the kernels of the last project_features / detect_features) in
+ * milliseconds (HIP events on the context's stream); < 0 if none. */
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx);
 int flame_stereo_last_hip_error(const flame_stereo_ctx* ctx);
 
