@@ -169,6 +169,7 @@ struct flame_nltgv2_ctx {
   PhotoGeometry photo_geo{};
   float photo_scale = 1.0f;
   int photo_border = 3;
+  bool photo_fresh = false;     // photo_err holds the residual of the current pos / x / images / target (else photo_residual_last sweeps)
   float* export_ptr = nullptr;  // flame_nltgv2_set_export_target: every run also leaves x * scale there
   float export_scale = 1.0f;
   int opt_fault = 0;     // test hook: > 0 = the next persistent runs time out after this many spins
@@ -475,6 +476,12 @@ constexpr size_t kMaxChain = 256;  // operations enqueued behind an unchecked pe
 bool persistent_eligible(flame_nltgv2_ctx* ctx, int n);
 int prepare_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n);
 PhotoFuse photo_target(const flame_nltgv2_ctx* ctx);
+// Declared right behind enter() by every call that can change pos, x, the graph, the images or the standing target: whatever the
+// call goes on to do (settle, redo an expired chain, then change the state), the residual in photo_err no longer describes it.
+struct PhotoStale {
+  flame_nltgv2_ctx* ctx;
+  ~PhotoStale() { ctx->photo_fresh = false; }
+};
 int enqueue_photo_sweep(flame_nltgv2_ctx* ctx, bool packed_current);
 int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n);
 // reads the error word; rolls a failed persistent run back and redoes it.  unpack_behind: the unpack of the state is enqueued before the

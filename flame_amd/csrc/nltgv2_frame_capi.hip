@@ -168,8 +168,10 @@ int flame_nltgv2_photo_set_images(flame_nltgv2_ctx* ctx, const uint8_t* ref, con
                                   int step_bytes) {
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (!ref || !cmp || rows < 2 || cols < 2 || step_bytes < cols) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  const size_t bytes = (size_t)rows * (size_t)step_bytes;
+  // the last row ends at its cols-th byte: the caller's buffer need not hold that row's padding
+  const size_t bytes = (size_t)(rows - 1) * (size_t)step_bytes + (size_t)cols;
   HIPCHK(ctx, wait_solver_stream(ctx));
   rc = ensure(ctx, ctx->img_ref, bytes + 16);
   if (!rc) rc = ensure(ctx, ctx->img_cmp, bytes + 16);
@@ -185,6 +187,7 @@ int flame_nltgv2_photo_residual(flame_nltgv2_ctx* ctx, const float* KRKinv, cons
                                 int border, float* err_out) {
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (it writes photo_err with the caller's target, not the standing one)
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (!KRKinv || !Kt || !err_out || border < 1 || ctx->img_rows == 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   rc = ensure_canon(ctx);
@@ -207,6 +210,7 @@ int flame_nltgv2_photo_fuse(flame_nltgv2_ctx* ctx, const float* KRKinv, const fl
                             int enable) {
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (!enable) {
     ctx->photo_fused = false;
     return FLAME_NLTGV2_OK;
@@ -230,6 +234,11 @@ int flame_nltgv2_photo_residual_last(flame_nltgv2_ctx* ctx, float* err_out) {
   if (!ctx->photo_fused || !err_out) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (ctx->pending.active) {
     rc = finish(ctx);
+    if (rc) return rc;
+  }
+  if (!ctx->photo_fresh) {  // no run since the graph, the state, the images or the target changed: the stand-alone sweep, never stale values
+    rc = ensure_canon(ctx);
+    if (!rc) rc = enqueue_photo_sweep(ctx, false);
     if (rc) return rc;
   }
   const size_t fV = sizeof(float) * (size_t)ctx->L.V;

@@ -13,6 +13,7 @@ int flame_nltgv2_upload_graph(flame_nltgv2_ctx* ctx, const flame_nltgv2_graph* g
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_upload_graph");
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (!g) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const int32_t V = g->V, E = g->E;
   if (V < 0 || E < 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
@@ -372,6 +373,7 @@ int flame_nltgv2_sync_graph(flame_nltgv2_ctx* ctx, const flame_nltgv2_sync_input
   int rc = enter(ctx);
   if (!rc) rc = sync_input_ok(ctx, in);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (ctx->opt_sync_path != 1) {
     bool applicable = false, done = false;
     rc = topo_prepare(ctx, in, &applicable);
@@ -440,6 +442,7 @@ int flame_nltgv2_sync_commit(flame_nltgv2_ctx* ctx) {
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_sync_commit");
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   flame_nltgv2_ctx::PreparedSync& P = ctx->prepared;
   if (!P.active || P.topo != ctx->topo || !ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // nothing prepared (or cancelled)
   const char* base = P.device ? static_cast<const char*>(ctx->stage[1].h) : ctx->prep_host.data();
@@ -464,6 +467,7 @@ int flame_nltgv2_project_graph(flame_nltgv2_ctx* ctx, const flame_nltgv2_project
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_project_graph");
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (!pr || !(graph_scale > 0.0f) || (ctx->L.V > 0 && !keep_out)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const size_t V = (size_t)ctx->L.V;
@@ -523,6 +527,7 @@ int flame_nltgv2_rescale_data(flame_nltgv2_ctx* ctx, float graph_scale, float* n
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_rescale_data");
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (!new_graph_scale || !p || ctx->L.V <= 0 || !(graph_scale > 0.0f)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   rc = ensure_canon(ctx);
@@ -592,6 +597,7 @@ int flame_nltgv2_update_data(flame_nltgv2_ctx* ctx, const float* data_term, cons
 int flame_nltgv2_upload_state(flame_nltgv2_ctx* ctx, const flame_nltgv2_graph* s) {
   int rc = enter(ctx);
   if (rc) return rc;
+  PhotoStale stale_{ctx};  // (photo_err no longer describes what this call leaves)
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (!s) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   rc = ensure_canon(ctx);

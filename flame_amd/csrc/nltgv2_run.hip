@@ -290,6 +290,7 @@ int enqueue_photo_sweep(flame_nltgv2_ctx* ctx, bool packed_current) {
     LAUNCHCHK(ctx, launch_photo_residual(ctx->c, f.graph_scale, f.geo, f.ref, f.cmp, f.rows, f.cols, f.step, f.border, f.err,
                                          ctx->stream));
   }
+  ctx->photo_fresh = true;
   return 0;
 }
 
@@ -671,6 +672,7 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
         op.dst = ctx->export_ptr, op.scale = ctx->export_scale;  // the standing export target THIS run was enqueued with
         ctx->pending.ops.push_back(op);
       }
+      ctx->photo_fresh = photo_target(ctx).err != nullptr;  // (the epilogue of this run writes it)
       ctx->open_inflight = open_run, ctx->open_stop_sent = false;
       if (open_run) ctx->want_open = 2;
       if (!open_run && ctx->replaying == 0) ctx->iters_total += n;  // (an open run: counted by finish(), which learns how far it went)
@@ -1076,6 +1078,7 @@ int flame_nltgv2_step(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p) { ret
   int NAME(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p) {               \
     int rc = enter(ctx);                                                        \
     if (rc) return rc;                                                          \
+    PhotoStale stale_{ctx};                                                     \
     if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);          \
     if (!params_ok(p)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);          \
     rc = ensure_canon(ctx);                                                     \

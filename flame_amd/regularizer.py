@@ -38,6 +38,11 @@ VERTEX_STATE = ("x", "w1", "w2", "x_bar", "w1_bar", "w2_bar", "x_prev", "w1_prev
 EDGE_STATE = ("q1", "q2", "q3")
 
 
+def _rows_contiguous_u8(a) -> bool:
+    """A 2-D u8 array whose rows are contiguous and lie at least a row's width apart, in order."""
+    return a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and a.strides[0] >= max(a.shape[1], 1)
+
+
 class NLTGV2Error(RuntimeError):
     def __init__(self, status: int, what: str):
         super().__init__(f"{what}: status {status} ({status_string(status)})")
@@ -514,10 +519,13 @@ class Regularizer:
 
     # ---- config-5 epilogue ----------------------------------------------------------------------
     def photo_set_images(self, ref, cmp):
-        ref = np.ascontiguousarray(ref, np.uint8)
-        cmp = np.ascontiguousarray(cmp, np.uint8)
+        """Row-strided u8 views with contiguous rows (e.g. img[:, :cols] of a padded buffer) go as they are, strides[0] as the
+        row step; anything else is copied into contiguous rows first."""
+        ref, cmp = np.asarray(ref), np.asarray(cmp)
         if ref.shape != cmp.shape or ref.ndim != 2:
             raise ValueError("two equally sized single-channel u8 images expected")
+        if not (_rows_contiguous_u8(ref) and _rows_contiguous_u8(cmp) and ref.strides[0] == cmp.strides[0]):
+            ref, cmp = np.ascontiguousarray(ref, np.uint8), np.ascontiguousarray(cmp, np.uint8)
         U8 = C.POINTER(C.c_uint8)
         self._chk(self._L.flame_nltgv2_photo_set_images(self._ctx, ref.ctypes.data_as(U8), cmp.ctypes.data_as(U8),
                                                          ref.shape[0], ref.shape[1], ref.strides[0]), "photo_set_images")

@@ -289,7 +289,8 @@ int flame_delaunay_triangulate(const float* xy, int32_t n, int32_t* triangles, i
  * EpipolarGeometry::project (stereo/epipolar_geometry.h:127-143) and utils::bilinearInterp<uint8_t,float>
  * (utils/image_utils.h:230-255).  err[v] = |I_cmp(project(pos_v, x_v*graph_scale)) - I_ref(pos_v)|, NaN
  * where either pixel is outside [border, size-border).  An epilogue: it never modifies x.
- * KRKinv: 9 floats row-major, Kt: 3 floats (EpipolarGeometry::loadGeometry, h:88-93). */
+ * KRKinv: 9 floats row-major, Kt: 3 floats (EpipolarGeometry::loadGeometry, h:88-93).
+ * Images: rows of cols bytes, step_bytes >= cols apart; (rows - 1) * step_bytes + cols bytes are read. */
 int flame_nltgv2_photo_set_images(flame_nltgv2_ctx* ctx, const uint8_t* ref, const uint8_t* cmp, int rows, int cols,
                                   int step_bytes);
 int flame_nltgv2_photo_residual(flame_nltgv2_ctx* ctx, const float* KRKinv, const float* Kt, float graph_scale,
@@ -298,8 +299,10 @@ int flame_nltgv2_photo_residual(flame_nltgv2_ctx* ctx, const float* KRKinv, cons
  * data-term residual fused into the primal step"): while enabled, every run()/run_async() leaves the residual of its
  * final x in a device buffer -- the persistent kernels evaluate it in their epilogue, right after the last primal
  * step, from the registers that hold x; the one-launch-per-step path appends one sweep.  It never feeds back into x.
- * flame_nltgv2_photo_residual_last copies that buffer out (V floats, caller's vertex order; no kernel is launched).
- * The images are those of flame_nltgv2_photo_set_images; enable = 0 switches it off. */
+ * flame_nltgv2_photo_residual_last copies that buffer out (V floats, caller's vertex order; no kernel is launched) --
+ * unless the graph, the state, the images or the target changed after the last run (upload, sync, projection, rescale,
+ * single solver steps, new images, photo_fuse again) or flame_nltgv2_photo_residual used the buffer for its own target:
+ * then it computes the residual of the current pos and x for the standing target with the stand-alone sweep first.  The images are those of flame_nltgv2_photo_set_images; enable = 0 switches it off. */
 int flame_nltgv2_photo_fuse(flame_nltgv2_ctx* ctx, const float* KRKinv, const float* Kt, float graph_scale, int border,
                             int enable);
 int flame_nltgv2_photo_residual_last(flame_nltgv2_ctx* ctx, float* err_out);

@@ -200,8 +200,11 @@ def photo_residual(pos, x, graph_scale, KRKinv, Kt, ref, cmp, border):
     x = np.ascontiguousarray(x, np.float32)
     k = np.ascontiguousarray(KRKinv, np.float32).reshape(9)
     t = np.ascontiguousarray(Kt, np.float32).reshape(3)
-    ref = np.ascontiguousarray(ref, np.uint8)
-    cmp = np.ascontiguousarray(cmp, np.uint8)
+    ref, cmp = np.asarray(ref), np.asarray(cmp)
+    # row-strided views (contiguous rows, strides[0] >= cols) are read in place, strides[0] as the step, like the device's copy
+    if ref.strides != cmp.strides or not all(a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and a.strides[0] >= a.shape[1]
+                                              for a in (ref, cmp)):
+        ref, cmp = np.ascontiguousarray(ref, np.uint8), np.ascontiguousarray(cmp, np.uint8)
     assert ref.shape == cmp.shape and ref.strides == cmp.strides
     err = np.empty(x.shape[0], np.float32)
     U8 = C.POINTER(C.c_uint8)
