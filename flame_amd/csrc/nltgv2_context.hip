@@ -519,6 +519,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   ok = ok && hipEventCreateWithFlags(&ctx->ev_snap, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_raster_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_topo_ready, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreate(&ctx->ev_mesh0) == hipSuccess && hipEventCreate(&ctx->ev_mesh1) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_expanded, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[0], hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[1], hipEventDisableTiming) == hipSuccess;
@@ -563,6 +564,9 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   for (auto& b : ctx->nx) ctx->all.push_back(&b);
   for (auto& b : ctx->ex) ctx->all.push_back(&b);
   ctx->all.push_back(&ctx->pos_undo);
+  for (DevBuf* b : {&ctx->m_P, &ctx->m_idepth, &ctx->m_normals, &ctx->m_tvalid, &ctx->m_nvalid, &ctx->m_tnormal, &ctx->m_offset, &ctx->m_cursor,
+                    &ctx->m_incident, &ctx->m_keys, &ctx->m_img, &ctx->m_cov})
+    ctx->all.push_back(b);
   ctx->all.push_back(&ctx->stop_dev);
   ctx->all.push_back(&ctx->place_patch_nx), ctx->all.push_back(&ctx->place_fill_nx);
   for (auto& b : ctx->sp_v) ctx->all.push_back(&b);
@@ -598,6 +602,9 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
   for (hipEvent_t e : ctx->ev_run)
     if (e) (void)hipEventDestroy(e);
   if (ctx->h_img) (void)hipHostFree(ctx->h_img);
+  if (ctx->h_mesh) (void)hipHostFree(ctx->h_mesh);
+  if (ctx->ev_mesh0) (void)hipEventDestroy(ctx->ev_mesh0);
+  if (ctx->ev_mesh1) (void)hipEventDestroy(ctx->ev_mesh1);
   if (ctx->h_dims) (void)hipHostFree(ctx->h_dims);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -307,6 +307,21 @@ struct flame_nltgv2_ctx {
   size_t h_img_cap = 0;
   int map_rows = 0, map_cols = 0;     // the dense map resident in r_img (0: none)
   int img_pending_rows = 0, img_pending_cols = 0;  // the map an interpolate_mesh_begin left in h_img for its _end (0: none pending)
+  // flame_nltgv2_mesh_outputs_begin / _end (mesh_kernels.hip): the triangles interpolate_mesh[_begin] left in r_tris (-1: none, or
+  // they index other arrays than the graph's) and the topology their indices were checked against; scratch, outputs and the
+  // filtered map with buffers of their own (r_img / h_img stay the unfiltered map's)
+  int32_t tris_T = -1;
+  uint64_t tris_topo = ~0ull;
+  DevBuf m_P, m_idepth, m_normals, m_tvalid, m_nvalid, m_tnormal, m_offset, m_cursor, m_incident, m_keys, m_img, m_cov;
+  char* h_mesh = nullptr;             // pinned: normals, vtx_idepth, {n_valid, coverage}, filtered map, tri_valid
+  size_t h_mesh_cap = 0;
+  struct MeshPending {
+    bool active = false;
+    int32_t V = 0, T = 0;
+    int rows = 0, cols = 0;           // of the filtered map (0: not asked for)
+    size_t off_idepth = 0, off_counts = 0, off_map = 0, off_valid = 0;  // byte offsets in h_mesh (normals at 0)
+  } mesh_pending;
+  hipEvent_t ev_mesh0 = nullptr, ev_mesh1 = nullptr;  // timing events around the stage on the side stream
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

@@ -3,7 +3,24 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include "mesh_kernels.h"
 #include "nltgv2_context.hpp"
+
+// Which state a mesh stage on the side stream describes (interpolate_mesh_begin, mesh_outputs_begin), and the wait that lets `rs` read
+// it in the canonical arrays.  FLAME_NLTGV2_OPT_MESH_STATE = 1 and runs enqueued since the last settle: the state that settle left,
+// which the canonical arrays still hold (enqueue_run recorded ev_snap behind their last writer); the runs in flight are not waited
+// for.  Otherwise the runs are settled and the state unpacked; the caller may enqueue the next run as soon as this returns.
+static int mesh_state_on(flame_nltgv2_ctx* ctx, hipStream_t rs) {
+  if (ctx->opt_mesh_state == 1 && !ctx->canon_valid && ctx->snap_topo == ctx->topo) {
+    HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_snap, 0));
+    return FLAME_NLTGV2_OK;
+  }
+  const int rc = ensure_canon(ctx);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_canon, ctx->stream));
+  HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_canon, 0));
+  return FLAME_NLTGV2_OK;
+}
 
 extern "C" {
 
@@ -86,18 +103,10 @@ int flame_nltgv2_interpolate_mesh_begin(flame_nltgv2_ctx* ctx, const int32_t* tr
     HIPCHK(ctx, hipMemcpyAsync(d_tv, tri_valid, (size_t)T, hipMemcpyHostToDevice, rs));
   }
   tr_a = tr_us();
-  if (ctx->opt_mesh_state == 1 && !ctx->canon_valid && ctx->snap_topo == ctx->topo) {
-    // FLAME_NLTGV2_OPT_MESH_STATE = 1 and runs enqueued since the last settle: the map is of the state that settle left, which the
-    // canonical arrays still hold (enqueue_run recorded ev_snap behind their last writer); the runs in flight are not waited for
-    tr_b = tr_us();
-    HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_snap, 0));
-  } else {
-    rc = ensure_canon(ctx);  // ... it stops here ...
-    if (rc) return rc;
-    tr_b = tr_us();
-    HIPCHK(ctx, hipEventRecord(ctx->ev_canon, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(rs, ctx->ev_canon, 0));  // ... and may go on as soon as the caller enqueues the next run
-  }
+  ctx->tris_T = T, ctx->tris_topo = ctx->topo;  // (what flame_nltgv2_mesh_outputs_begin(triangles = NULL) refers to)
+  rc = mesh_state_on(ctx, rs);  // ... it stops here, and may go on as soon as the caller enqueues the next run
+  if (rc) return rc;
+  tr_b = tr_us();
   LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.x, graph_scale, nullptr, d_tv,
                                          (unsigned long long*)ctx->r_keys.p, (float*)ctx->r_img.p, (int*)ctx->r_cov.p, rows, cols, rs));
   // the rasteriser's kernels are the last readers of the canonical arrays (and the writers of the resident map): whoever rewrites those
@@ -140,6 +149,7 @@ int flame_nltgv2_interpolate_mesh(flame_nltgv2_ctx* ctx, const int32_t* triangle
   rc = interpolate_common(ctx, triangles, T, ctx->L.V, nullptr, tri_valid, ctx->c.pos, ctx->c.x, graph_scale, rows,
                           cols, idepthmap_out, coverage_out);
   if (!rc) ctx->map_rows = rows, ctx->map_cols = cols;  // (the map stays on the device: flame_nltgv2_sync_input.init_from_map)
+  ctx->tris_T = rc ? -1 : T, ctx->tris_topo = ctx->topo;
   return rc;
 }
 
@@ -160,8 +170,190 @@ int flame_nltgv2_interpolate_mesh_arrays(flame_nltgv2_ctx* ctx, const int32_t* t
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
   ctx->map_rows = ctx->map_cols = 0;  // (r_img will hold an image of the caller's arrays, not the graph's map)
+  ctx->tris_T = -1;                   // (... and r_tris triangles of those arrays)
   return interpolate_common(ctx, triangles, T, V, vtx_valid, tri_valid, (const float2*)ctx->r_vtx.p,
                             (const float*)ctx->r_val.p, 1.0f, rows, cols, img_out, coverage_out);
+}
+
+void flame_nltgv2_default_mesh_filter_params(flame_nltgv2_mesh_filter_params* p) {
+  if (!p) return;
+  // params.h:69-85
+  p->do_oblique_triangle_filter = 1;
+  p->oblique_normal_thresh = 1.39626f;
+  p->oblique_idepth_diff_factor = 0.35f;
+  p->oblique_idepth_diff_abs = 0.1f;
+  p->do_edge_length_filter = 1;
+  p->edge_length_thresh = 0.333f;
+  p->do_idepth_triangle_filter = 1;
+  p->min_triangle_idepth = 0.01f;
+}
+
+// Floats in their numeric order as integers: ord(a) < ord(b) <=> a < b (no NaNs; -0 just below +0).
+static int64_t float_ord(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, sizeof(u));
+  return (u & 0x80000000u) ? -(int64_t)(u & 0x7fffffffu) - 1 : (int64_t)u;
+}
+static float ord_float(int64_t o) {
+  const uint32_t u = o < 0 ? (uint32_t)(-(o + 1)) | 0x80000000u : (uint32_t)o;
+  float f;
+  std::memcpy(&f, &u, sizeof(f));
+  return f;
+}
+
+float flame_nltgv2_oblique_cos_bound(float thresh) {
+  // accepted(d) := (float)acos((double)d) <= thresh is monotone in d (the arc cosine falls): find the smallest accepted float of [-1, 1]
+  auto accepted = [thresh](float d) { return (float)std::acos((double)d) <= thresh; };
+  if (!(thresh == thresh)) return -1.0f;  // a NaN threshold: `angle > thresh` is never true
+  if (accepted(-1.0f)) return -1.0f;      // thresh >= pi
+  if (!accepted(1.0f)) return HUGE_VALF;  // thresh < 0
+  int64_t lo = float_ord(-1.0f), hi = float_ord(1.0f);  // accepted(hi), !accepted(lo)
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (accepted(ord_float(mid))) hi = mid; else lo = mid;
+  }
+  return ord_float(hi);
+}
+
+// The mesh outputs on the side stream (see flame_nltgv2.h).  Everything is checked before the stream or a buffer is touched: an error
+// leaves what an earlier begin put into the pinned outputs, and its pending _end, as they are.
+int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, const float* Kinv,
+                                    const flame_nltgv2_mesh_filter_params* filter, int rows, int cols, float graph_scale,
+                                    int want_filtered_map) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_mesh_outputs_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  const int32_t V = ctx->L.V;
+  if (T < 0 || rows <= 0 || cols <= 0 || !Kinv || !filter) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!triangles && (ctx->tris_T != T || ctx->tris_topo != ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (triangles)
+    for (int32_t t = 0; t < 3 * T; ++t)
+      if (triangles[t] < 0 || triangles[t] >= V) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const size_t n = want_filtered_map ? (size_t)rows * (size_t)cols : 0;
+  hipStream_t rs = ctx->raster_stream;
+  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned outputs and the device buffers are about to be reused)
+  // pinned outputs: normals | vtx_idepth | n_valid, coverage | filtered map | tri_valid
+  flame_nltgv2_ctx::MeshPending mp;
+  mp.V = V, mp.T = T, mp.rows = want_filtered_map ? rows : 0, mp.cols = want_filtered_map ? cols : 0;
+  mp.off_idepth = sizeof(float) * 3 * (size_t)V;
+  mp.off_counts = mp.off_idepth + sizeof(float) * (size_t)V;
+  mp.off_map = mp.off_counts + 4 * sizeof(int32_t);
+  mp.off_valid = mp.off_map + sizeof(float) * n;
+  const size_t h_bytes = mp.off_valid + (size_t)T + 16;
+  if (ctx->h_mesh_cap < h_bytes) {
+    request_open_stop(ctx);  // (the pinned allocator waits for the device)
+    void* h = nullptr;
+    if (hipHostMalloc(&h, h_bytes + h_bytes / 2, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
+    }
+    if (ctx->h_mesh) (void)hipHostFree(ctx->h_mesh);
+    ctx->h_mesh = (char*)h, ctx->h_mesh_cap = h_bytes + h_bytes / 2;
+    ctx->mesh_pending.active = false;
+  }
+  const size_t fV = sizeof(float) * (size_t)V;
+  rc = ensure(ctx, ctx->m_P, 4 * fV);
+  if (!rc) rc = ensure(ctx, ctx->m_idepth, fV);
+  if (!rc) rc = ensure(ctx, ctx->m_normals, 3 * fV);
+  if (!rc) rc = ensure(ctx, ctx->m_tvalid, (size_t)T + 16);
+  if (!rc) rc = ensure(ctx, ctx->m_nvalid, sizeof(int));
+  if (!rc) rc = ensure(ctx, ctx->m_tnormal, sizeof(float4) * (size_t)T);
+  if (!rc) rc = ensure(ctx, ctx->m_offset, sizeof(int) * ((size_t)V + 1));
+  if (!rc) rc = ensure(ctx, ctx->m_cursor, sizeof(int) * (size_t)V);
+  if (!rc) rc = ensure(ctx, ctx->m_incident, sizeof(int32_t) * 3 * (size_t)T);
+  if (!rc && triangles) rc = ensure(ctx, ctx->r_tris, sizeof(int32_t) * 3 * (size_t)T);
+  if (!rc && want_filtered_map) {
+    rc = ensure(ctx, ctx->m_keys, sizeof(unsigned long long) * n);
+    if (!rc) rc = ensure(ctx, ctx->m_img, sizeof(float) * n);
+    if (!rc) rc = ensure(ctx, ctx->m_cov, sizeof(int));
+  }
+  if (rc) return rc;
+  ctx->mesh_pending.active = false;  // (from here on the pinned outputs are being rewritten)
+  if (triangles) {
+    if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
+    ctx->tris_T = T, ctx->tris_topo = ctx->topo;
+  }
+  flame_hip::MeshFilter mf;
+  std::memcpy(mf.Kinv, Kinv, sizeof(mf.Kinv));
+  mf.do_oblique = filter->do_oblique_triangle_filter != 0;
+  mf.do_edge_length = filter->do_edge_length_filter != 0;
+  mf.do_idepth = filter->do_idepth_triangle_filter != 0;
+  mf.cos_bound = flame_nltgv2_oblique_cos_bound(filter->oblique_normal_thresh);
+  mf.diff_factor = filter->oblique_idepth_diff_factor, mf.diff_abs = filter->oblique_idepth_diff_abs;
+  float dist_thresh2 = filter->edge_length_thresh * (float)cols;  // flame.cc:2297-2298
+  dist_thresh2 *= dist_thresh2;
+  mf.edge_thresh2 = dist_thresh2;
+  mf.min_idepth = filter->min_triangle_idepth;
+  flame_hip::MeshBuffers mb;
+  mb.P = (float4*)ctx->m_P.p, mb.vtx_idepth = (float*)ctx->m_idepth.p, mb.normals = (float*)ctx->m_normals.p;
+  mb.tri_valid = (uint8_t*)ctx->m_tvalid.p, mb.n_valid = (int*)ctx->m_nvalid.p, mb.tri_normal = (float4*)ctx->m_tnormal.p;
+  mb.offset = (int*)ctx->m_offset.p, mb.cursor = (int*)ctx->m_cursor.p, mb.incident = (int32_t*)ctx->m_incident.p;
+  rc = mesh_state_on(ctx, rs);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_mesh0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_mesh_outputs(V, T, ctx->c.pos, ctx->c.x, graph_scale, (const int32_t*)ctx->r_tris.p, mf, mb, rs));
+  // the filtered map: the rasteriser of interpolate_mesh over the idepths and the validity this stage has just left on the device
+  if (want_filtered_map)
+    LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, mb.vtx_idepth, 1.0f, nullptr, mb.tri_valid,
+                                           (unsigned long long*)ctx->m_keys.p, (float*)ctx->m_img.p, (int*)ctx->m_cov.p, rows, cols, rs));
+  HIPCHK(ctx, hipEventRecord(ctx->ev_raster_done, rs));  // (the last readers of the canonical pos / x: see interpolate_mesh_begin)
+  ctx->raster_inflight = true;
+  char* h = ctx->h_mesh;
+  HIPCHK(ctx, hipMemcpyAsync(h, mb.normals, 3 * fV, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.off_idepth, mb.vtx_idepth, fV, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.off_counts, mb.n_valid, sizeof(int), hipMemcpyDeviceToHost, rs));
+  if (T > 0) HIPCHK(ctx, hipMemcpyAsync(h + mp.off_valid, mb.tri_valid, (size_t)T, hipMemcpyDeviceToHost, rs));
+  if (want_filtered_map) {
+    HIPCHK(ctx, hipMemcpyAsync(h + mp.off_map, ctx->m_img.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + mp.off_counts + sizeof(int32_t), ctx->m_cov.p, sizeof(int), hipMemcpyDeviceToHost, rs));
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev_mesh1, rs));
+  mp.active = true;
+  ctx->mesh_pending = mp;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_mesh_outputs_end(flame_nltgv2_ctx* ctx, flame_nltgv2_mesh_outputs_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_mesh_outputs_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::MeshPending& mp = ctx->mesh_pending;
+  if (!out || !ctx->h_mesh || !mp.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  const char* h = ctx->h_mesh;
+  int32_t counts[2];
+  std::memcpy(counts, h + mp.off_counts, sizeof(counts));
+  out->V = mp.V, out->T = mp.T;
+  out->tri_valid = (const uint8_t*)(h + mp.off_valid);
+  out->normals = (const float*)h;
+  out->vtx_idepth = (const float*)(h + mp.off_idepth);
+  out->n_valid = counts[0];
+  out->rows = mp.rows, out->cols = mp.cols;
+  out->filtered_map = mp.rows > 0 ? (const float*)(h + mp.off_map) : nullptr;
+  out->filtered_coverage = mp.rows > 0 ? counts[1] : 0;
+  out->device_ms = 0.0f;
+  if (hipEventElapsedTime(&out->device_ms, ctx->ev_mesh0, ctx->ev_mesh1) != hipSuccess) (void)hipGetLastError(), out->device_ms = 0.0f;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, const float* Kinv,
+                              const flame_nltgv2_mesh_filter_params* filter, int rows, int cols, float graph_scale,
+                              uint8_t* tri_valid_out, float* normals_out, float* vtx_idepth_out, int32_t* n_valid_out,
+                              float* filtered_map_out, int32_t* filtered_coverage_out) {
+  int rc = flame_nltgv2_mesh_outputs_begin(ctx, triangles, T, Kinv, filter, rows, cols, graph_scale,
+                                           filtered_map_out != nullptr || filtered_coverage_out != nullptr);
+  if (rc) return rc;
+  flame_nltgv2_mesh_outputs_view v;
+  rc = flame_nltgv2_mesh_outputs_end(ctx, &v);
+  if (rc) return rc;
+  if (tri_valid_out && v.T > 0) std::memcpy(tri_valid_out, v.tri_valid, (size_t)v.T);
+  if (normals_out) std::memcpy(normals_out, v.normals, sizeof(float) * 3 * (size_t)v.V);
+  if (vtx_idepth_out) std::memcpy(vtx_idepth_out, v.vtx_idepth, sizeof(float) * (size_t)v.V);
+  if (n_valid_out) *n_valid_out = v.n_valid;
+  if (filtered_map_out) std::memcpy(filtered_map_out, v.filtered_map, sizeof(float) * (size_t)v.rows * (size_t)v.cols);
+  if (filtered_coverage_out) *filtered_coverage_out = v.filtered_coverage;
+  return FLAME_NLTGV2_OK;
 }
 
 int flame_nltgv2_photo_set_images(flame_nltgv2_ctx* ctx, const uint8_t* ref, const uint8_t* cmp, int rows, int cols,

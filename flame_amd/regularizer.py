@@ -58,6 +58,28 @@ class Params(C.Structure):
         super().__init__(data_factor, step_x, step_q, theta, x_min, x_max)
 
 
+class MeshFilterParams(C.Structure):
+    """== the mesh filter fields of struct Params, params.h:69-85 (same defaults); flame_nltgv2_mesh_filter_params."""
+
+    _fields_ = [("do_oblique_triangle_filter", C.c_int32), ("oblique_normal_thresh", C.c_float),
+                ("oblique_idepth_diff_factor", C.c_float), ("oblique_idepth_diff_abs", C.c_float),
+                ("do_edge_length_filter", C.c_int32), ("edge_length_thresh", C.c_float),
+                ("do_idepth_triangle_filter", C.c_int32), ("min_triangle_idepth", C.c_float)]
+
+    def __init__(self, do_oblique_triangle_filter=True, oblique_normal_thresh=1.39626, oblique_idepth_diff_factor=0.35,
+                 oblique_idepth_diff_abs=0.1, do_edge_length_filter=True, edge_length_thresh=0.333,
+                 do_idepth_triangle_filter=True, min_triangle_idepth=0.01):
+        super().__init__(int(bool(do_oblique_triangle_filter)), oblique_normal_thresh, oblique_idepth_diff_factor,
+                         oblique_idepth_diff_abs, int(bool(do_edge_length_filter)), edge_length_thresh,
+                         int(bool(do_idepth_triangle_filter)), min_triangle_idepth)
+
+
+class _MeshOutputsView(C.Structure):
+    _fields_ = [("V", C.c_int32), ("T", C.c_int32), ("tri_valid", C.POINTER(C.c_uint8)), ("normals", _FP), ("vtx_idepth", _FP),
+                ("n_valid", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("filtered_map", _FP),
+                ("filtered_coverage", C.c_int32), ("device_ms", C.c_float)]
+
+
 class _Graph(C.Structure):
     _fields_ = (
         [("V", C.c_int32), ("E", C.c_int32), ("pos", _FP)]
@@ -113,6 +135,8 @@ ABI_SYMBOLS = (
     "flame_nltgv2_interpolate_mesh_begin", "flame_nltgv2_interpolate_mesh_end",
     "flame_nltgv2_interpolate_mesh_arrays", "flame_nltgv2_project_graph", "flame_nltgv2_rescale_data",
     "flame_delaunay_triangulate",
+    "flame_nltgv2_default_mesh_filter_params", "flame_nltgv2_oblique_cos_bound", "flame_nltgv2_mesh_outputs_begin",
+    "flame_nltgv2_mesh_outputs_end", "flame_nltgv2_mesh_outputs",
 )
 
 
@@ -183,6 +207,13 @@ def load_library():
         "flame_nltgv2_interpolate_mesh_end": (C.c_int, [ctx, C.POINTER(_FP), _IP]),
         "flame_nltgv2_interpolate_mesh_arrays": (C.c_int, [ctx, _IP, C.c_int32, _FP, _FP, C.c_int32, C.POINTER(C.c_uint8),
                                                            C.POINTER(C.c_uint8), C.c_int, C.c_int, _FP, _IP]),
+        "flame_nltgv2_default_mesh_filter_params": (None, [C.POINTER(MeshFilterParams)]),
+        "flame_nltgv2_oblique_cos_bound": (C.c_float, [C.c_float]),
+        "flame_nltgv2_mesh_outputs_begin": (C.c_int, [ctx, _IP, C.c_int32, _FP, C.POINTER(MeshFilterParams), C.c_int, C.c_int,
+                                                      C.c_float, C.c_int]),
+        "flame_nltgv2_mesh_outputs_end": (C.c_int, [ctx, C.POINTER(_MeshOutputsView)]),
+        "flame_nltgv2_mesh_outputs": (C.c_int, [ctx, _IP, C.c_int32, _FP, C.POINTER(MeshFilterParams), C.c_int, C.c_int, C.c_float,
+                                                C.POINTER(C.c_uint8), _FP, _FP, _IP, _FP, _IP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -273,6 +304,7 @@ class Regularizer:
     def __init__(self, device: int = 0):
         self._L = load_library()
         self._ctx = C.c_void_p()
+        self._mesh_T = -1  # triangles the last interpolate_mesh[_begin] / mesh_outputs_begin of this object sent down
         rc = self._L.flame_nltgv2_create(C.byref(self._ctx), int(device))
         if rc != 0:
             self._ctx = None
@@ -481,6 +513,7 @@ class Regularizer:
                                                         None if tv is None else tv.ctypes.data_as(U8), rows, cols,
                                                         C.c_float(graph_scale), img.ctypes.data_as(_FP), C.byref(cov)),
                   "interpolate_mesh")
+        self._mesh_T = tr.shape[0]
         return img, int(cov.value)
 
     def interpolate_mesh_begin(self, triangles, rows, cols, graph_scale=1.0, tri_valid=None):
@@ -493,6 +526,7 @@ class Regularizer:
                                                               None if tv is None else tv.ctypes.data_as(U8), rows, cols,
                                                               C.c_float(graph_scale)), "interpolate_mesh_begin")
         self._map_shape = (rows, cols)
+        self._mesh_T = tr.shape[0]
 
     def interpolate_mesh_end(self, copy=True):
         """-> (idepthmap, coverage); copy=False: a view of the context's pinned buffer, valid until the next begin."""
@@ -501,6 +535,45 @@ class Regularizer:
         rows, cols = self._map_shape
         img = np.ctypeslib.as_array(p, shape=(rows, cols))
         return (img.copy() if copy else img), int(cov.value)
+
+    # -- the mesh outputs of Flame::update(), flame.cc:372-407 (flame_nltgv2_mesh_outputs*) -------------------------------------
+    def mesh_outputs_begin(self, triangles, Kinv, rows, cols, graph_scale=1.0, filter=None, want_filtered_map=False):
+        """Enqueues vtx_idepths / vertex normals / triangle validity (and the filtered dense map) of the resident state on the side
+        stream and returns.  triangles=None: the triangles the last interpolate_mesh[_begin] of this object left on the device (an
+        int instead: that many of them -- the library refuses a count that is not the resident one)."""
+        if triangles is None or isinstance(triangles, (int, np.integer)):
+            T = self._mesh_T if triangles is None else int(triangles)
+            tp = None
+        else:
+            tr = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+            T, tp = tr.shape[0], tr.ctypes.data_as(_IP)
+        k = np.ascontiguousarray(Kinv, np.float32).reshape(9)
+        f = filter if filter is not None else MeshFilterParams()
+        self._chk(self._L.flame_nltgv2_mesh_outputs_begin(self._ctx, tp, T, k.ctypes.data_as(_FP), C.byref(f), rows, cols,
+                                                          C.c_float(graph_scale), int(bool(want_filtered_map))), "mesh_outputs_begin")
+        if tp is not None:
+            self._mesh_T = T
+
+    def mesh_outputs_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(tri_valid (T,) u8, normals (V,3), vtx_idepth (V,), n_valid, device_ms and, if asked for,
+        filtered_map (rows,cols), filtered_coverage).  copy=False: views of the context's pinned memory, valid until the next begin."""
+        v = _MeshOutputsView()
+        self._chk(self._L.flame_nltgv2_mesh_outputs_end(self._ctx, C.byref(v)), "mesh_outputs_end")
+        take = (lambda a: a.copy()) if copy else (lambda a: a)
+        out = dict(
+            tri_valid=take(np.ctypeslib.as_array(v.tri_valid, shape=(v.T,))) if v.T > 0 else np.zeros(0, np.uint8),
+            normals=take(np.ctypeslib.as_array(v.normals, shape=(v.V, 3))),
+            vtx_idepth=take(np.ctypeslib.as_array(v.vtx_idepth, shape=(v.V,))),
+            n_valid=int(v.n_valid), device_ms=float(v.device_ms))
+        if v.rows > 0:
+            out["filtered_map"] = take(np.ctypeslib.as_array(v.filtered_map, shape=(v.rows, v.cols)))
+            out["filtered_coverage"] = int(v.filtered_coverage)
+        return out
+
+    def mesh_outputs(self, triangles, Kinv, rows, cols, graph_scale=1.0, filter=None, want_filtered_map=False) -> dict:
+        """mesh_outputs_begin; mesh_outputs_end."""
+        self.mesh_outputs_begin(triangles, Kinv, rows, cols, graph_scale, filter, want_filtered_map)
+        return self.mesh_outputs_end()
 
     def interpolate_mesh_arrays(self, triangles, vertices, values, rows, cols, vtx_valid=None, tri_valid=None):
         tr = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)

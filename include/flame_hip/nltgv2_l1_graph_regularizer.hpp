@@ -23,6 +23,7 @@
 #define FLAME_HIP_NLTGV2_L1_GRAPH_REGULARIZER_HPP_
 
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -175,6 +176,32 @@ inline flame_nltgv2_params to_c(const Params& p) {
   return c;
 }
 
+// == the mesh filter fields of flame::Params (params.h:69-85): layout-identical to flame_nltgv2_mesh_filter_params, same defaults.
+struct MeshFilterParams {
+  int32_t do_oblique_triangle_filter = 1;
+  float oblique_normal_thresh = 1.39626f;       // 80 degrees. Max angle between surface normal and viewing ray.
+  float oblique_idepth_diff_factor = 0.35f;     // (max_idepth - min_idepth)/max_idepth
+  float oblique_idepth_diff_abs = 0.1f;         // (max_idepth - min_idepth)
+  int32_t do_edge_length_filter = 1;
+  float edge_length_thresh = 0.333f;            // As fraction of image width.
+  int32_t do_idepth_triangle_filter = 1;
+  float min_triangle_idepth = 0.01f;
+};
+static_assert(sizeof(MeshFilterParams) == sizeof(flame_nltgv2_mesh_filter_params), "MeshFilterParams must mirror the C-ABI struct");
+
+// What Flame::update() leaves for its getters (flame.cc:372-407), under the reference's member names.  Pointers into pinned
+// memory of the DeviceGraph, valid until its next meshOutputsBegin().
+struct MeshOutputs {
+  size_t num_vertices = 0, num_triangles = 0;
+  const float* vtx_idepths = nullptr;     // [num_vertices]      vtx_idepths_
+  const float* vtx_normals = nullptr;     // [3 * num_vertices]  vtx_normals_, (x, y, z) interleaved
+  const uint8_t* tri_validity = nullptr;  // [num_triangles]     tri_validity_
+  int num_valid_triangles = 0;
+  int rows = 0, cols = 0;
+  const float* filtered_idepthmap = nullptr;  // [rows * cols] getFilteredInverseDepthMap (flame.h:217-228), or nullptr
+  int filtered_coverage = 0;
+};
+
 // Device image of ONE Graph: what the pipeline keeps next to `Graph graph_` (flame.h:536).  Not
 // thread-safe -- hold graph_mtx_ (flame.h:539) around every call exactly as the reference does around
 // step() and the graph edits (flame.cc:103, 302, 309, 329, 365).
@@ -266,6 +293,28 @@ class DeviceGraph {
     int32_t coverage = 0;
     check(flame_nltgv2_interpolate_mesh_end(ctx_, idepthmap, &coverage), "interpolate_mesh_end");
     return coverage;
+  }
+
+  // The mesh outputs of Flame::update() (flame.cc:372-407: vtx_idepths_, getVertexNormals, the three triangle filters) and, if
+  // asked for, getFilteredInverseDepthMap's map, from the device state on the side stream (flame_nltgv2_mesh_outputs_begin / _end).
+  // `triangles` == nullptr: the triangles the last interpolateMesh[Begin] left on the device (num_triangles of them).
+  void meshOutputsBegin(const std::vector<int32_t>* triangles, size_t num_triangles, const float Kinv[9], const MeshFilterParams& filter,
+                        int rows, int cols, float graph_scale, bool want_filtered_map) {
+    flame_nltgv2_mesh_filter_params c;
+    std::memcpy(&c, &filter, sizeof(c));
+    check(flame_nltgv2_mesh_outputs_begin(ctx_, triangles ? triangles->data() : nullptr,
+                                          static_cast<int32_t>(triangles ? triangles->size() / 3 : num_triangles), Kinv, &c, rows, cols,
+                                          graph_scale, want_filtered_map ? 1 : 0), "mesh_outputs_begin");
+  }
+  MeshOutputs meshOutputsEnd() {
+    flame_nltgv2_mesh_outputs_view v;
+    check(flame_nltgv2_mesh_outputs_end(ctx_, &v), "mesh_outputs_end");
+    MeshOutputs m;
+    m.num_vertices = static_cast<size_t>(v.V), m.num_triangles = static_cast<size_t>(v.T);
+    m.vtx_idepths = v.vtx_idepth, m.vtx_normals = v.normals, m.tri_validity = v.tri_valid;
+    m.num_valid_triangles = v.n_valid;
+    m.rows = v.rows, m.cols = v.cols, m.filtered_idepthmap = v.filtered_map, m.filtered_coverage = v.filtered_coverage;
+    return m;
   }
 
   // utils::interpolateMesh (utils/image_utils.cc:373-396) at its call site flame.cc:409-415: rasterises

@@ -274,6 +274,81 @@ int flame_nltgv2_interpolate_mesh_arrays(flame_nltgv2_ctx* ctx, const int32_t* t
                                          const uint8_t* vtx_valid, const uint8_t* tri_valid, int rows, int cols,
                                          float* img_out, int32_t* coverage_out);
 
+/* Mesh outputs: what Flame::update() makes of the graph between the solver and its getters (flame.cc:372-415; getters
+ * flame.h:207-250) -- vtx_idepths_ (flame.cc:377), getVertexNormals (the triangle-based overload, flame.cc:2554-2641), tri_validity_ from
+ * obliqueTriangleFilter / edgeLengthFilter / idepthTriangleFilter (flame.cc:2207-2361, applied in that order, flame.cc:389-407) and the
+ * FILTERED dense map (getFilteredInverseDepthMap, flame.h:217-228: interpolateMesh with tri_validity_) -- from the resident state, on the
+ * context's side stream, beside the running solver.  The arithmetic is the reference's scalar float code operation for operation
+ * (tests/mesh_ref.py restates it; device and checker agree bit for bit).  Pinned down here, since Eigen is not part of this tree:
+ *   - P = (Kinv * (pos.x, pos.y, 1)) / idepth: the full 3x3 product, then three divisions; every sum of three products -- matrix rows,
+ *     dot products, squared norms -- is taken left to right, (a + b) + c, as everywhere else in this library (flame_nltgv2_project_graph);
+ *   - normalize() leaves a vector whose squared norm is not > 0 unchanged (Eigen >= 3.3), so a degenerate triangle has a zero normal;
+ *   - every comparison with a NaN is false: a NaN never clears validity; idepth == 0 gives infinite points and plain IEEE results;
+ *     the reference's FLAME_ASSERT(max_id >= min_id) (flame.cc:2263) is not reproduced: nothing aborts;
+ *   - the angle test `fabs(acos(d)) > oblique_normal_thresh` (flame.cc:2252-2253) is made on d itself: no arc cosine runs on the device
+ *     (see flame_nltgv2_oblique_cos_bound);
+ *   - a vertex normal is the reference's SEQUENTIAL running mean over its triangles in ascending triangle index,
+ *     n = normalize((count * n + normal_t) / (count + 1)) (flame.cc:2614-2630), triangles with a corner idepth <= 0 skipped
+ *     (flame.cc:2585); a vertex without a contributing triangle has the normal (0, 0, 0).  Normals are OUTWARD (delta2 x delta1,
+ *     flame.cc:2611); the filter's normal is the inward one (flame.cc:2244).
+ *
+ * == the mesh filter fields of struct Params, params.h:69-85 (same defaults). */
+typedef struct flame_nltgv2_mesh_filter_params {
+  int32_t do_oblique_triangle_filter; /* 1        params.h:70 */
+  float oblique_normal_thresh;        /* 1.39626  params.h:71  angle between inward normal and viewing ray, radians (80 deg) */
+  float oblique_idepth_diff_factor;   /* 0.35     params.h:73  (max_id - min_id) / max_id, flame.cc:2265 */
+  float oblique_idepth_diff_abs;      /* 0.1      params.h:76  max_id - min_id, flame.cc:2269 */
+  int32_t do_edge_length_filter;      /* 1        params.h:80 */
+  float edge_length_thresh;           /* 0.333    params.h:81  fraction of the map WIDTH: thresh2 = (thresh * cols)^2, flame.cc:2297-2298 */
+  int32_t do_idepth_triangle_filter;  /* 1        params.h:84 */
+  float min_triangle_idepth;          /* 0.01     params.h:85  mean corner idepth, flame.cc:2346-2347 */
+} flame_nltgv2_mesh_filter_params;
+void flame_nltgv2_default_mesh_filter_params(flame_nltgv2_mesh_filter_params* p);
+
+/* The smallest float D in [-1, 1] with (float)acos((double)D) <= thresh, found by bisection over the floats (HOST code, double libm, no
+ * context, no GPU).  The reference rejects a triangle when fabs(acos(d)) > thresh (flame.cc:2252-2253); the arc cosine is monotone, so
+ * that is `d >= -1 && d <= 1 && d < D` -- for |d| > 1 or a NaN the reference's angle is a NaN, which rejects nothing.  A device arc cosine
+ * differs from the host's in the last ulps and would flip triangles at the threshold; this comparison cannot.  thresh >= pi: -1 (rejects
+ * nothing); thresh < 0: +infinity (rejects every d in [-1, 1]); a NaN threshold: -1.  Default threshold 1.39626: 0.17365146f. */
+float flame_nltgv2_oblique_cos_bound(float oblique_normal_thresh);
+
+/* Pointers into pinned memory of the context, valid until the next flame_nltgv2_mesh_outputs_begin. */
+typedef struct flame_nltgv2_mesh_outputs_view {
+  int32_t V, T;
+  const uint8_t* tri_valid;   /* [T] tri_validity_, flame.cc:389-407 */
+  const float* normals;       /* [3V] vtx_normals_, (x, y, z) interleaved, caller's vertex order */
+  const float* vtx_idepth;    /* [V] vtx_idepths_ = x * graph_scale, flame.cc:377 */
+  int32_t n_valid;            /* number of non-zero tri_valid */
+  int32_t rows, cols;         /* of the filtered map (0, 0: not asked for) */
+  const float* filtered_map;  /* [rows * cols] getFilteredInverseDepthMap, NaN where no VALID triangle covers the pixel; NULL: not asked for */
+  int32_t filtered_coverage;  /* its non-NaN pixels */
+  float device_ms;            /* measurement aid: HIP-event time of the stage on the side stream, kernels and copies out */
+} flame_nltgv2_mesh_outputs_view;
+
+/* begin  checks the arguments -- an error (no graph, T < 0, an index outside [0, V), rows / cols <= 0, Kinv or filter NULL, triangles NULL
+ *        without resident triangles or with another T) is reported before anything is enqueued and leaves the outputs of an earlier begin
+ *        as they are --, then enqueues everything on the context's side stream and returns.  WHICH STATE it describes is decided exactly as
+ *        in flame_nltgv2_interpolate_mesh_begin (the runs are settled and the canonical arrays read; with FLAME_NLTGV2_OPT_MESH_STATE = 1
+ *        and runs in flight: the state the last settle left, nothing waited for), so a mesh_outputs_begin right behind an
+ *        interpolate_mesh_begin describes the state of that map.
+ *        triangles == NULL: the T triangles the last flame_nltgv2_interpolate_mesh[_begin] of this context left on the device for the
+ *        current topology (the frame loop calls both on one triangulation: no second upload).
+ *        Kinv: 9 floats row-major (Flame::Kinv_).  rows / cols: the map's size; cols also scales edge_length_thresh.
+ *        want_filtered_map != 0: the filtered map is rasterised as well, into buffers OF ITS OWN: the resident unfiltered map
+ *        (flame_nltgv2_sync_input.init_from_map) and the pinned map of interpolate_mesh_end stay what they were.  The validity goes from
+ *        the filter kernel to the rasteriser on the device.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_mesh_outputs == begin; end; copies into the caller's arrays (each may be NULL).
+ * getInverseDepthMesh (flame.h:233-249) = the caller's positions + vtx_idepth + normals + the caller's triangles + tri_valid. */
+int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, const float* Kinv,
+                                    const flame_nltgv2_mesh_filter_params* filter, int rows, int cols, float graph_scale,
+                                    int want_filtered_map);
+int flame_nltgv2_mesh_outputs_end(flame_nltgv2_ctx* ctx, flame_nltgv2_mesh_outputs_view* out);
+int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, const float* Kinv,
+                              const flame_nltgv2_mesh_filter_params* filter, int rows, int cols, float graph_scale,
+                              uint8_t* tri_valid_out, float* normals_out, float* vtx_idepth_out, int32_t* n_valid_out,
+                              float* filtered_map_out, int32_t* filtered_coverage_out);
+
 /* 2-D Delaunay triangulation of float32 points: the counterpart of utils::Delaunay
  * (src/flame/utils/delaunay.{h,cc}, a wrapper of the vendored Shewchuk Triangle called with "zneQB",
  * delaunay.cc:66-68) that feeds Flame::syncGraph its edge list (flame.cc:2073-2104) and interpolateMesh its
