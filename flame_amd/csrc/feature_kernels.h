@@ -34,9 +34,20 @@ struct DetectInit {
   float idepth_init, idepth_var_init;
 };
 
-// stats words of both stages: [kFrontAssert] lowest index that hit a reference assert, [kFrontBadFrame] lowest
-// feature index with an unknown frame id (both start at INT_MAX), [kFrontCount] kept / new features.
-constexpr int kFrontAssert = 0, kFrontBadFrame = 1, kFrontCount = 2, kFrontWords = 4;
+// cv::Rect valid_region(border, border + row_offset, width - 2 border, height - 2 border - 2 row_offset) of
+// prunePoseFrames (flame.cc:604-606): integers, tested with rect_contains (stereo_geometry.hpp).
+struct PruneRegion {
+  int x, y, w, h;
+};
+
+// k_prune_move's flag byte per feature.
+constexpr uint8_t kPruneKeep = 1, kPruneRewritten = 2, kPruneMoved = 4, kPruneInvalidated = 8;
+
+// stats words of the stages: [kFrontAssert] lowest index that hit a reference assert, [kFrontBadFrame] lowest
+// feature index with an unknown frame id (both start at INT_MAX), [kFrontCount] kept / new features;
+// the prune adds [kPruneStatMoved] and [kPruneStatInvalidated].
+constexpr int kFrontAssert = 0, kFrontBadFrame = 1, kFrontCount = 2, kPruneStatMoved = 3, kPruneStatInvalidated = 4,
+              kFrontWords = 8;
 
 // k_project_flag + k_project_scatter: `feats` (n) -> stably compacted `feats_out` / `proj_out`; proj_tmp and keep are
 // n-sized scratch, counts (n + 255) / 256 ints.
@@ -51,5 +62,14 @@ hipError_t launch_detect_features(const DetectGrid& grid, const Geo& geo, const 
                                   const float* gy_pad, int n_mask, const float* mask_xy, int mask_stride, uint8_t* blocked,
                                   unsigned long long* cell_key, int* counts, const DetectInit& init, const float* idepthmap,
                                   StereoFeature* out, int* stats, hipStream_t stream);
+// k_prune_move + k_prune_commit (Flame::prunePoseFrames, flame.cc:608-700) on `feats` (n records; [first_new, n) are
+// new_feats_).  keep_ids: n_keep ids; dropped: n_dropped entries with the geometry of target.pose.inverse() * pf.pose.
+// `moved` is n records of scratch, `flags` n bytes, `counts` 3 * ((n + 255) / 256) ints, `feats_out` room for n records.
+// Afterwards, unless stats[kFrontAssert] or stats[kFrontBadFrame] left INT_MAX (then nothing was written to feats or
+// feats_out): stats[kFrontCount] records remain -- in `feats`, in place, when that is n, else compacted in `feats_out`.
+hipError_t launch_prune_features(const StereoCamera& cam, const PruneRegion& region, int n_keep, const uint32_t* keep_ids,
+                                 int n_dropped, const ProjectPoseEntry* dropped, uint32_t target_frame_id, int first_new, int n,
+                                 StereoFeature* feats, StereoFeature* moved, uint8_t* flags, int* counts,
+                                 StereoFeature* feats_out, int* stats, hipStream_t stream);
 
 }  // namespace flame_hip

@@ -22,10 +22,37 @@
 //   k_detect_emit      one lane per cell: the same ranking as k_project_scatter, in row-major cell order, and the
 //                      initialised 40-byte records at n_res + rank.
 //
+// prunePoseFrames (flame.cc:554-706), the two feature loops (flame.cc:608-700):
+//   k_prune_move       one lane per feature: the kept-id lookup; a feature of a kept pose-frame is left alone.  Any
+//                      other feature is looked up in the table of dropped pose-frames (geometry towards the target
+//                      pose-frame), run through inverse_depth_filter::predict and rewritten into a scratch record;
+//                      a flag byte per feature (kPruneKeep | kPruneRewritten | kPruneMoved | kPruneInvalidated) and
+//                      three counts per workgroup (kept, moved, invalidated; three arrays).
+//   k_prune_commit     one lane per feature, after k_prune_move on the same stream: does nothing when an error index
+//                      was raised.  When every record is kept, the rewritten records go back IN PLACE; otherwise the
+//                      kept records are compacted stably into the other buffer (group_base / group_rank).  Writes
+//                      the totals.
+//   What the reference's loops do, kept literally:
+//    1. the target is pruned_pfs.crbegin() of a std::map: the kept pose-frame with the LARGEST id (the host passes it);
+//    2. `valid` is not tested: invalid features of a dropped frame are moved too; `valid` is only ever cleared;
+//    3. records [0, first_new) (feats_) get frame_id, xy, idepth_mu, idepth_var overwritten BEFORE the success test,
+//       also when the move fails (idepth_mu = the 0 predict returns, xy = the projected point);
+//    4. idepth_var *= (idepth_pf / old_idepth)^4 as two squarings, 1 when double(idepth_pf) < 1e-6 (the NEW value);
+//       predict's var_pred is discarded, so process_var_factor has no effect;
+//    5. the region is an integer cv::Rect against a Point2f that is rounded to nearest-even first (rect_contains of
+//       stereo_geometry.hpp, the update kernel's rule; unpinned: OpenCV is not available to check it).  A NaN
+//       coordinate is outside;
+//    6. where EpipolarGeometry::project asserts (negative or NaN idepth_mu, a zero third coordinate): the lowest
+//       such index in stats[kFrontAssert], nothing is committed;
+//    7. records [first_new, n) (new_feats_) that fail are REMOVED, never rewritten; failing feats_ records are kept
+//       with valid = 0;
+//    8. (the `pruned_pfs.size() == 0 -> clear()` branch is unreachable once the current pose-frame was found.)
+//
 // Arithmetic keeps the reference's expression order and width; the build has -ffp-contract=off and correctly rounded
 // division and sqrt, so results are bit-identical to the reference's scalar float code.  Nothing depends on the order
 // in which atomics arrive: the only atomics are atomicMin of an error index.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "feature_kernels.h"
@@ -142,6 +169,100 @@ __global__ __launch_bounds__(kGroup) void k_project_scatter(const int n, const u
     proj_out[at] = proj[i];
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) stats[kFrontCount] = base + total;
+}
+
+// ---- prunePoseFrames --------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kGroup) void k_prune_move(const StereoCamera cam, const PruneRegion R, const int n_keep,
+                                                       const uint32_t* __restrict__ keep_ids, const int n_dropped,
+                                                       const ProjectPoseEntry* __restrict__ dropped,
+                                                       const uint32_t target_frame_id, const int first_new, const int n,
+                                                       const StereoFeature* __restrict__ feats,
+                                                       StereoFeature* __restrict__ moved, uint8_t* __restrict__ flags,
+                                                       int* __restrict__ counts, int* __restrict__ stats) {
+  const int i = blockIdx.x * kGroup + threadIdx.x;
+  uint8_t fl = 0;
+  if (i < n) {
+    fl = kPruneKeep;
+    StereoFeature f = feats[i];
+    int k = 0;
+    while (k < n_keep && keep_ids[k] != f.frame_id) ++k;
+    if (k == n_keep) {  // pruned_pfs.count(feat.frame_id) == 0
+      int d = 0;
+      while (d < n_dropped && dropped[d].frame_id != f.frame_id) ++d;
+      V2 u_pf;
+      float idepth_pf;
+      if (d == n_dropped) {  // pfs_[feat.frame_id] of a frame that is not there
+        atomicMin(&stats[kFrontBadFrame], i);
+      } else if (!project_idepth(dropped[d].geo, cam, V2{f.x, f.y}, f.idepth_mu, &u_pf, &idepth_pf)) {
+        atomicMin(&stats[kFrontAssert], i);
+      } else {
+        bool move_success = true;  // inverse_depth_filter::predict (inverse_depth_filter.cc:41-47)
+        if (idepth_pf < 0.0f) {
+          idepth_pf = 0.0f;
+          move_success = false;
+        }
+        const bool ok = move_success && rect_contains(R.x, R.y, R.w, R.h, u_pf);
+        if (!ok && i >= first_new) {
+          fl = 0;  // new_feats_: removed, not rewritten (flame.cc:675-678)
+        } else {
+          f.frame_id = target_frame_id;
+          f.x = u_pf.x, f.y = u_pf.y;
+          const float old_idepth = f.idepth_mu;
+          f.idepth_mu = idepth_pf;
+          float v4 = idepth_pf / old_idepth;
+          v4 *= v4;
+          v4 *= v4;
+          if ((double)idepth_pf < 1e-6) v4 = 1;
+          f.idepth_var *= v4;
+          if (!ok) f.valid = 0;  // feats_: kept, marked (flame.cc:643-647)
+          moved[i] = f;
+          fl = kPruneKeep | kPruneRewritten | (ok ? kPruneMoved : kPruneInvalidated);
+        }
+      }
+    }
+    flags[i] = fl;
+  }
+  const int c_keep = __syncthreads_count(fl & kPruneKeep);
+  const int c_moved = __syncthreads_count(fl & kPruneMoved);
+  const int c_inval = __syncthreads_count(fl & kPruneInvalidated);
+  if (threadIdx.x == 0) {
+    counts[blockIdx.x] = c_keep;
+    counts[gridDim.x + blockIdx.x] = c_moved;
+    counts[2 * gridDim.x + blockIdx.x] = c_inval;
+  }
+}
+
+__global__ __launch_bounds__(kGroup) void k_prune_commit(const int n, const uint8_t* __restrict__ flags,
+                                                         const int* __restrict__ counts,
+                                                         StereoFeature* __restrict__ feats,
+                                                         const StereoFeature* __restrict__ moved,
+                                                         StereoFeature* __restrict__ feats_out, int* __restrict__ stats) {
+  if (stats[kFrontAssert] != INT_MAX || stats[kFrontBadFrame] != INT_MAX) return;  // (uniform: written by k_prune_move only)
+  const int i = blockIdx.x * kGroup + threadIdx.x;
+  const int groups = gridDim.x;
+  const int kept = group_base(counts, groups);  // the kept counts of all workgroups
+  const uint8_t fl = i < n ? flags[i] : 0;
+  if (kept == n) {  // nothing removed: in place, only the rewritten records are stored
+    if (fl & kPruneRewritten) feats[i] = moved[i];
+  } else {
+    __syncthreads();  // (group_base's LDS words are reused)
+    const int base = group_base(counts, blockIdx.x);
+    int total;
+    const int at = base + group_rank(fl & kPruneKeep, &total);
+    if (fl & kPruneKeep) feats_out[at] = (fl & kPruneRewritten) ? moved[i] : feats[i];
+  }
+  if (blockIdx.x == 0) {
+    __syncthreads();
+    const int n_moved = group_base(counts + groups, groups);
+    __syncthreads();
+    const int n_inval = group_base(counts + 2 * groups, groups);
+    if (threadIdx.x == 0) {
+      stats[kFrontCount] = kept;
+      stats[kPruneStatMoved] = n_moved;
+      stats[kPruneStatInvalidated] = n_inval;
+    }
+  }
 }
 
 // ---- detectFeatures ---------------------------------------------------------------------------------------------
@@ -277,6 +398,18 @@ hipError_t launch_detect_features(const DetectGrid& grid, const Geo& geo, const 
   hipLaunchKernelGGL(k_detect_count, dim3(groups), dim3(kGroup), 0, stream, n_cells, cell_key, blocked, counts);
   hipLaunchKernelGGL(k_detect_emit, dim3(groups), dim3(kGroup), 0, stream, n_cells, cam.width, cell_key, blocked, counts, init,
                      idepthmap, out, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_prune_features(const StereoCamera& cam, const PruneRegion& region, int n_keep, const uint32_t* keep_ids,
+                                 int n_dropped, const ProjectPoseEntry* dropped, uint32_t target_frame_id, int first_new, int n,
+                                 StereoFeature* feats, StereoFeature* moved, uint8_t* flags, int* counts,
+                                 StereoFeature* feats_out, int* stats, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const int groups = (n + kGroup - 1) / kGroup;
+  hipLaunchKernelGGL(k_prune_move, dim3(groups), dim3(kGroup), 0, stream, cam, region, n_keep, keep_ids, n_dropped, dropped,
+                     target_frame_id, first_new, n, feats, moved, flags, counts, stats);
+  hipLaunchKernelGGL(k_prune_commit, dim3(groups), dim3(kGroup), 0, stream, n, flags, counts, feats, moved, feats_out, stats);
   return hipGetLastError();
 }
 

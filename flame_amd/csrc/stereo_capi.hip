@@ -39,7 +39,8 @@ struct flame_stereo_ctx {
   StereoCamera cam{};
   std::unordered_map<uint32_t, Frame> frames;
   std::vector<Frame> spare;  // buffers of dropped frames, reused by the next add_frame: hipFree waits for every stream of the device, also
-                             // for a solver that runs beside the tracker (tools/frame_loop.py --pipelined: 0.5 ms per frame)
+                             // for a solver that runs beside the tracker (tools/frame_loop.py --pipelined: 0.5 ms per frame).
+                             // At most kSpareFrames of them (release_frame).
   uint8_t* d_raw = nullptr;  // staging of the unpadded upload
   size_t raw_cap = 0;
   StereoPoseEntry* d_poses = nullptr;
@@ -70,6 +71,8 @@ struct flame_stereo_ctx {
   size_t groups_cap = 0;
   ProjectPoseEntry* d_ppose = nullptr;
   size_t ppose_cap = 0;
+  uint32_t* d_keep_ids = nullptr;  // prune_pose_frames: the ids of the kept pose-frames
+  size_t keep_ids_cap = 0;
   unsigned long long* d_cell_key = nullptr;
   size_t cell_key_cap = 0;
   uint8_t* d_blocked = nullptr;
@@ -111,6 +114,15 @@ void drop_all_frames(flame_stereo_ctx* ctx) {
   ctx->frames.clear();
   for (Frame& f : ctx->spare) free_frame(f);  // (the camera changes: another padded size)
   ctx->spare.clear();
+}
+
+// The buffers of a frame that leaves go to `spare` for the next add_frame, up to kSpareFrames sets; the rest is freed
+// (hipFree waits for the device).  4 covers the steady state of a front-end that drops one non-pose frame per frame and
+// prunes one or two pose-frames every few frames, and bounds the idle memory at 4 x 3 padded planes (72 MB at 1080p).
+constexpr size_t kSpareFrames = 4;
+void release_frame(flame_stereo_ctx* ctx, std::unordered_map<uint32_t, Frame>::iterator it) {
+  if (ctx->spare.size() < kSpareFrames) ctx->spare.push_back(it->second); else free_frame(it->second);
+  ctx->frames.erase(it);
 }
 
 size_t padded_pixels(const StereoCamera& c) { return (size_t)(c.width + 2 * c.border) * (size_t)(c.height + 2 * c.border); }
@@ -229,10 +241,91 @@ int front_border(const flame_stereo_params& P) { return (int)(P.rescale_factor_m
 // Enqueues the front-end stats block reset (the two error indices at INT_MAX, the count at 0).
 int reset_front_stats(flame_stereo_ctx* ctx) {
   ctx->h_fstats[kFrontAssert] = ctx->h_fstats[kFrontBadFrame] = INT_MAX;
-  ctx->h_fstats[kFrontCount] = 0;
-  ctx->h_fstats[3] = 0;
+  for (int w = kFrontCount; w < kFrontWords; ++w) ctx->h_fstats[w] = 0;
   SCHK(ctx, hipMemcpyAsync(ctx->d_fstats, ctx->h_fstats, kFrontWords * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   return 0;
+}
+
+// Flame::prunePoseFrames' feature loops on `d_in` (n records in device memory): validates, uploads the tables, launches
+// and waits.  On success *moved_out tells where the records are: false = in place in d_in (nothing was removed), true =
+// compacted in ctx->d_res_alt.  Nothing of the context changes here; the callers commit.
+int run_prune(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t target_frame_id, int n_keep,
+              const uint32_t* keep_ids, int n_dropped, const flame_stereo_pose* dropped, int first_new, int n,
+              StereoFeature* d_in, bool* moved_out, flame_stereo_prune_stats* stats) {
+  *moved_out = false;
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    stats->error_feature = -1;
+  }
+  if (!params || n_keep < 1 || !keep_ids || n_dropped < 0 || (n_dropped > 0 && !dropped) || first_new < 0 || first_new > n)
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  if (std::find(keep_ids, keep_ids + n_keep, target_frame_id) == keep_ids + n_keep) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  for (int k = 0; k < n_dropped; ++k)  // a pose-frame cannot both stay and go (this also keeps the target out of `dropped`)
+    if (std::find(keep_ids, keep_ids + n_keep, dropped[k].frame_id) != keep_ids + n_keep) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int border = front_border(*params);
+  if (border < 1) return FLAME_NLTGV2_ERR_INVALID_ARG;  // (rect_contains relies on a rectangle that excludes 0)
+  const int row_offset = params->do_letterbox ? ctx->cam.height / 3 : 0;
+  const PruneRegion region = {border, border + row_offset, ctx->cam.width - 2 * border,
+                              ctx->cam.height - 2 * border - 2 * row_offset};
+  if (stats) stats->num_examined = n, stats->num_features = n;
+  if (n == 0) return 0;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated; the pinned stats block is reused)
+  const size_t groups = ((size_t)n + 255) / 256;
+  if (int rc = grow(ctx, &ctx->d_res_alt, &ctx->res_alt_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_proj_tmp, &ctx->proj_tmp_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_keep, &ctx->keep_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_groups, &ctx->groups_cap, 3 * groups)) return rc;
+  if (int rc = grow(ctx, &ctx->d_ppose, &ctx->ppose_cap, (size_t)n_dropped + 1)) return rc;
+  if (int rc = grow(ctx, &ctx->d_keep_ids, &ctx->keep_ids_cap, (size_t)n_keep)) return rc;
+  std::vector<ProjectPoseEntry> table((size_t)n_dropped);
+  for (int k = 0; k < n_dropped; ++k) {
+    std::memset(&table[k], 0, sizeof table[k]);
+    table[k].frame_id = dropped[k].frame_id;
+    load_geometry(table[k].geo, ctx->cam, dropped[k].q_ref_to_new, dropped[k].t_ref_to_new);
+  }
+  if (n_dropped > 0)
+    SCHK(ctx, hipMemcpyAsync(ctx->d_ppose, table.data(), (size_t)n_dropped * sizeof(ProjectPoseEntry), hipMemcpyHostToDevice,
+                             ctx->stream));
+  SCHK(ctx, hipMemcpyAsync(ctx->d_keep_ids, keep_ids, (size_t)n_keep * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = reset_front_stats(ctx)) return rc;
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, launch_prune_features(ctx->cam, region, n_keep, ctx->d_keep_ids, n_dropped, ctx->d_ppose, target_frame_id, first_new,
+                                  n, d_in, ctx->d_proj_tmp, ctx->d_keep, ctx->d_groups, ctx->d_res_alt, ctx->d_fstats,
+                                  ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(ctx->h_fstats, ctx->d_fstats, kFrontWords * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (also: `table` and keep_ids were pageable memory)
+  const int* s = ctx->h_fstats;
+  if (s[kFrontBadFrame] != INT_MAX) {  // pfs_[feat.frame_id] of a frame that is neither kept nor listed
+    if (stats) stats->error_feature = s[kFrontBadFrame];
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  if (s[kFrontAssert] != INT_MAX) {
+    if (stats) stats->error_feature = s[kFrontAssert];
+    return FLAME_NLTGV2_ERR_ASSERT;
+  }
+  *moved_out = s[kFrontCount] != n;
+  if (stats) {
+    stats->num_moved = s[kPruneStatMoved];
+    stats->num_invalidated = s[kPruneStatInvalidated];
+    stats->num_removed = n - s[kFrontCount];
+    stats->num_features = s[kFrontCount];
+  }
+  return 0;
+}
+
+// Releases the resident frames named in `dropped` (the stream is idle: run_prune waited, or nothing was enqueued).
+int release_dropped(flame_stereo_ctx* ctx, int n_dropped, const flame_stereo_pose* dropped) {
+  int released = 0;
+  for (int k = 0; k < n_dropped; ++k) {
+    auto it = ctx->frames.find(dropped[k].frame_id);
+    if (it == ctx->frames.end()) continue;
+    release_frame(ctx, it);
+    ++released;
+  }
+  return released;
 }
 
 }  // namespace
@@ -302,7 +395,7 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   if (ctx->d_feats) (void)hipFree(ctx->d_feats);
   if (ctx->d_res) (void)hipFree(ctx->d_res);
   for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
-                  (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
+                  (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_keep_ids, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
                   (void*)ctx->d_fstats})
     if (p) (void)hipFree(p);
   if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
@@ -372,9 +465,7 @@ int flame_stereo_drop_frame(flame_stereo_ctx* ctx, uint32_t frame_id) {
   auto it = ctx->frames.find(frame_id);
   if (it == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
-  constexpr size_t kSpareFrames = 4;
-  if (ctx->spare.size() < kSpareFrames) ctx->spare.push_back(it->second); else free_frame(it->second);
-  ctx->frames.erase(it);
+  release_frame(ctx, it);
   return 0;
 }
 
@@ -642,6 +733,63 @@ int flame_stereo_detect_features(flame_stereo_ctx* ctx, const flame_stereo_param
   }
   ctx->n_res = n_res + s[kFrontCount];
   if (stats) stats->num_features = s[kFrontCount];
+  return 0;
+}
+
+int flame_stereo_prune_pose_frames(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t target_frame_id,
+                                   int n_keep, const uint32_t* keep_ids, int n_dropped, const flame_stereo_pose* dropped,
+                                   int first_new, flame_stereo_prune_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_prune_pose_frames");
+  if (int rc = enter(ctx)) return rc;
+  bool moved = false;
+  flame_stereo_prune_stats local;
+  if (!stats) stats = &local;
+  if (int rc = run_prune(ctx, params, target_frame_id, n_keep, keep_ids, n_dropped, dropped, first_new, ctx->n_res, ctx->d_res,
+                         &moved, stats))
+    return rc;
+  if (moved) {
+    std::swap(ctx->d_res, ctx->d_res_alt);
+    std::swap(ctx->res_cap, ctx->res_alt_cap);
+    ctx->n_res = stats->num_features;
+  }
+  if (ctx->n_res == 0) SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (run_prune returned before it waited)
+  stats->num_frames_dropped = release_dropped(ctx, n_dropped, dropped);
+  return 0;
+}
+
+int flame_stereo_prune_features(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t target_frame_id, int n_keep,
+                                const uint32_t* keep_ids, int n_dropped, const flame_stereo_pose* dropped, int first_new,
+                                int* n_feats, flame_stereo_feature* feats, flame_stereo_prune_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_prune_features");
+  if (int rc = enter(ctx)) return rc;
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    stats->error_feature = -1;
+  }
+  if (!n_feats || *n_feats < 0 || (*n_feats > 0 && !feats)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int n = *n_feats;
+  if (int rc = grow(ctx, &ctx->d_feats, &ctx->feats_cap, (size_t)n + 1)) return rc;
+  if (n > 0)
+    SCHK(ctx, hipMemcpyAsync(ctx->d_feats, feats, (size_t)n * sizeof(StereoFeature), hipMemcpyHostToDevice, ctx->stream));
+  bool moved = false;
+  flame_stereo_prune_stats local;
+  if (!stats) stats = &local;
+  if (int rc = run_prune(ctx, params, target_frame_id, n_keep, keep_ids, n_dropped, dropped, first_new, n, ctx->d_feats, &moved,
+                         stats))
+    return rc;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats->num_features > 0)
+    SCHK(ctx, hipMemcpy(feats, moved ? ctx->d_res_alt : ctx->d_feats, (size_t)stats->num_features * sizeof(StereoFeature),
+                        hipMemcpyDeviceToHost));
+  *n_feats = stats->num_features;
+  stats->num_frames_dropped = release_dropped(ctx, n_dropped, dropped);
+  return 0;
+}
+
+int flame_stereo_clear_features(flame_stereo_ctx* ctx) {
+  if (int rc = enter(ctx)) return rc;
+  ctx->n_res = 0;
+  ctx->n_proj = 0;
   return 0;
 }
 

@@ -1,5 +1,5 @@
 // stereo_geometry.hpp -- the EpipolarGeometry<float> pieces (src/flame/stereo/epipolar_geometry.h) that more than one
-// kernel file runs: maxDepthProjection, project(u, idepth, &u_cmp, &new_idepth) and referenceEpiline.  Used by
+// kernel file runs: maxDepthProjection, project(u, idepth, &u_cmp, &new_idepth), referenceEpiline, and cv::Rect::contains.  Used by
 // stereo_kernels.hip (updateFeatureIDepths) and feature_kernels.hip (projectFeatures, detectFeatures).  Same
 // expression order as the reference and, with the build's -ffp-contract=off, the same bits.
 #pragma once
@@ -40,6 +40,15 @@ __device__ __forceinline__ bool project_idepth(const Geo& g, const StereoCamera&
   *new_idepth = nid;
   *out = {u0 * nid, u1 * nid};
   return true;
+}
+
+// cv::Rect::contains(Point2f): the point becomes a Point2i through cvRound (round to nearest, ties to even) before
+// x <= p.x < x + w.  Unpinned reading (OpenCV is not available to check it); shared by the update kernel's move to the
+// newest pose-frame and by prunePoseFrames.  A NaN coordinate converts to 0 here (INT_MIN in cvRound on x86): outside
+// either way, as the rectangle starts at border >= 1.
+__device__ __forceinline__ bool rect_contains(int rx, int ry, int rw, int rh, V2 p) {
+  const int ix = __float2int_rn(p.x), iy = __float2int_rn(p.y);
+  return rx <= ix && ix < rx + rw && ry <= iy && iy < ry + rh;
 }
 
 // referenceEpiline h:303-325

@@ -493,11 +493,7 @@ __device__ int line_match_row(const StereoParams& P, float rescale_factor, const
 }
 
 
-// cv::Rect::contains(Point2f): the point becomes a Point2i through cvRound
-__device__ __forceinline__ bool rect_contains(int rx, int ry, int rw, int rh, V2 p) {
-  const int ix = __float2int_rn(p.x), iy = __float2int_rn(p.y);
-  return rx <= ix && ix < rx + rw && ry <= iy && iy < ry + rh;
-}
+// (rect_contains: cv::Rect::contains(Point2f), stereo_geometry.hpp)
 
 __device__ __forceinline__ uint32_t fail_feature(const StereoParams& P, StereoFeature& f) {  // -> counters to bump (bit c)
   uint32_t bits = 0;

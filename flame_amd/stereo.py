@@ -2,8 +2,9 @@
 
 Mirrors the reference interface of /root/reference/src/flame/flame.cc:1280-1752 (Flame::updateFeatureIDepths,
 Flame::trackFeature), flame.cc:1754-1860 (Flame::projectFeatures), flame.cc:708-773 + 822-1278 (the detection loop
-and Flame::detectFeatures) and src/flame/utils/frame.cc:33-71 (Frame::create, level 0).  There is no CPU path: every
-call fails with NLTGV2Error when the HIP library or a gfx950 device is missing.
+and Flame::detectFeatures), flame.cc:554-706 (Flame::prunePoseFrames) and src/flame/utils/frame.cc:33-71
+(Frame::create, level 0).  There is no CPU path: every call fails with NLTGV2Error when the HIP library or a gfx950
+device is missing.
 """
 from __future__ import annotations
 
@@ -66,6 +67,11 @@ class _FeatureStats(C.Structure):
     _fields_ = [("num_features", C.c_int32), ("num_examined", C.c_int32), ("error_feature", C.c_int32)]
 
 
+class _PruneStats(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_examined", "num_moved", "num_invalidated", "num_removed", "num_features",
+                                          "num_frames_dropped", "error_feature")]
+
+
 class _Stats(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_idepth_updates", "num_fail_max_var", "num_fail_max_dropouts",
                                           "num_fail_ref_patch_grad", "num_fail_ambiguous_match", "num_fail_max_cost",
@@ -79,7 +85,8 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_last_kernel_ms", "flame_stereo_last_hip_error", "flame_stereo_set_features",
     "flame_stereo_update_resident", "flame_stereo_get_features", "flame_stereo_features_device", "flame_stereo_set_option",
     "flame_stereo_default_detect_params", "flame_stereo_project_features", "flame_stereo_get_projected",
-    "flame_stereo_projected_device", "flame_stereo_detect_features",
+    "flame_stereo_projected_device", "flame_stereo_detect_features", "flame_stereo_prune_pose_frames",
+    "flame_stereo_prune_features", "flame_stereo_clear_features",
 )
 OPT_LANES_PER_FEATURE = 1
 
@@ -123,6 +130,12 @@ def _lib():
             "flame_stereo_projected_device": (C.c_int, [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
             "flame_stereo_detect_features": (C.c_int, [ctx, PP, C.POINTER(DetectParams), C.c_uint32, _FP, _FP, _FP,
                                                        C.c_void_p, C.c_int, _FP, C.c_uint32, C.POINTER(_FeatureStats)]),
+            "flame_stereo_prune_pose_frames": (C.c_int, [ctx, PP, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_int,
+                                                         C.POINTER(_Pose), C.c_int, C.POINTER(_PruneStats)]),
+            "flame_stereo_prune_features": (C.c_int, [ctx, PP, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_int,
+                                                      C.POINTER(_Pose), C.c_int, C.POINTER(C.c_int), C.c_void_p,
+                                                      C.POINTER(_PruneStats)]),
+            "flame_stereo_clear_features": (C.c_int, [ctx]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -320,6 +333,58 @@ class FeatureTracker:
         if rc != 0:
             raise NLTGV2Error(rc, "detect_features: %s (pixel %d)" % (status_string(rc), stats["error_feature"]))
         return stats["num_features"]
+
+    # ---- letting a pose-frame go ----
+    @staticmethod
+    def _keep_ids(keep_ids):
+        ids = [int(k) for k in keep_ids]
+        return (C.c_uint32 * max(len(ids), 1))(*ids), len(ids)
+
+    def prune_pose_frames(self, params: StereoParams, target_frame_id: int, keep_ids, dropped, first_new: int = None,
+                          raise_on_error: bool = True):
+        """Flame::prunePoseFrames (flame.cc:554-706) on the resident set: the features of the pose-frames in `dropped`
+        are re-anchored in `target_frame_id` (the kept pose-frame with the largest id), then those frames are released.
+        `keep_ids`: the ids that stay; `dropped`: list of dicts {id, q_to_new, t_to_new} with
+        T = target.pose.inverse() * pf.pose.  Records [first_new, n) are new_feats_ (removed when the move fails, where
+        older records are marked invalid); None = all are feats_.  Returns the stats dict, or (status, stats dict) when
+        raise_on_error is False."""
+        ids, n_keep = self._keep_ids(keep_ids)
+        if first_new is None:
+            first_new = self.features_device()[1]
+        st = _PruneStats()
+        rc = self._L.flame_stereo_prune_pose_frames(self._ctx, C.byref(params), target_frame_id, n_keep, ids, len(dropped),
+                                                    self._poses(dropped), int(first_new), C.byref(st))
+        stats = {n: int(getattr(st, n)) for n, _ in _PruneStats._fields_}
+        if not raise_on_error:
+            return rc, stats
+        if rc != 0:
+            raise NLTGV2Error(rc, "prune_pose_frames: %s (feature %d)" % (status_string(rc), stats["error_feature"]))
+        return stats
+
+    def prune_features(self, params: StereoParams, target_frame_id: int, keep_ids, dropped, feats: np.ndarray,
+                       first_new: int = None, raise_on_error: bool = True):
+        """The same on a host array: returns (the pruned array -- a view of `feats`, which is updated in place --,
+        stats dict), or (status, array or None, stats dict) when raise_on_error is False."""
+        if feats.dtype != FEATURE_DTYPE or not feats.flags.c_contiguous:
+            raise ValueError("feats must be a contiguous FEATURE_DTYPE array")
+        ids, n_keep = self._keep_ids(keep_ids)
+        n = C.c_int(feats.shape[0])
+        if first_new is None:
+            first_new = feats.shape[0]
+        st = _PruneStats()
+        rc = self._L.flame_stereo_prune_features(self._ctx, C.byref(params), target_frame_id, n_keep, ids, len(dropped),
+                                                 self._poses(dropped), int(first_new), C.byref(n), feats.ctypes.data,
+                                                 C.byref(st))
+        stats = {k: int(getattr(st, k)) for k, _ in _PruneStats._fields_}
+        if not raise_on_error:
+            return rc, (feats[:n.value] if rc == 0 else None), stats
+        if rc != 0:
+            raise NLTGV2Error(rc, "prune_features: %s (feature %d)" % (status_string(rc), stats["error_feature"]))
+        return feats[:n.value], stats
+
+    def clear_features(self):
+        """The feature half of Flame::clear(): no resident features, no projected set; frames stay."""
+        self._chk(self._L.flame_stereo_clear_features(self._ctx), "clear_features")
 
     def set_lanes_per_feature(self, lanes: int):
         self._chk(self._L.flame_stereo_set_option(self._ctx, OPT_LANES_PER_FEATURE, int(lanes)), "set_option")

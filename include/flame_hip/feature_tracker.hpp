@@ -15,12 +15,16 @@
 //   here       tracker.detectFeatures(params, fref, fprev, idepthmap, curr_feats, &feat_count_, &new_feats);
 //   (and the resident-set forms projectFeatures(params, pfs, fcur) / detectFeaturesResident(...), which keep the
 //   features on the device)
+//   reference  void Flame::prunePoseFrames(pfs_to_keep)  (flame.cc:554-706; on pfs_, curr_pf_, feats_, new_feats_)
+//   here       tracker.prunePoseFrames(params, &pfs_, *curr_pf_, pfs_to_keep, first_new);            // resident set
+//              tracker.prunePoseFrames(params, &pfs_, *curr_pf_, pfs_to_keep, &feats_, &new_feats_);  // host vectors
 //
 // Works with the reference's own types through templates (no Eigen/Sophus/OpenCV headers are needed here):
 //   Matrix3    anything with operator()(row, col)                      (Eigen::Matrix3f)
 //   SE3        .inverse(), operator*, .unit_quaternion().{w,x,y,z}(), .translation()(i)   (Sophus::SE3f)
 //   Frame      .id, .pose                                               (utils::Frame, frame.h)
-//   FrameMap   iterable of (id, pointer-to-Frame) pairs                 (FrameIDToFrame, flame.h:72)
+//   FrameMap   iterable of (id, pointer-to-Frame) pairs                 (FrameIDToFrame, flame.h:72);
+//              prunePoseFrames also uses its find / count / erase (std::map)
 //   Feature    layout of FeatureWithIDepth (flame.h:88-99); checked with static_asserts by adoptFeatures()
 #ifndef FLAME_HIP_FEATURE_TRACKER_HPP_
 #define FLAME_HIP_FEATURE_TRACKER_HPP_
@@ -233,9 +237,94 @@ class FeatureTracker {
           "flame_stereo_get_features");
   }
 
+  // ---- prunePoseFrames ----
+  // == Flame::prunePoseFrames(pfs_to_keep) on the resident set.  Does the host half of flame.cc:562-607 here: the kept
+  // pose-frames are pfs_to_keep intersected with *pfs; when curr_pf is not among them nothing changes and false is
+  // returned (the reference prints "Current poseframe is not in to_keep list" and returns); the target is the kept
+  // pose-frame with the largest id (pruned_pfs.crbegin() of a std::map); every other entry of *pfs goes away, with
+  // T = target.pose.inverse() * pf.pose (flame.cc:612).  After the call the dropped entries are erased from *pfs
+  // (pfs_.swap(pruned_pfs)) and their resident frames released.  Records [first_new, n) of the resident set are
+  // new_feats_ (the detections appended since the last update); first_new < 0 = all are feats_.
+  // Not imitated: the `pruned_pfs.size() == 0 -> clear()` branch (flame.cc:591-595), which cannot be reached once
+  // curr_pf was found in the list (clearFeatures() is there for a caller who wants it), and the detection queue
+  // (flame.cc:580-589), which is the caller's: drop its entries whose ref or cmp pose-frame is no longer in *pfs.
+  template <class FlameParams, class FrameMap, class Frame>
+  bool prunePoseFrames(const FlameParams& params, FrameMap* pfs, const Frame& curr_pf, const std::vector<uint32_t>& pfs_to_keep,
+                       int first_new = -1, flame_stereo_prune_stats* stats = nullptr) {
+    PrunePlan plan;
+    if (!planPrune(*pfs, curr_pf, pfs_to_keep, &plan)) return false;
+    if (first_new < 0) check(flame_stereo_features_device(ctx_, nullptr, &first_new), -1, "flame_stereo_features_device");
+    const flame_stereo_params sp = toStereoParams(params);
+    flame_stereo_prune_stats local;
+    flame_stereo_prune_stats* st = stats ? stats : &local;
+    const int rc = flame_stereo_prune_pose_frames(ctx_, &sp, plan.target, (int)plan.keep.size(), plan.keep.data(),
+                                                  (int)plan.dropped.size(), plan.dropped.empty() ? nullptr : plan.dropped.data(),
+                                                  first_new, st);
+    check(rc, st->error_feature, "flame_stereo_prune_pose_frames");
+    for (size_t k = 0; k < plan.dropped.size(); ++k) pfs->erase(plan.dropped[k].frame_id);
+    return true;
+  }
+  // The same on the reference's two vectors: one call on feats + new_feats with first_new = feats->size(), split again
+  // afterwards (a failed feats record is marked invalid and stays, a failed new_feats record is gone).
+  template <class FlameParams, class FrameMap, class Frame, class Feature>
+  bool prunePoseFrames(const FlameParams& params, FrameMap* pfs, const Frame& curr_pf, const std::vector<uint32_t>& pfs_to_keep,
+                       std::vector<Feature>* feats, std::vector<Feature>* new_feats, flame_stereo_prune_stats* stats = nullptr) {
+    PrunePlan plan;
+    if (!planPrune(*pfs, curr_pf, pfs_to_keep, &plan)) return false;
+    const size_t n_old = feats->size();
+    std::vector<Feature> all(*feats);
+    all.insert(all.end(), new_feats->begin(), new_feats->end());
+    int n = (int)all.size();
+    const flame_stereo_params sp = toStereoParams(params);
+    flame_stereo_prune_stats local;
+    flame_stereo_prune_stats* st = stats ? stats : &local;
+    const int rc = flame_stereo_prune_features(ctx_, &sp, plan.target, (int)plan.keep.size(), plan.keep.data(),
+                                               (int)plan.dropped.size(), plan.dropped.empty() ? nullptr : plan.dropped.data(),
+                                               (int)n_old, &n, all.empty() ? nullptr : adoptFeatures(all.data()), st);
+    check(rc, st->error_feature, "flame_stereo_prune_features");
+    feats->assign(all.begin(), all.begin() + n_old);
+    new_feats->assign(all.begin() + n_old, all.begin() + n);
+    for (size_t k = 0; k < plan.dropped.size(); ++k) pfs->erase(plan.dropped[k].frame_id);
+    return true;
+  }
+  // The feature half of Flame::clear(): no resident features, no projected set; the frames stay.
+  void clearFeatures() { check(flame_stereo_clear_features(ctx_), -1, "flame_stereo_clear_features"); }
+
   flame_stereo_ctx* handle() const { return ctx_; }
 
  private:
+  struct PrunePlan {
+    uint32_t target;
+    std::vector<uint32_t> keep;
+    std::vector<flame_stereo_pose> dropped;
+  };
+  // flame.cc:562-578 and 607-615: false when curr_pf is not kept.
+  template <class FrameMap, class Frame>
+  static bool planPrune(const FrameMap& pfs, const Frame& curr_pf, const std::vector<uint32_t>& pfs_to_keep, PrunePlan* plan) {
+    bool found_curr_pf = false;
+    for (size_t i = 0; i < pfs_to_keep.size(); ++i) {
+      if (pfs.count(pfs_to_keep[i]) == 0) continue;
+      bool seen = false;
+      for (size_t k = 0; k < plan->keep.size(); ++k) seen = seen || plan->keep[k] == pfs_to_keep[i];
+      if (!seen) plan->keep.push_back(pfs_to_keep[i]);
+      found_curr_pf = found_curr_pf || pfs_to_keep[i] == curr_pf.id;
+    }
+    if (!found_curr_pf) return false;
+    plan->target = plan->keep[0];
+    for (size_t k = 1; k < plan->keep.size(); ++k) plan->target = plan->keep[k] > plan->target ? plan->keep[k] : plan->target;
+    const typename FrameMap::const_iterator target = pfs.find(plan->target);
+    for (typename FrameMap::const_iterator it = pfs.begin(); it != pfs.end(); ++it) {
+      bool kept = false;
+      for (size_t k = 0; k < plan->keep.size(); ++k) kept = kept || plan->keep[k] == it->first;
+      if (kept) continue;
+      flame_stereo_pose p;
+      std::memset(&p, 0, sizeof p);
+      p.frame_id = it->first;
+      toQuatTrans(target->second->pose.inverse() * it->second->pose, p.q_ref_to_new, p.t_ref_to_new);
+      plan->dropped.push_back(p);
+    }
+    return true;
+  }
   template <class FlameParams, class Frame>
   int detect(const FlameParams& params, const Frame& fref, const Frame& fprev, const float* map_host, const void* map_device,
              int n_mask, const float* mask, uint32_t* feat_count) {

@@ -114,6 +114,7 @@ int flame_stereo_set_stream(flame_stereo_ctx* ctx, void* hip_stream);
 int flame_stereo_set_camera(flame_stereo_ctx* ctx, const float K[9], const float Kinv[9], int width, int height,
                             int border);
 
+/* (drop_frame hands the frame's buffers to the next add_frame; at most 4 sets wait there, the rest is freed.)  */
 /* utils::Frame::create, level 0 (frame.cc:33-71): uploads the width x height 8-bit image and builds, on the
  * device, img_pad (cv::BORDER_REFLECT_101) and gradx_pad / grady_pad (getCentralGradient, image_utils.h:425-470,
  * then cv::BORDER_CONSTANT 0).  The frame stays resident until dropped (a pose-frame is read by every later
@@ -143,7 +144,7 @@ int flame_stereo_update_feature_idepths_device(flame_stereo_ctx* ctx, const flam
  *   update_resident  Flame::updateFeatureIDepths on it; `stats` NULL = enqueue only (results are ordered on the stream);
  *   get_features     copies it back (feats may be NULL to query the count);
  *   features_device  its device address and count (valid until the next set_features, project_features or
- *                    detect_features). */
+ *                    detect_features, or a prune_pose_frames that removes a record). */
 int flame_stereo_set_features(flame_stereo_ctx* ctx, int n_feats, const flame_stereo_feature* feats);
 int flame_stereo_update_resident(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t new_frame_id,
                                  uint32_t curr_pf_id, int n_poses, const flame_stereo_pose* poses, flame_stereo_stats* stats);
@@ -211,13 +212,83 @@ int flame_stereo_detect_features(flame_stereo_ctx* ctx, const flame_stereo_param
                                  const void* idepthmap_device, int n_mask, const float* mask_xy, uint32_t first_id,
                                  flame_stereo_feature_stats* stats);
 
+/* ---- Letting a pose-frame go -------------------------------------------------------------------------------------
+ * Flame::prunePoseFrames(pfs_to_keep) (flame.cc:554-706, flame.h:174): every feature anchored in a pose-frame that
+ * goes away is re-anchored in the target pose-frame, then the frames are released.  The caller does the host half
+ * (flame.cc:562-607: intersect pfs_to_keep with its map, give up when the current pose-frame is not kept, pick the
+ * target, form the relative poses); include/flame_hip/feature_tracker.hpp does exactly that.  What the reference's
+ * loops (flame.cc:608-700) do is reproduced literally; our numpy restatement tests/prune_ref.py is the checker, and
+ * like the rest of the front-end the parity with the reference binary is unpinned:
+ *   1. The target is `pruned_pfs.crbegin()` of a std::map<uint32_t, ...>: the kept pose-frame with the LARGEST id
+ *      (the comment beside it says "oldest").  The caller passes it as target_frame_id.
+ *   2. `valid` is not tested: invalid features of a dropped pose-frame are moved too.  `valid` is only ever cleared.
+ *   3. Records [0, first_new) (feats_): frame_id, xy, idepth_mu and idepth_var are overwritten BEFORE the success
+ *      test, so also when the move fails (idepth_mu is then the 0 that predict returns, xy the projected point).
+ *   4. idepth_var is scaled by (idepth_pf / old_idepth)^4, formed as two squarings, and by 1 when idepth_pf < 1e-6
+ *      (the NEW value, a float compared with a double literal).  predict's own var_pred is discarded, so
+ *      process_var_factor has no effect.
+ *   5. The valid region is an integer cv::Rect (border, border + row_offset, width - 2 border, height - 2 border -
+ *      2 row_offset; border = int(rescale_factor_max * win_size / 2 + 1), row_offset = height / 3 with do_letterbox)
+ *      tested against a cv::Point2f, which OpenCV first rounds to an integer point (cvRound: to nearest, ties to
+ *      even): x <= round(p.x) < x + w.  projectFeatures' rectangle is float; this one is not.  It is the rule the
+ *      update already uses when it moves a feature to the newest pose-frame.  UNPINNED: OpenCV is not available to
+ *      check this reading against.  A NaN coordinate is outside (cvRound gives INT_MIN on x86).
+ *   6. A feature of a dropped pose-frame whose input makes EpipolarGeometry::project assert (negative or NaN
+ *      idepth_mu, a zero third coordinate; epipolar_geometry.h:128, 139) gives FLAME_NLTGV2_ERR_ASSERT with the lowest
+ *      such index; nothing changes.
+ *   7. A failed move (behind the target camera, or outside the region) of a record in [0, first_new) marks it invalid
+ *      and keeps it; a failed record in [first_new, n) (new_feats_) is removed, unrewritten, and the survivors keep
+ *      their order.  The resident set holds both lists because detect_features appends at once where the reference
+ *      parks detections in new_feats_ until the next update() (flame.cc:257); the two outcomes differ downstream (the
+ *      update does not test `valid` on entry and can set it again), hence first_new.
+ *   8. The `pruned_pfs.size() == 0 -> clear()` branch (flame.cc:591-595) cannot be reached once the current pose-frame
+ *      was found in the list; flame_stereo_clear_features is there for a caller that wants Flame::clear().
+ * The detection queue (flame.cc:580-589) is the caller's. */
+typedef struct flame_stereo_prune_stats {
+  int32_t num_examined;       /* features looked at */
+  int32_t num_moved;          /* re-anchored in the target pose-frame, move succeeded */
+  int32_t num_invalidated;    /* index <  first_new: move failed or left the valid region, marked invalid */
+  int32_t num_removed;        /* index >= first_new: the same, removed */
+  int32_t num_features;       /* features in the set afterwards */
+  int32_t num_frames_dropped; /* resident frames released */
+  int32_t error_feature;      /* -1, or the lowest offending feature index */
+} flame_stereo_prune_stats;
+
+/* Flame::prunePoseFrames on the resident set.  Records [0, first_new) are feats_, records [first_new, n) are
+ * new_feats_ (the detections appended since the last update_resident); first_new = the resident count means "all
+ * feats_"; 0 <= first_new <= n.
+ *   keep_ids   the ids of the pose-frames that stay (n_keep >= 1); target_frame_id must be one of them.
+ *   dropped    one entry per pose-frame that goes away, with q/t_ref_to_new = target.pose.inverse() * pf.pose
+ *              (flame.cc:612-615; the *_to_pf members are not read).  An id in both lists is an error.
+ * A feature whose frame is neither kept nor listed in `dropped` gives FLAME_NLTGV2_ERR_INVALID_ARG with its index.  On
+ * any error the resident set, the projected set and the resident frames are unchanged.  After success every resident
+ * frame named in `dropped` is released as by flame_stereo_drop_frame: its buffers wait for the next add_frame, at most
+ * 4 sets of them (what a front-end that prunes every few frames reuses); further ones are freed with hipFree, which
+ * waits for the whole device -- acceptable in a call made every few seconds.  Frames named in neither list (the current
+ * and previous non-pose frames) stay.  The projected set is not touched.
+ * The move is in place: the address from flame_stereo_features_device stays valid when nothing was removed
+ * (stats.num_removed == 0); otherwise the call may move the resident set, like project_features, and the address is
+ * valid until then.  Enqueues on the context's stream and waits once.  `stats` may be NULL. */
+int flame_stereo_prune_pose_frames(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t target_frame_id,
+                                   int n_keep, const uint32_t* keep_ids, int n_dropped, const flame_stereo_pose* dropped,
+                                   int first_new, flame_stereo_prune_stats* stats);
+/* The same on a host array (the four-edit integration): `feats` (*n_feats records) is updated in place and *n_feats
+ * rewritten; the resident set is not read or changed, the resident frames named in `dropped` are released. */
+int flame_stereo_prune_features(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t target_frame_id, int n_keep,
+                                const uint32_t* keep_ids, int n_dropped, const flame_stereo_pose* dropped, int first_new,
+                                int* n_feats, flame_stereo_feature* feats, flame_stereo_prune_stats* stats);
+/* The feature half of Flame::clear() (flame.h:179-202): no resident features, no projected set.  Frames stay, as pfs_
+ * does in the reference. */
+int flame_stereo_clear_features(flame_stereo_ctx* ctx);
+
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
  * bit for bit. */
 enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1 };
 int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value);
 
-/* Device time of the last update kernel (or of the kernels of the last project_features / detect_features) in
+/* Device time of the last update kernel (or of the kernels of the last project_features / detect_features /
+ * prune_pose_frames / prune_features) in
  * milliseconds (HIP events on the context's stream); < 0 if none. */
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx);
 int flame_stereo_last_hip_error(const flame_stereo_ctx* ctx);
