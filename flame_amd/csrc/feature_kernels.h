@@ -72,4 +72,31 @@ hipError_t launch_prune_features(const StereoCamera& cam, const PruneRegion& reg
                                  StereoFeature* feats, StereoFeature* moved, uint8_t* flags, int* counts,
                                  StereoFeature* feats_out, int* stats, hipStream_t stream);
 
+// syncGraph's preprocessing (flame.cc:1954-1980): what the rule reads of flame::Params, and graph_scale.
+struct SelectRule {
+  float idepth_var_max_graph, min_height, max_height, graph_scale;
+  int adaptive_data_weights;
+};
+// One per pose-frame: row 1 of the rotation of pf.pose (camera -> world) and the y of its translation -- all that
+// -world.y needs (select_pose_entry forms them on the host from the quaternion).
+struct SelectPoseEntry {
+  uint32_t frame_id;
+  float r10, r11, r12, ty;
+};
+SelectPoseEntry select_pose_entry(uint32_t frame_id, const float q[4], const float t[3]);
+// k_select_flag's class byte per record.
+constexpr uint8_t kSelectTaken = 0, kSelectInvalid = 1, kSelectFailVar = 2, kSelectFailHeight = 3, kSelectNone = 255;
+// The selection's stats words beyond kFrontAssert / kFrontBadFrame / kFrontCount (= V): the three reject counts and
+// [kSelectBadId], the lowest selected index whose id does not fit int32_t (starts at INT_MAX).
+constexpr int kSelectStatInvalid = 3, kSelectStatFailVar = 4, kSelectStatFailHeight = 5, kSelectBadId = 6;
+// k_select_flag + k_select_scatter on `feats` / `proj` (n index-aligned records each, only read).  `cls` n bytes,
+// `counts` 4 * ((n + 255) / 256) ints.  `out`: kFrontWords stats words (preset by the caller: the three error words at
+// INT_MAX, the rest 0), then feat_id[V] | pos[2V] | data_term[V] | data_weight[V] | feat_index[V] with the sections
+// `section` words apart (section >= n), or V words apart when section <= 0; room for kFrontWords + 6 n words.  Nothing but
+// the error words is written when one of them was raised.
+hipError_t launch_select_graph_features(const StereoCamera& cam, const SelectRule& rule, int n_poses,
+                                        const SelectPoseEntry* poses, int n, const StereoFeature* feats,
+                                        const StereoFeature* proj, uint8_t* cls, int* counts, int section, int* out,
+                                        hipStream_t stream);
+
 }  // namespace flame_hip

@@ -48,6 +48,19 @@
 //       with valid = 0;
 //    8. (the `pruned_pfs.size() == 0 -> clear()` branch is unreachable once the current pose-frame was found.)
 //
+// syncGraph's preprocessing (flame.cc:1954-1980, and the data-term lines 2001-2004, 2041-2044):
+//   k_select_flag      one lane per record: FLAME_ASSERT(idepth >= 0) and pfs.at(frame_id) for EVERY record (the lowest
+//                      failing index of each by atomicMin), the height of the RESIDENT record's point in the world, its
+//                      class (selected, or the first failing test: invalid, variance, height) as a byte, and four counts
+//                      per workgroup (four arrays).
+//   k_select_scatter   one lane per record, after k_select_flag on the same stream: does nothing when an error index was
+//                      raised.  The selected records are compacted stably (group_base / group_rank) into the output
+//                      block: feat_id from the resident record, pos / data_term / data_weight from the PROJECTED record
+//                      at the same index, and the index itself.  Writes the totals.
+//   The output block is kFrontWords stats words, then five sections S words apart (pos: 2 S): S = the record count when
+//   the host copies the whole block down in one piece, or the selected count (every workgroup sums it itself) when the
+//   host copies the stats first and then 6 V words.
+//
 // Arithmetic keeps the reference's expression order and width; the build has -ffp-contract=off and correctly rounded
 // division and sqrt, so results are bit-identical to the reference's scalar float code.  Nothing depends on the order
 // in which atomics arrive: the only atomics are atomicMin of an error index.
@@ -265,6 +278,105 @@ __global__ __launch_bounds__(kGroup) void k_prune_commit(const int n, const uint
   }
 }
 
+// ---- syncGraph's preprocessing ----------------------------------------------------------------------------------
+
+// The class of one record: selected, or the first of the reference's tests that fails (flame.cc:1976-1977).
+__device__ uint8_t select_one(const StereoCamera& cam, const SelectRule& rule, int n_poses,
+                              const SelectPoseEntry* __restrict__ poses, int i, const StereoFeature& f,
+                              int* __restrict__ stats) {
+  const float idepth = f.idepth_mu;
+  bool error = false;
+  if (!(idepth >= 0.0f)) {  // FLAME_ASSERT(idepth >= 0.0f) (flame.cc:1968): every record, valid or not; NaN fails
+    atomicMin(&stats[kFrontAssert], i);
+    error = true;
+  }
+  int k = 0;
+  while (k < n_poses && poses[k].frame_id != f.frame_id) ++k;
+  if (k == n_poses) {  // pfs.at(feat.frame_id) (flame.cc:1974): every record
+    atomicMin(&stats[kFrontBadFrame], i);
+    error = true;
+  }
+  if (error) return kSelectNone;
+  // pix /= idepth: three true divisions (Eigen >= 3.3); Kinv * pix: the full product, each row (a + b) + c
+  const float px = f.x / idepth, py = f.y / idepth, pz = 1.0f / idepth;
+  const float X = (cam.Kinv[0] * px + cam.Kinv[1] * py) + cam.Kinv[2] * pz;
+  const float Y = (cam.Kinv[3] * px + cam.Kinv[4] * py) + cam.Kinv[5] * pz;
+  const float Z = (cam.Kinv[6] * px + cam.Kinv[7] * py) + cam.Kinv[8] * pz;
+  const SelectPoseEntry P = poses[k];
+  const float wy = ((P.r10 * X + P.r11 * Y) + P.r12 * Z) + P.ty;
+  const float h = -wy;
+  if (!f.valid) return kSelectInvalid;
+  if (!(f.idepth_var < rule.idepth_var_max_graph)) return kSelectFailVar;
+  if (!(h >= rule.min_height && h <= rule.max_height)) return kSelectFailHeight;
+  if (f.id > (uint32_t)INT_MAX) atomicMin(&stats[kSelectBadId], i);  // the sync's feat_id is int32_t >= 0
+  return kSelectTaken;
+}
+
+__global__ __launch_bounds__(kGroup) void k_select_flag(const StereoCamera cam, const SelectRule rule, const int n_poses,
+                                                        const SelectPoseEntry* __restrict__ poses, const int n,
+                                                        const StereoFeature* __restrict__ feats, uint8_t* __restrict__ cls,
+                                                        int* __restrict__ counts, int* __restrict__ stats) {
+  const int i = blockIdx.x * kGroup + threadIdx.x;
+  uint8_t c = kSelectNone;
+  if (i < n) {
+    c = select_one(cam, rule, n_poses, poses, i, feats[i], stats);
+    cls[i] = c;
+  }
+  const int c_taken = __syncthreads_count(c == kSelectTaken);
+  const int c_invalid = __syncthreads_count(c == kSelectInvalid);
+  const int c_var = __syncthreads_count(c == kSelectFailVar);
+  const int c_height = __syncthreads_count(c == kSelectFailHeight);
+  if (threadIdx.x == 0) {
+    counts[blockIdx.x] = c_taken;
+    counts[gridDim.x + blockIdx.x] = c_invalid;
+    counts[2 * gridDim.x + blockIdx.x] = c_var;
+    counts[3 * gridDim.x + blockIdx.x] = c_height;
+  }
+}
+
+// `out`: kFrontWords stats words (k_select_flag's `stats`), then the five sections, `section` words apart (pos: twice
+// that); section <= 0 = the selected count.
+__global__ __launch_bounds__(kGroup) void k_select_scatter(const SelectRule rule, const int n, const uint8_t* __restrict__ cls,
+                                                           const int* __restrict__ counts,
+                                                           const StereoFeature* __restrict__ feats,
+                                                           const StereoFeature* __restrict__ proj, const int section,
+                                                           int* __restrict__ out) {
+  if (out[kFrontAssert] != INT_MAX || out[kFrontBadFrame] != INT_MAX || out[kSelectBadId] != INT_MAX) return;  // (uniform)
+  const int i = blockIdx.x * kGroup + threadIdx.x;
+  const int groups = gridDim.x;
+  const int taken_all = group_base(counts, groups);
+  __syncthreads();  // (group_base's LDS words are reused)
+  const int base = group_base(counts, blockIdx.x);
+  const bool taken = i < n && cls[i] == kSelectTaken;
+  int total;
+  const int at = base + group_rank(taken, &total);
+  if (taken) {
+    const size_t S = (size_t)(section > 0 ? section : taken_all);
+    int* body = out + kFrontWords;
+    const StereoFeature c = proj[i];  // feats_in_curr[feat_id_to_idx[id]]: neither its `valid` nor its `id` is read
+    body[at] = (int)feats[i].id;
+    float* pos = (float*)(body + S);
+    pos[2 * (size_t)at] = c.x, pos[2 * (size_t)at + 1] = c.y;
+    ((float*)(body + 3 * S))[at] = c.idepth_mu / rule.graph_scale;
+    ((float*)(body + 4 * S))[at] = rule.adaptive_data_weights ? 1.0f / c.idepth_var : 1.0f;
+    (body + 5 * S)[at] = i;
+  }
+  if (blockIdx.x == 0) {
+    __syncthreads();
+    const int n_invalid = group_base(counts + groups, groups);
+    __syncthreads();
+    const int n_var = group_base(counts + 2 * groups, groups);
+    __syncthreads();
+    const int n_height = group_base(counts + 3 * groups, groups);
+    if (threadIdx.x == 0) {
+      out[kFrontCount] = taken_all;
+      out[kSelectStatInvalid] = n_invalid;
+      out[kSelectStatFailVar] = n_var;
+      out[kSelectStatFailHeight] = n_height;
+    }
+  }
+}
+
 // ---- detectFeatures ---------------------------------------------------------------------------------------------
 
 // A mask point (x, y) clears cell (uint(y / win), uint(x / win)) (flame.cc:1006-1010); `stride` floats between points.
@@ -410,6 +522,31 @@ hipError_t launch_prune_features(const StereoCamera& cam, const PruneRegion& reg
   hipLaunchKernelGGL(k_prune_move, dim3(groups), dim3(kGroup), 0, stream, cam, region, n_keep, keep_ids, n_dropped, dropped,
                      target_frame_id, first_new, n, feats, moved, flags, counts, stats);
   hipLaunchKernelGGL(k_prune_commit, dim3(groups), dim3(kGroup), 0, stream, n, flags, counts, feats, moved, feats_out, stats);
+  return hipGetLastError();
+}
+
+SelectPoseEntry select_pose_entry(uint32_t frame_id, const float q[4], const float t[3]) {
+  // row 1 of Eigen's Quaternion::toRotationMatrix() (w, x, y, z), in float: the host build is uncontracted like the device's
+  const float w = q[0], x = q[1], y = q[2], z = q[3];
+  const float tx = 2.0f * x, ty = 2.0f * y, tz = 2.0f * z;
+  const float twx = tx * w, twz = tz * w, txx = tx * x, txy = tx * y, tyz = ty * z, tzz = tz * z;
+  SelectPoseEntry e;
+  e.frame_id = frame_id;
+  e.r10 = txy + twz;
+  e.r11 = 1.0f - (txx + tzz);
+  e.r12 = tyz - twx;
+  e.ty = t[1];
+  return e;
+}
+
+hipError_t launch_select_graph_features(const StereoCamera& cam, const SelectRule& rule, int n_poses,
+                                        const SelectPoseEntry* poses, int n, const StereoFeature* feats,
+                                        const StereoFeature* proj, uint8_t* cls, int* counts, int section, int* out,
+                                        hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const int groups = (n + kGroup - 1) / kGroup;
+  hipLaunchKernelGGL(k_select_flag, dim3(groups), dim3(kGroup), 0, stream, cam, rule, n_poses, poses, n, feats, cls, counts, out);
+  hipLaunchKernelGGL(k_select_scatter, dim3(groups), dim3(kGroup), 0, stream, rule, n, cls, counts, feats, proj, section, out);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // stereo_capi.hip -- C-ABI of include/flame_stereo.h: resident frames (padded image + gradients built on the
 // device), the per-launch pose table, the host/device feature-array entry points of the per-feature epipolar
-// inverse-depth update, and projectFeatures / detectFeatures on the resident set.  All arithmetic of the path runs in
+// inverse-depth update, projectFeatures / detectFeatures / prunePoseFrames on the resident set, and the selection of the
+// graph's vertices (syncGraph's preprocessing).  All arithmetic of the path runs in
 // stereo_kernels.hip and feature_kernels.hip; this file only moves bytes.
 #include <hip/hip_runtime.h>
 
@@ -83,6 +84,15 @@ struct flame_stereo_ctx {
   size_t mask_cap = 0;
   int* d_fstats = nullptr;
   int* h_fstats = nullptr;  // pinned, kFrontWords ints
+  // select_graph_features (feature_kernels.hip)
+  bool aligned = false;  // the resident and the projected set are index-aligned (set by project_features)
+  SelectPoseEntry* d_spose = nullptr;
+  size_t spose_cap = 0;
+  int* d_sel = nullptr;  // the output block: kFrontWords stats words + 6 words per record
+  size_t sel_cap = 0;
+  int* h_sel = nullptr;  // pinned, the same
+  size_t h_sel_cap = 0;
+  int graph_copy = 0;  // FLAME_STEREO_OPT_GRAPH_COPY
 };
 
 namespace {
@@ -328,6 +338,85 @@ int release_dropped(flame_stereo_ctx* ctx, int n_dropped, const flame_stereo_pos
   return released;
 }
 
+void clear_graph_inputs(flame_stereo_graph_inputs* out) {
+  std::memset(out, 0, sizeof *out);
+  out->error_feature = -1;
+}
+
+// syncGraph's preprocessing on the index-aligned device arrays d_feats / d_proj (n records each, only read): validates,
+// uploads the pose table, launches, copies the result into the pinned block and waits for it.
+int run_select(flame_stereo_ctx* ctx, const flame_stereo_graph_params* gp, float graph_scale, int n_poses,
+               const flame_stereo_world_pose* poses, int n, const StereoFeature* d_feats, const StereoFeature* d_proj,
+               flame_stereo_graph_inputs* out) {
+  out->num_examined = n;
+  if (n == 0) return 0;
+  const size_t groups = ((size_t)n + 255) / 256;
+  const size_t words = (size_t)kFrontWords + 6 * (size_t)n;
+  if (int rc = grow(ctx, &ctx->d_keep, &ctx->keep_cap, (size_t)n)) return rc;
+  if (int rc = grow(ctx, &ctx->d_groups, &ctx->groups_cap, 4 * groups)) return rc;
+  if (int rc = grow(ctx, &ctx->d_spose, &ctx->spose_cap, (size_t)n_poses + 1)) return rc;
+  if (int rc = grow(ctx, &ctx->d_sel, &ctx->sel_cap, words)) return rc;
+  if (ctx->h_sel_cap < words) {
+    if (ctx->h_sel) SCHK(ctx, hipHostFree(ctx->h_sel));
+    ctx->h_sel = nullptr, ctx->h_sel_cap = 0;
+    const size_t want = words + words / 2 + 16;
+    SCHK(ctx, hipHostMalloc((void**)&ctx->h_sel, want * sizeof(int), hipHostMallocDefault));
+    ctx->h_sel_cap = want;
+  }
+  std::vector<SelectPoseEntry> table((size_t)n_poses);
+  for (int k = 0; k < n_poses; ++k) table[k] = select_pose_entry(poses[k].frame_id, poses[k].q, poses[k].t);
+  if (n_poses > 0)
+    SCHK(ctx, hipMemcpyAsync(ctx->d_spose, table.data(), (size_t)n_poses * sizeof(SelectPoseEntry), hipMemcpyHostToDevice,
+                             ctx->stream));
+  for (int w = 0; w < kFrontWords; ++w) ctx->h_fstats[w] = 0;
+  ctx->h_fstats[kFrontAssert] = ctx->h_fstats[kFrontBadFrame] = ctx->h_fstats[kSelectBadId] = INT_MAX;
+  SCHK(ctx, hipMemcpyAsync(ctx->d_sel, ctx->h_fstats, kFrontWords * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  const SelectRule rule = {gp->idepth_var_max_graph, gp->min_height, gp->max_height, graph_scale, gp->adaptive_data_weights};
+  // The copy-out.  0: the whole block in one copy, sections n words apart, one wait.  1: the stats words, a wait, then the
+  // 6 V words the kernel packed V words apart, a second wait.  Which is faster: profiles/graph_inputs.txt.
+  const bool count_first = ctx->graph_copy == 1;
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, launch_select_graph_features(ctx->cam, rule, n_poses, ctx->d_spose, n, d_feats, d_proj, ctx->d_keep, ctx->d_groups,
+                                         count_first ? 0 : n, ctx->d_sel, ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(ctx->h_sel, ctx->d_sel, (count_first ? (size_t)kFrontWords : words) * sizeof(int),
+                           hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (also: `table` was pageable memory)
+  const int* s = ctx->h_sel;
+  if (s[kFrontAssert] != INT_MAX || s[kFrontBadFrame] != INT_MAX) {
+    // the reference's loop stops at the first record that fails either; within a record the assert comes first
+    const bool is_assert = s[kFrontAssert] <= s[kFrontBadFrame];
+    out->error_feature = is_assert ? s[kFrontAssert] : s[kFrontBadFrame];
+    return is_assert ? FLAME_NLTGV2_ERR_ASSERT : FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  if (s[kSelectBadId] != INT_MAX) {  // an id >= 2^31 among the selected
+    out->error_feature = s[kSelectBadId];
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  const int V = s[kFrontCount];
+  if (V < 0 || V > n) return FLAME_NLTGV2_ERR_HIP;  // (cannot happen: the kernel counted n records)
+  if (count_first && V > 0) {
+    SCHK(ctx, hipMemcpyAsync(ctx->h_sel + kFrontWords, ctx->d_sel + kFrontWords, 6 * (size_t)V * sizeof(int), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  const size_t S = count_first ? (size_t)V : (size_t)n;
+  const int* body = ctx->h_sel + kFrontWords;
+  out->V = V;
+  out->num_invalid = s[kSelectStatInvalid];
+  out->num_fail_var = s[kSelectStatFailVar];
+  out->num_fail_height = s[kSelectStatFailHeight];
+  if (V > 0) {
+    out->feat_id = body;
+    out->pos = (const float*)(body + S);
+    out->data_term = (const float*)(body + 3 * S);
+    out->data_weight = (const float*)(body + 4 * S);
+    out->feat_index = body + 5 * S;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -396,9 +485,10 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   if (ctx->d_res) (void)hipFree(ctx->d_res);
   for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
                   (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_keep_ids, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
-                  (void*)ctx->d_fstats})
+                  (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel})
     if (p) (void)hipFree(p);
   if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
+  if (ctx->h_sel) (void)hipHostFree(ctx->h_sel);
   if (ctx->d_stats) (void)hipFree(ctx->d_stats);
   if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -522,6 +612,10 @@ int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value) {
       if (value != 0 && value != 1 && value != 16) return FLAME_NLTGV2_ERR_INVALID_ARG;
       ctx->lanes_per_feature = value;
       return 0;
+    case FLAME_STEREO_OPT_GRAPH_COPY:
+      if (value != 0 && value != 1) return FLAME_NLTGV2_ERR_INVALID_ARG;
+      ctx->graph_copy = value;
+      return 0;
     default:
       return FLAME_NLTGV2_ERR_INVALID_ARG;
   }
@@ -538,6 +632,7 @@ int flame_stereo_set_features(flame_stereo_ctx* ctx, int n_feats, const flame_st
     SCHK(ctx, hipStreamSynchronize(ctx->stream));  // `feats` is the caller's (pageable) memory
   }
   ctx->n_res = n_feats;
+  ctx->aligned = false;
   return 0;
 }
 
@@ -589,6 +684,7 @@ int flame_stereo_project_features(flame_stereo_ctx* ctx, const flame_stereo_para
   if (stats) stats->num_examined = n;
   if (n == 0) {
     ctx->n_proj = 0;
+    ctx->aligned = true;
     return 0;
   }
   SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated; the pinned stats block is reused)
@@ -633,6 +729,7 @@ int flame_stereo_project_features(flame_stereo_ctx* ctx, const flame_stereo_para
   std::swap(ctx->d_proj, ctx->d_proj_alt);
   std::swap(ctx->proj_cap, ctx->proj_alt_cap);
   ctx->n_res = ctx->n_proj = s[kFrontCount];
+  ctx->aligned = true;
   if (stats) stats->num_features = s[kFrontCount];
   return 0;
 }
@@ -732,6 +829,7 @@ int flame_stereo_detect_features(flame_stereo_ctx* ctx, const flame_stereo_param
     return FLAME_NLTGV2_ERR_ASSERT;
   }
   ctx->n_res = n_res + s[kFrontCount];
+  if (s[kFrontCount] > 0) ctx->aligned = false;  // (records without a projected counterpart)
   if (stats) stats->num_features = s[kFrontCount];
   return 0;
 }
@@ -751,6 +849,7 @@ int flame_stereo_prune_pose_frames(flame_stereo_ctx* ctx, const flame_stereo_par
     std::swap(ctx->d_res, ctx->d_res_alt);
     std::swap(ctx->res_cap, ctx->res_alt_cap);
     ctx->n_res = stats->num_features;
+    ctx->aligned = false;  // a record was removed
   }
   if (ctx->n_res == 0) SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (run_prune returned before it waited)
   stats->num_frames_dropped = release_dropped(ctx, n_dropped, dropped);
@@ -790,7 +889,61 @@ int flame_stereo_clear_features(flame_stereo_ctx* ctx) {
   if (int rc = enter(ctx)) return rc;
   ctx->n_res = 0;
   ctx->n_proj = 0;
+  ctx->aligned = false;
   return 0;
+}
+
+void flame_stereo_default_graph_params(flame_stereo_graph_params* p) {
+  if (!p) return;
+  p->idepth_var_max_graph = 1e-2f;
+  p->min_height = 0.1f;
+  p->max_height = 4.0f;
+  p->adaptive_data_weights = 0;
+}
+
+int flame_stereo_select_graph_features(flame_stereo_ctx* ctx, const flame_stereo_graph_params* gp, float graph_scale, int n_poses,
+                                       const flame_stereo_world_pose* poses, flame_stereo_graph_inputs* out) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_select_graph_features");
+  if (out) clear_graph_inputs(out);
+  if (int rc = enter(ctx)) return rc;
+  if (!gp || !out || n_poses < 0 || (n_poses > 0 && !poses)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  if (!ctx->aligned || ctx->n_proj != ctx->n_res) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated; the pinned blocks are reused)
+  const int rc = run_select(ctx, gp, graph_scale, n_poses, poses, ctx->n_res, ctx->d_res, ctx->d_proj, out);
+  if (rc != 0) {
+    const int e = out->error_feature, n = out->num_examined;
+    clear_graph_inputs(out);
+    out->error_feature = e, out->num_examined = n;
+  }
+  return rc;
+}
+
+int flame_stereo_select_graph_features_arrays(flame_stereo_ctx* ctx, const flame_stereo_graph_params* gp, float graph_scale,
+                                              int n_poses, const flame_stereo_world_pose* poses, int n_feats,
+                                              const flame_stereo_feature* feats, const flame_stereo_feature* feats_in_curr,
+                                              flame_stereo_graph_inputs* out) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_select_graph_features_arrays");
+  if (out) clear_graph_inputs(out);
+  if (int rc = enter(ctx)) return rc;
+  if (!gp || !out || n_poses < 0 || (n_poses > 0 && !poses) || n_feats < 0 || (n_feats > 0 && (!feats || !feats_in_curr)))
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated; the pinned blocks are reused)
+  if (int rc = grow(ctx, &ctx->d_feats, &ctx->feats_cap, (size_t)n_feats + 1)) return rc;
+  if (int rc = grow(ctx, &ctx->d_proj_tmp, &ctx->proj_tmp_cap, (size_t)n_feats + 1)) return rc;
+  if (n_feats > 0) {
+    const size_t bytes = (size_t)n_feats * sizeof(StereoFeature);
+    SCHK(ctx, hipMemcpyAsync(ctx->d_feats, feats, bytes, hipMemcpyHostToDevice, ctx->stream));
+    SCHK(ctx, hipMemcpyAsync(ctx->d_proj_tmp, feats_in_curr, bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const int rc = run_select(ctx, gp, graph_scale, n_poses, poses, n_feats, ctx->d_feats, ctx->d_proj_tmp, out);
+  if (rc != 0) {
+    const int e = out->error_feature, n = out->num_examined;
+    clear_graph_inputs(out);
+    out->error_feature = e, out->num_examined = n;
+  }
+  return rc;
 }
 
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx) {

@@ -2,7 +2,7 @@
 
 Mirrors the reference interface of /root/reference/src/flame/flame.cc:1280-1752 (Flame::updateFeatureIDepths,
 Flame::trackFeature), flame.cc:1754-1860 (Flame::projectFeatures), flame.cc:708-773 + 822-1278 (the detection loop
-and Flame::detectFeatures), flame.cc:554-706 (Flame::prunePoseFrames) and src/flame/utils/frame.cc:33-71
+and Flame::detectFeatures), flame.cc:554-706 (Flame::prunePoseFrames), flame.cc:1954-1980 (the preprocessing of Flame::syncGraph) and src/flame/utils/frame.cc:33-71
 (Frame::create, level 0).  There is no CPU path: every call fails with NLTGV2Error when the HIP library or a gfx950
 device is missing.
 """
@@ -72,6 +72,34 @@ class _PruneStats(C.Structure):
                                           "num_frames_dropped", "error_feature")]
 
 
+class GraphParams(C.Structure):
+    """flame_stereo_graph_params: the members of flame::Params that syncGraph's preprocessing reads; defaults are the
+    reference's (flame_stereo_default_graph_params)."""
+    _fields_ = [("idepth_var_max_graph", C.c_float), ("min_height", C.c_float), ("max_height", C.c_float),
+                ("adaptive_data_weights", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib().flame_stereo_default_graph_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown graph parameter %r" % k)
+            setattr(self, k, v)
+
+
+class _WorldPose(C.Structure):
+    _fields_ = [("frame_id", C.c_uint32), ("q", C.c_float * 4), ("t", C.c_float * 3)]
+
+
+_I32P = C.POINTER(C.c_int32)
+GRAPH_COUNTERS = ("num_examined", "num_invalid", "num_fail_var", "num_fail_height", "error_feature")
+
+
+class _GraphInputs(C.Structure):
+    _fields_ = [("V", C.c_int32), ("feat_id", _I32P), ("pos", C.POINTER(C.c_float)), ("data_term", C.POINTER(C.c_float)),
+                ("data_weight", C.POINTER(C.c_float)), ("feat_index", _I32P)] + [(n, C.c_int32) for n in GRAPH_COUNTERS]
+
+
 class _Stats(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_idepth_updates", "num_fail_max_var", "num_fail_max_dropouts",
                                           "num_fail_ref_patch_grad", "num_fail_ambiguous_match", "num_fail_max_cost",
@@ -86,9 +114,11 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_update_resident", "flame_stereo_get_features", "flame_stereo_features_device", "flame_stereo_set_option",
     "flame_stereo_default_detect_params", "flame_stereo_project_features", "flame_stereo_get_projected",
     "flame_stereo_projected_device", "flame_stereo_detect_features", "flame_stereo_prune_pose_frames",
-    "flame_stereo_prune_features", "flame_stereo_clear_features",
+    "flame_stereo_prune_features", "flame_stereo_clear_features", "flame_stereo_default_graph_params",
+    "flame_stereo_select_graph_features", "flame_stereo_select_graph_features_arrays",
 )
 OPT_LANES_PER_FEATURE = 1
+OPT_GRAPH_COPY = 2
 
 _READY = False
 _FP = C.POINTER(C.c_float)
@@ -136,6 +166,12 @@ def _lib():
                                                       C.POINTER(_Pose), C.c_int, C.POINTER(C.c_int), C.c_void_p,
                                                       C.POINTER(_PruneStats)]),
             "flame_stereo_clear_features": (C.c_int, [ctx]),
+            "flame_stereo_default_graph_params": (None, [C.POINTER(GraphParams)]),
+            "flame_stereo_select_graph_features": (C.c_int, [ctx, C.POINTER(GraphParams), C.c_float, C.c_int,
+                                                             C.POINTER(_WorldPose), C.POINTER(_GraphInputs)]),
+            "flame_stereo_select_graph_features_arrays": (C.c_int, [ctx, C.POINTER(GraphParams), C.c_float, C.c_int,
+                                                                    C.POINTER(_WorldPose), C.c_int, C.c_void_p, C.c_void_p,
+                                                                    C.POINTER(_GraphInputs)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -385,6 +421,74 @@ class FeatureTracker:
     def clear_features(self):
         """The feature half of Flame::clear(): no resident features, no projected set; frames stay."""
         self._chk(self._L.flame_stereo_clear_features(self._ctx), "clear_features")
+
+    # ---- which features become vertices of the graph ----
+    @staticmethod
+    def _world_poses(world_poses):
+        arr = (_WorldPose * max(len(world_poses), 1))()
+        for i, p in enumerate(world_poses):
+            arr[i].frame_id = int(p["id"])
+            q, t = _f32(p["q"], 4), _f32(p["t"], 3)
+            for k in range(4):
+                arr[i].q[k] = float(q[k])
+            for k in range(3):
+                arr[i].t[k] = float(t[k])
+        return arr
+
+    def select_graph_features(self, gparams: GraphParams, graph_scale: float, world_poses, feats: np.ndarray = None,
+                              feats_in_curr: np.ndarray = None, raise_on_error: bool = True):
+        """The preprocessing of Flame::syncGraph (flame.cc:1954-1980): which features become vertices of the graph and
+        with which data term.  `world_poses`: list of dicts {id, q, t} with pf.pose (camera -> world) of every
+        pose-frame.  Without the two arrays it runs on the resident and the projected set (index-aligned, i.e. right after
+        project_features); with them (FEATURE_DTYPE, the same length) on those, touching neither resident set.  Returns a
+        dict of numpy copies feat_id [V], pos [V, 2], data_term [V], data_weight [V], feat_index [V] -- what
+        flame_nltgv2_sync_input takes -- plus V and the counters; (status, dict) when raise_on_error is False."""
+        out = _GraphInputs()
+        wp = self._world_poses(world_poses)
+        if (feats is None) != (feats_in_curr is None):
+            raise ValueError("feats and feats_in_curr go together")
+        if feats is None:
+            rc = self._L.flame_stereo_select_graph_features(self._ctx, C.byref(gparams), graph_scale, len(world_poses), wp,
+                                                            C.byref(out))
+        else:
+            for a in (feats, feats_in_curr):
+                if a.dtype != FEATURE_DTYPE or not a.flags.c_contiguous:
+                    raise ValueError("feats must be a contiguous FEATURE_DTYPE array")
+            if feats.shape != feats_in_curr.shape:
+                raise ValueError("feats and feats_in_curr must be index-aligned")
+            rc = self._L.flame_stereo_select_graph_features_arrays(self._ctx, C.byref(gparams), graph_scale, len(world_poses),
+                                                                   wp, feats.shape[0], feats.ctypes.data,
+                                                                   feats_in_curr.ctypes.data, C.byref(out))
+        V = int(out.V)
+        res = {n: int(getattr(out, n)) for n in GRAPH_COUNTERS}
+        res["V"] = V
+
+        def take(ptr, count, dtype):
+            if count == 0 or not ptr:
+                return np.zeros(count, dtype)
+            return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True)
+
+        res["feat_id"] = take(out.feat_id, V, np.int32)
+        res["pos"] = take(out.pos, 2 * V, np.float32).reshape(V, 2)
+        res["data_term"] = take(out.data_term, V, np.float32)
+        res["data_weight"] = take(out.data_weight, V, np.float32)
+        res["feat_index"] = take(out.feat_index, V, np.int32)
+        if not raise_on_error:
+            return rc, res
+        if rc != 0:
+            raise NLTGV2Error(rc, "select_graph_features: %s (feature %d)" % (status_string(rc), res["error_feature"]))
+        return res
+
+    def get_raw_idepths(self):
+        """Flame::getRawIDepths (flame.h:255-273): (xy [n, 2], idepth_mu [n], idepth_var [n]) of the valid records of
+        the projected set.  Host code over get_projected."""
+        p = self.get_projected()
+        p = p[p["valid"] != 0]
+        return np.stack([p["x"], p["y"]], axis=1), p["idepth_mu"].copy(), p["idepth_var"].copy()
+
+    def set_graph_copy(self, mode: int):
+        """How select_graph_features copies its arrays down: 0 one block, 1 the counters first (same results)."""
+        self._chk(self._L.flame_stereo_set_option(self._ctx, OPT_GRAPH_COPY, int(mode)), "set_option")
 
     def set_lanes_per_feature(self, lanes: int):
         self._chk(self._L.flame_stereo_set_option(self._ctx, OPT_LANES_PER_FEATURE, int(lanes)), "set_option")

@@ -18,6 +18,13 @@
 //   reference  void Flame::prunePoseFrames(pfs_to_keep)  (flame.cc:554-706; on pfs_, curr_pf_, feats_, new_feats_)
 //   here       tracker.prunePoseFrames(params, &pfs_, *curr_pf_, pfs_to_keep, first_new);            // resident set
 //              tracker.prunePoseFrames(params, &pfs_, *curr_pf_, pfs_to_keep, &feats_, &new_feats_);  // host vectors
+//   reference  the preprocessing of Flame::syncGraph (flame.cc:1954-1980: which features become vertices) and the data-term
+//              lines of its vertex loops (flame.cc:2001-2004, 2041-2044)
+//   here       flame_stereo_graph_inputs g = tracker.selectGraphFeatures(params, pfs_, graph_scale_);            // resident
+//              ... = tracker.selectGraphFeatures(params, pfs_, graph_scale_, feats_, feats_in_curr_);           // vectors
+//              g.feat_id / g.pos / g.data_term / g.data_weight go into DeviceGraph::syncPrepare as they are
+//   reference  Flame::getRawIDepths(&vertices, &idepths_mu, &idepths_var)  (flame.h:255-273)
+//   here       tracker.getRawIDepths(&vertices, &idepths_mu, &idepths_var);
 //
 // Works with the reference's own types through templates (no Eigen/Sophus/OpenCV headers are needed here):
 //   Matrix3    anything with operator()(row, col)                      (Eigen::Matrix3f)
@@ -92,6 +99,18 @@ inline flame_stereo_detect_params toDetectParams(const FlameParams& p) {
   return o;
 }
 
+// flame::Params -> flame_stereo_graph_params (the members syncGraph's preprocessing reads, params.h:88-91).
+template <class FlameParams>
+inline flame_stereo_graph_params toGraphParams(const FlameParams& p) {
+  flame_stereo_graph_params o;
+  flame_stereo_default_graph_params(&o);
+  o.idepth_var_max_graph = p.idepth_var_max_graph;
+  o.min_height = p.min_height;
+  o.max_height = p.max_height;
+  o.adaptive_data_weights = p.adaptive_data_weights ? 1 : 0;
+  return o;
+}
+
 // (quaternion, translation) of an SE3 into the C arrays of a flame_stereo_pose.
 template <class SE3>
 inline void toQuatTrans(const SE3& T, float q[4], float t[3]) {
@@ -125,6 +144,11 @@ inline flame_stereo_feature* adoptFeatures(Feature* feats) {
   static_assert(offsetof(Feature, num_dropouts) == offsetof(flame_stereo_feature, num_dropouts), "num_dropouts");
   static_assert(offsetof(Feature, search_status) == offsetof(flame_stereo_feature, search_status), "search_status");
   return reinterpret_cast<flame_stereo_feature*>(feats);
+}
+
+template <class Feature>
+inline const flame_stereo_feature* adoptFeatures(const Feature* feats) {
+  return adoptFeatures(const_cast<Feature*>(feats));
 }
 
 class FeatureTracker {
@@ -237,6 +261,54 @@ class FeatureTracker {
           "flame_stereo_get_features");
   }
 
+  // ---- which features become vertices of the graph ----
+  // == the preprocessing of Flame::syncGraph (flame.cc:1954-1980) on the resident and the projected set, which must be
+  // index-aligned: call it after projectFeatures(params, pfs, fcur).  pfs: the pose-frames, whose pose (camera -> world,
+  // pfs.at(id)->pose) gives the height.  The arrays of the result belong to the tracker and stay valid until the next
+  // selectGraphFeatures; they are what DeviceGraph::sync / syncPrepare take (pointer + count forms).
+  template <class FlameParams, class FrameMap>
+  flame_stereo_graph_inputs selectGraphFeatures(const FlameParams& params, const FrameMap& pfs, float graph_scale) {
+    const std::vector<flame_stereo_world_pose> poses = worldPoses(pfs);
+    const flame_stereo_graph_params gp = toGraphParams(params);
+    flame_stereo_graph_inputs out;
+    const int rc = flame_stereo_select_graph_features(ctx_, &gp, graph_scale, (int)poses.size(),
+                                                      poses.empty() ? nullptr : poses.data(), &out);
+    check(rc, out.error_feature, "flame_stereo_select_graph_features");
+    return out;
+  }
+  // The same on the reference's two vectors (feats_, feats_in_curr_: index-aligned); neither resident set is touched.
+  template <class FlameParams, class FrameMap, class Feature>
+  flame_stereo_graph_inputs selectGraphFeatures(const FlameParams& params, const FrameMap& pfs, float graph_scale,
+                                                const std::vector<Feature>& feats, const std::vector<Feature>& feats_in_curr) {
+    if (feats.size() != feats_in_curr.size()) throw StereoError(FLAME_NLTGV2_ERR_INVALID_ARG, -1, "selectGraphFeatures");
+    const std::vector<flame_stereo_world_pose> poses = worldPoses(pfs);
+    const flame_stereo_graph_params gp = toGraphParams(params);
+    flame_stereo_graph_inputs out;
+    const int rc = flame_stereo_select_graph_features_arrays(
+        ctx_, &gp, graph_scale, (int)poses.size(), poses.empty() ? nullptr : poses.data(), (int)feats.size(),
+        feats.empty() ? nullptr : adoptFeatures(feats.data()), feats.empty() ? nullptr : adoptFeatures(feats_in_curr.data()), &out);
+    check(rc, out.error_feature, "flame_stereo_select_graph_features_arrays");
+    return out;
+  }
+  // == Flame::getRawIDepths (flame.h:255-273): the valid records of the projected set (feats_in_curr_), copied back.
+  // Point: anything with .x / .y (cv::Point2f).
+  template <class Point>
+  void getRawIDepths(std::vector<Point>* vertices, std::vector<float>* idepths_mu, std::vector<float>* idepths_var) {
+    vertices->clear(), idepths_mu->clear(), idepths_var->clear();
+    int n = 0;
+    check(flame_stereo_get_projected(ctx_, 0, nullptr, &n), -1, "flame_stereo_get_projected");
+    std::vector<flame_stereo_feature> cur((size_t)n);
+    check(flame_stereo_get_projected(ctx_, n, n ? cur.data() : nullptr, &n), -1, "flame_stereo_get_projected");
+    for (int i = 0; i < n; ++i) {
+      if (!cur[i].valid) continue;
+      Point p;
+      p.x = cur[i].x, p.y = cur[i].y;
+      vertices->push_back(p);
+      idepths_mu->push_back(cur[i].idepth_mu);
+      idepths_var->push_back(cur[i].idepth_var);
+    }
+  }
+
   // ---- prunePoseFrames ----
   // == Flame::prunePoseFrames(pfs_to_keep) on the resident set.  Does the host half of flame.cc:562-607 here: the kept
   // pose-frames are pfs_to_keep intersected with *pfs; when curr_pf is not among them nothing changes and false is
@@ -293,6 +365,19 @@ class FeatureTracker {
   flame_stereo_ctx* handle() const { return ctx_; }
 
  private:
+  // pfs.at(id)->pose of every pose-frame, as makePose forms the relative poses.
+  template <class FrameMap>
+  static std::vector<flame_stereo_world_pose> worldPoses(const FrameMap& pfs) {
+    std::vector<flame_stereo_world_pose> poses;
+    for (typename FrameMap::const_iterator it = pfs.begin(); it != pfs.end(); ++it) {
+      flame_stereo_world_pose p;
+      std::memset(&p, 0, sizeof p);
+      p.frame_id = it->first;
+      toQuatTrans(it->second->pose, p.q, p.t);
+      poses.push_back(p);
+    }
+    return poses;
+  }
   struct PrunePlan {
     uint32_t target;
     std::vector<uint32_t> keep;

@@ -250,12 +250,20 @@ class DeviceGraph {
   void sync(const std::vector<int32_t>& feat_id, const std::vector<float>& pos_xy, const std::vector<float>& data_term,
             const std::vector<float>& data_weight, const std::vector<int32_t>& edges, bool check_sticky_obstacles = false,
             const float* init_x = nullptr, float init_graph_scale = 0.0f, bool edges_unique = false) {
+    sync(static_cast<int32_t>(feat_id.size()), feat_id.data(), pos_xy.data(), data_term.data(), data_weight.data(), edges,
+         check_sticky_obstacles, init_x, init_graph_scale, edges_unique);
+  }
+  // Pointer + count form: V vertices in arrays that need not be std::vectors -- the arrays of
+  // flame_hip::FeatureTracker::selectGraphFeatures (flame_stereo_graph_inputs) go in as they are, without a copy.
+  void sync(int32_t V, const int32_t* feat_id, const float* pos_xy, const float* data_term, const float* data_weight,
+            const std::vector<int32_t>& edges, bool check_sticky_obstacles = false, const float* init_x = nullptr,
+            float init_graph_scale = 0.0f, bool edges_unique = false) {
     flame_nltgv2_sync_input in{};
     in.init_graph_scale = init_graph_scale;  // > 0: NaN entries of init_x -> neighbours' mean (flame.cc:2133-2158)
     in.edges_unique = edges_unique ? 1 : 0;  // the caller vouches (a triangulator's edge list): no search for repeated pairs
-    in.V = static_cast<int32_t>(feat_id.size());
-    in.feat_id = feat_id.data(), in.pos = pos_xy.data();
-    in.data_term = data_term.data(), in.data_weight = data_weight.data();
+    in.V = V;
+    in.feat_id = feat_id, in.pos = pos_xy;
+    in.data_term = data_term, in.data_weight = data_weight;
     in.init_x = init_x;
     in.E = static_cast<int32_t>(edges.size() / 2);
     in.edges = edges.data();
@@ -271,11 +279,18 @@ class DeviceGraph {
   void syncPrepare(const std::vector<int32_t>& feat_id, const std::vector<float>& pos_xy, const std::vector<float>& data_term,
                    const std::vector<float>& data_weight, const std::vector<int32_t>& edges, bool check_sticky_obstacles = false,
                    const float* init_x = nullptr, float init_graph_scale = 0.0f, bool edges_unique = false, bool init_from_map = false) {
+    syncPrepare(static_cast<int32_t>(feat_id.size()), feat_id.data(), pos_xy.data(), data_term.data(), data_weight.data(), edges,
+                check_sticky_obstacles, init_x, init_graph_scale, edges_unique, init_from_map);
+  }
+  // Pointer + count form (see sync): the caller's arrays are free when it returns.
+  void syncPrepare(int32_t V, const int32_t* feat_id, const float* pos_xy, const float* data_term, const float* data_weight,
+                   const std::vector<int32_t>& edges, bool check_sticky_obstacles = false, const float* init_x = nullptr,
+                   float init_graph_scale = 0.0f, bool edges_unique = false, bool init_from_map = false) {
     flame_nltgv2_sync_input in{};
     in.init_graph_scale = init_graph_scale, in.edges_unique = edges_unique ? 1 : 0, in.init_from_map = init_from_map ? 1 : 0;
-    in.V = static_cast<int32_t>(feat_id.size());
-    in.feat_id = feat_id.data(), in.pos = pos_xy.data();
-    in.data_term = data_term.data(), in.data_weight = data_weight.data();
+    in.V = V;
+    in.feat_id = feat_id, in.pos = pos_xy;
+    in.data_term = data_term, in.data_weight = data_weight;
     in.init_x = init_x;
     in.E = static_cast<int32_t>(edges.size() / 2);
     in.edges = edges.data();

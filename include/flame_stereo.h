@@ -139,7 +139,8 @@ int flame_stereo_update_feature_idepths_device(flame_stereo_ctx* ctx, const flam
                                                flame_stereo_stats* stats);
 /* The resident feature set -- the default way to run the path: the features live in device memory from detection to
  * removal (as Flame::feats_ lives in the Flame object, flame.h:529), every frame runs the update on them in place, and the
- * host reads them back only when it needs them (new detections, the data terms of the graph).
+ * host need not read them back at all: detections are appended on the device (detect_features) and the graph's vertices
+ * and data terms come down as the arrays the regulariser's sync takes (select_graph_features).
  *   set_features     replaces the resident set (host array of n_feats records);
  *   update_resident  Flame::updateFeatureIDepths on it; `stats` NULL = enqueue only (results are ordered on the stream);
  *   get_features     copies it back (feats may be NULL to query the count);
@@ -281,14 +282,102 @@ int flame_stereo_prune_features(flame_stereo_ctx* ctx, const flame_stereo_params
  * does in the reference. */
 int flame_stereo_clear_features(flame_stereo_ctx* ctx);
 
+/* ---- Which features become vertices of the graph ------------------------------------------------------------------
+ * The preprocessing of Flame::syncGraph (flame.cc:1954-1980) and the data-term lines of its two vertex loops
+ * (flame.cc:2001-2004, 2041-2044): which features become graph vertices, and with which position, data term and data
+ * weight.  The result is exactly what flame_nltgv2_sync_input takes (flame_nltgv2.h): feat_id, pos, data_term,
+ * data_weight, member for member.  The reference's loop is reproduced literally; our numpy restatement
+ * tests/select_ref.py is the checker, and like the rest of the front-end the parity with the reference binary is unpinned:
+ *   1. The predicate reads the RESIDENT record feats[i] (anchored frame): valid, idepth_var, xy, idepth_mu, frame_id.
+ *      The variance tested is the resident record's, not the projected one.
+ *   2. The outputs read the PROJECTED record feats_in_curr[i] at the same index (feat_id_to_idx, flame.cc:1998, 2032):
+ *      pos = its xy, data_term = its idepth_mu / graph_scale, data_weight = adaptive_data_weights ? 1.0f / its idepth_var
+ *      : 1.0f.  Its `valid` flag and its `id` are not read; feat_id is feats[i].id.
+ *   3. Height: pix = (x, y, 1) / idepth_mu; xyz = Kinv * pix; world = pose * xyz.  A feature is selected iff
+ *      valid && idepth_var < idepth_var_max_graph && -world.y >= min_height && -world.y <= max_height.  Only world.y is
+ *      formed.  Every comparison with a NaN is false: idepth_mu == 0 gives infinite or NaN points and plain IEEE results,
+ *      so the feature is not selected and counts under num_fail_height.
+ *   4. FLAME_ASSERT(idepth >= 0.0f) (flame.cc:1968) runs for EVERY record, valid or not: a negative or NaN idepth_mu gives
+ *      FLAME_NLTGV2_ERR_ASSERT.  pfs.at(feat.frame_id) (flame.cc:1974) also runs for every record: a frame that `poses`
+ *      does not name gives FLAME_NLTGV2_ERR_INVALID_ARG.  error_feature is the lowest index that fails either, the status
+ *      that of this record (the assert comes first within a record), as the reference's loop would stop there.  On any
+ *      error nothing is selected: V = 0 and the pointers are NULL.
+ *   5. Vertex order: the reference's is BGL hash order, unspecified; here ascending record index (a stable compaction),
+ *      like every other vertex order in this library.
+ *   6. feat.id is uint32_t, the sync's feat_id int32_t >= 0: an id >= 2^31 among the selected gives
+ *      FLAME_NLTGV2_ERR_INVALID_ARG with its index.  Duplicate ids are the caller's error and stay the sync's to reject
+ *      (in the reference feat_id_to_idx would keep the last; ids are unique by construction, feat_count_).
+ *   7. The resident form needs the resident and the projected set index-aligned, as they are right after
+ *      flame_stereo_project_features.  The context keeps a flag: project_features sets it; whatever changes membership or
+ *      order of the resident set clears it (set_features, a detect_features that appends a record, a prune that removes
+ *      a record, clear_features).  A call with the flag clear gives FLAME_NLTGV2_ERR_INVALID_ARG.  update_resident and a
+ *      prune in place between the two calls do not clear it.
+ *   8. No features: V = 0 with num_examined = 0 is a valid answer, and the pointers are NULL.
+ *   9. `do_nltgv2 == false` (flame.cc:2006-2009) and the existing-vertex loop's sticky-obstacle test are not part of
+ *      this call; the sticky-obstacle test lives in the sync (flame_nltgv2_sync_input.check_sticky_obstacles).
+ * UNPINNED arithmetic (Eigen and Sophus are not part of this tree; the same kind of statement as for the mesh outputs in
+ * flame_nltgv2.h), all in float, no FMA contraction:
+ *   pix       three true divisions by idepth_mu: x / mu, y / mu, 1 / mu.  That is Eigen >= 3.3; Eigen 3.2 multiplies by
+ *             1 / idepth_mu instead, which rounds differently.
+ *   Kinv*pix  the full 3 x 3 product, each row (a + b) + c, left to right.
+ *   rotation  row 1 of Eigen's Quaternion::toRotationMatrix() from q: tx = 2x, ty = 2y, tz = 2z; R10 = tx*y + tz*w,
+ *             R11 = 1 - (tx*x + tz*z), R12 = ty*z - tx*w.
+ *   world.y   ((R10*X + R11*Y) + R12*Z) + t[1]. */
+
+/* The members of flame::Params that syncGraph's preprocessing reads (params.h:88-91), with the reference's defaults
+ * (flame_stereo_default_graph_params). */
+typedef struct flame_stereo_graph_params {
+  float idepth_var_max_graph;    /* Params::idepth_var_max_graph   1e-2 */
+  float min_height;              /* Params::min_height             0.1  */
+  float max_height;              /* Params::max_height             4    */
+  int32_t adaptive_data_weights; /* Params::adaptive_data_weights  0    */
+} flame_stereo_graph_params;
+void flame_stereo_default_graph_params(flame_stereo_graph_params* p);
+
+/* pf.pose of one pose-frame (camera -> world, what pfs.at(id)->pose holds).  q = (w, x, y, z). */
+typedef struct flame_stereo_world_pose {
+  uint32_t frame_id;
+  float q[4], t[3];
+} flame_stereo_world_pose;
+
+/* The arrays are pinned host memory of the context: valid until the next call of either select function or until
+ * destroy.  The first four map one to one onto flame_nltgv2_sync_input. */
+typedef struct flame_stereo_graph_inputs {
+  int32_t V;                 /* selected features = vertices of the frame's graph */
+  const int32_t* feat_id;    /* [V]   -> flame_nltgv2_sync_input.feat_id      feats[i].id */
+  const float* pos;          /* [2V]  -> .pos          feats_in_curr[i].xy */
+  const float* data_term;    /* [V]   -> .data_term    feats_in_curr[i].idepth_mu / graph_scale */
+  const float* data_weight;  /* [V]   -> .data_weight  adaptive ? 1.0f / feats_in_curr[i].idepth_var : 1.0f */
+  const int32_t* feat_index; /* [V]   index i of the record in the resident / projected set, ascending */
+  int32_t num_examined;      /* records looked at */
+  int32_t num_invalid;       /* the first failing test, in this order: !valid, */
+  int32_t num_fail_var;      /*   idepth_var >= idepth_var_max_graph, */
+  int32_t num_fail_height;   /*   outside the height band or not finite; the three sum to num_examined - V */
+  int32_t error_feature;     /* -1, or the lowest index that hit the reference's assert / names an unknown frame / has
+                                an id >= 2^31 */
+} flame_stereo_graph_inputs;
+
+/* On the resident and the projected set (point 7).  Reads both, changes neither.  Enqueues on the context's stream and
+ * waits once. */
+int flame_stereo_select_graph_features(flame_stereo_ctx* ctx, const flame_stereo_graph_params* gp, float graph_scale,
+                                       int n_poses, const flame_stereo_world_pose* poses, flame_stereo_graph_inputs* out);
+/* The same on two index-aligned host arrays (feats_, feats_in_curr_; n_feats records each), as flame_stereo_prune_features
+ * is to flame_stereo_prune_pose_frames: uploads them, runs the same kernels, touches neither resident set nor the flag. */
+int flame_stereo_select_graph_features_arrays(flame_stereo_ctx* ctx, const flame_stereo_graph_params* gp, float graph_scale,
+                                              int n_poses, const flame_stereo_world_pose* poses, int n_feats,
+                                              const flame_stereo_feature* feats, const flame_stereo_feature* feats_in_curr,
+                                              flame_stereo_graph_inputs* out);
+
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
- * bit for bit. */
-enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1 };
+ * bit for bit.  GRAPH_COPY: how select_graph_features brings its arrays down: 0 (default) the whole output block in one
+ * copy and one wait, its sections spaced by the record count; 1 the counters first, then 24 bytes per selected vertex
+ * (two waits); same results (profiles/graph_inputs.txt has both timings). */
+enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1, FLAME_STEREO_OPT_GRAPH_COPY = 2 };
 int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value);
 
 /* Device time of the last update kernel (or of the kernels of the last project_features / detect_features /
- * prune_pose_frames / prune_features) in
+ * prune_pose_frames / prune_features / select_graph_features[_arrays]) in
  * milliseconds (HIP events on the context's stream); < 0 if none. */
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx);
 int flame_stereo_last_hip_error(const flame_stereo_ctx* ctx);
