@@ -8,6 +8,7 @@ Layout:
 There is no CPU fallback in this package: without the HIP library / a GPU every compute call raises.
 """
 from .regularizer import (  # noqa: F401
+    DebugImageParams,
     MeshFilterParams,
     NLTGV2Error,
     Params,

@@ -520,6 +520,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   ok = ok && hipEventCreateWithFlags(&ctx->ev_raster_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_topo_ready, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreate(&ctx->ev_mesh0) == hipSuccess && hipEventCreate(&ctx->ev_mesh1) == hipSuccess;
+  ok = ok && hipEventCreate(&ctx->ev_dbg0) == hipSuccess && hipEventCreate(&ctx->ev_dbg1) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_expanded, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[0], hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[1], hipEventDisableTiming) == hipSuccess;
@@ -567,6 +568,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   for (DevBuf* b : {&ctx->m_P, &ctx->m_idepth, &ctx->m_normals, &ctx->m_tvalid, &ctx->m_nvalid, &ctx->m_tnormal, &ctx->m_offset, &ctx->m_cursor,
                     &ctx->m_incident, &ctx->m_keys, &ctx->m_img, &ctx->m_cov})
     ctx->all.push_back(b);
+  for (DevBuf* b : {&ctx->d_gray, &ctx->d_idimg, &ctx->d_nimg, &ctx->d_w1map, &ctx->d_w2map, &ctx->d_keys, &ctx->d_cov}) ctx->all.push_back(b);
   ctx->all.push_back(&ctx->stop_dev);
   ctx->all.push_back(&ctx->place_patch_nx), ctx->all.push_back(&ctx->place_fill_nx);
   for (auto& b : ctx->sp_v) ctx->all.push_back(&b);
@@ -605,6 +607,9 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
   if (ctx->h_mesh) (void)hipHostFree(ctx->h_mesh);
   if (ctx->ev_mesh0) (void)hipEventDestroy(ctx->ev_mesh0);
   if (ctx->ev_mesh1) (void)hipEventDestroy(ctx->ev_mesh1);
+  if (ctx->h_dbg) (void)hipHostFree(ctx->h_dbg);
+  if (ctx->ev_dbg0) (void)hipEventDestroy(ctx->ev_dbg0);
+  if (ctx->ev_dbg1) (void)hipEventDestroy(ctx->ev_dbg1);
   if (ctx->h_dims) (void)hipHostFree(ctx->h_dims);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

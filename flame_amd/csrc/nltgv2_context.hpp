@@ -322,6 +322,21 @@ struct flame_nltgv2_ctx {
     size_t off_idepth = 0, off_counts = 0, off_map = 0, off_valid = 0;  // byte offsets in h_mesh (normals at 0)
   } mesh_pending;
   hipEvent_t ev_mesh0 = nullptr, ev_mesh1 = nullptr;  // timing events around the stage on the side stream
+  // flame_nltgv2_debug_images_begin / _end (debug_kernels.hip): r_keys is the key image of the resident map; it names the winning
+  // triangles of an all-valid rasterisation of r_tris exactly when keys_gen == tris_gen (tris_gen counts the uploads into r_tris,
+  // keys_gen is the count the last rasterisation of the graph's map saw, 0 where it had a validity mask or was another image's).
+  // Buffers, pinned outputs and timing events of its own: the resident map, h_img, h_mesh and r_keys are only read.
+  uint64_t tris_gen = 0, keys_gen = 0;
+  DevBuf d_gray, d_idimg, d_nimg, d_w1map, d_w2map, d_keys, d_cov;
+  char* h_dbg = nullptr;              // pinned: idepth image | normals image | w1 map | w2 map | staging of a host grey image
+  size_t h_dbg_cap = 0;
+  struct DebugPending {
+    bool active = false;
+    int rows = 0, cols = 0;
+    bool want_idepth = false, want_normals = false;
+    size_t off_nimg = 0, off_w1 = 0, off_w2 = 0, off_gray = 0;  // byte offsets in h_dbg (idepth image at 0)
+  } debug_pending;
+  hipEvent_t ev_dbg0 = nullptr, ev_dbg1 = nullptr;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

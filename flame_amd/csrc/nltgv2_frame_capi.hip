@@ -3,6 +3,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include "debug_kernels.h"
 #include "mesh_kernels.h"
 #include "nltgv2_context.hpp"
 
@@ -39,6 +40,7 @@ static int interpolate_common(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
   if (!rc) rc = ensure(ctx, ctx->r_cov, sizeof(int));
   if (rc) return rc;
   if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, ctx->stream));
+  ctx->tris_gen++, ctx->keys_gen = (tri_valid || vtx_valid) ? 0 : ctx->tris_gen;  // (r_keys: see flame_nltgv2_debug_images_begin)
   uint8_t* d_tv = nullptr;
   uint8_t* d_vv = nullptr;
   if (tri_valid && T > 0) {
@@ -97,6 +99,7 @@ int flame_nltgv2_interpolate_mesh_begin(flame_nltgv2_ctx* ctx, const int32_t* tr
   if (!rc) rc = ensure(ctx, ctx->r_cov, sizeof(int));
   if (rc) return rc;
   if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
+  ctx->tris_gen++, ctx->keys_gen = tri_valid ? 0 : ctx->tris_gen;  // (r_keys: see flame_nltgv2_debug_images_begin)
   uint8_t* d_tv = nullptr;
   if (tri_valid && T > 0) {
     d_tv = (uint8_t*)ctx->r_tvalid.p;
@@ -273,6 +276,7 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
   if (triangles) {
     if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
     ctx->tris_T = T, ctx->tris_topo = ctx->topo;
+    ctx->tris_gen++;  // (r_keys no longer speaks of r_tris)
   }
   flame_hip::MeshFilter mf;
   std::memcpy(mf.Kinv, Kinv, sizeof(mf.Kinv));
@@ -353,6 +357,139 @@ int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
   if (n_valid_out) *n_valid_out = v.n_valid;
   if (filtered_map_out) std::memcpy(filtered_map_out, v.filtered_map, sizeof(float) * (size_t)v.rows * (size_t)v.cols);
   if (filtered_coverage_out) *filtered_coverage_out = v.filtered_coverage;
+  return FLAME_NLTGV2_OK;
+}
+
+void flame_nltgv2_default_debug_image_params(flame_nltgv2_debug_image_params* p) {
+  if (!p) return;
+  p->scene_color_scale = 1.0f;  // params.h:109
+  p->flip = 0;
+  p->want_idepthmap = 1;
+  p->want_normals = 1;
+}
+
+// The debug images on the side stream (see flame_nltgv2.h).  Like mesh_outputs_begin: everything is checked before the stream or a
+// buffer is touched, so an error leaves what an earlier begin put into the pinned outputs, and its pending _end, as they are.
+int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
+                                    const float* K, const flame_nltgv2_debug_image_params* params, int rows, int cols) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_debug_images_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  if (rows <= 0 || cols <= 0 || ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (ctx->tris_T < 0 || ctx->tris_topo != ctx->topo) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if ((img_host != nullptr) == (img_device != nullptr) || step_bytes < cols || !K || !params) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t T = ctx->tris_T;
+  const size_t n = (size_t)rows * (size_t)cols;
+  const bool want_id = params->want_idepthmap != 0, want_n = params->want_normals != 0;
+  hipStream_t rs = ctx->raster_stream;
+  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned outputs and the device buffers are about to be reused)
+  // pinned: idepth image | normals image | w1 map | w2 map | the grey image on its way up
+  flame_nltgv2_ctx::DebugPending dp;
+  auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+  dp.rows = rows, dp.cols = cols, dp.want_idepth = want_id, dp.want_normals = want_n;
+  dp.off_nimg = up16(want_id ? 3 * n : 0);
+  dp.off_w1 = dp.off_nimg + up16(want_n ? 3 * n : 0);
+  dp.off_w2 = dp.off_w1 + up16(want_n ? sizeof(float) * n : 0);
+  dp.off_gray = dp.off_w2 + up16(want_n ? sizeof(float) * n : 0);
+  const size_t h_bytes = dp.off_gray + up16(img_host ? n : 0) + 16;
+  if (ctx->h_dbg_cap < h_bytes) {
+    request_open_stop(ctx);  // (the pinned allocator waits for the device)
+    void* h = nullptr;
+    if (hipHostMalloc(&h, h_bytes + h_bytes / 2, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
+    }
+    if (ctx->h_dbg) (void)hipHostFree(ctx->h_dbg);
+    ctx->h_dbg = (char*)h, ctx->h_dbg_cap = h_bytes + h_bytes / 2;
+    ctx->debug_pending.active = false;
+  }
+  const bool from_keys = ctx->keys_gen != 0 && ctx->keys_gen == ctx->tris_gen;
+  if (img_host) rc = ensure(ctx, ctx->d_gray, n + 16);
+  if (!rc && want_id) rc = ensure(ctx, ctx->d_idimg, 3 * n + 16);
+  if (!rc && want_n) {
+    rc = ensure(ctx, ctx->d_nimg, 3 * n + 16);
+    if (!rc) rc = ensure(ctx, ctx->d_w1map, sizeof(float) * n);
+    if (!rc) rc = ensure(ctx, ctx->d_w2map, sizeof(float) * n);
+    if (!rc && !from_keys) rc = ensure(ctx, ctx->d_keys, sizeof(unsigned long long) * n);
+    if (!rc && !from_keys) rc = ensure(ctx, ctx->d_cov, sizeof(int));
+  }
+  if (rc) return rc;
+  ctx->debug_pending.active = false;  // (from here on the pinned outputs are being rewritten)
+  char* h = ctx->h_dbg;
+  flame_hip::DebugImageArgs a;
+  a.rows = rows, a.cols = cols;
+  a.gray = (const uint8_t*)img_device, a.gray_step = step_bytes;
+  a.scene_color_scale = params->scene_color_scale, a.flip = params->flip != 0;
+  a.k00 = K[0], a.k11 = K[4];
+  if (img_host) {  // through pinned memory, rows packed: the caller's buffer is free again when this returns
+    for (int r = 0; r < rows; ++r) std::memcpy(h + dp.off_gray + (size_t)r * cols, img_host + (size_t)r * step_bytes, (size_t)cols);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_gray.p, h + dp.off_gray, n, hipMemcpyHostToDevice, rs));
+    a.gray = (const uint8_t*)ctx->d_gray.p, a.gray_step = cols;
+  }
+  if (want_n) {  // (w1 / w2 of the state mesh_state_on selects; the idepth image needs the resident map alone)
+    rc = mesh_state_on(ctx, rs);
+    if (rc) return rc;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev_dbg0, rs));
+  if (want_n) {
+    if (from_keys) {
+      LAUNCHCHK(ctx, flame_hip::launch_debug_wmaps((const unsigned long long*)ctx->r_keys.p, (const int32_t*)ctx->r_tris.p, ctx->c.pos,
+                                                   ctx->c.w1, ctx->c.w2, (float*)ctx->d_w1map.p, (float*)ctx->d_w2map.p, rows, cols, rs));
+    } else {  // the resident map was rasterised with a validity mask: the rasteriser itself, twice, into buffers of this stage
+      LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.w1, 1.0f, nullptr, nullptr,
+                                             (unsigned long long*)ctx->d_keys.p, (float*)ctx->d_w1map.p, (int*)ctx->d_cov.p, rows, cols, rs));
+      LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.w2, 1.0f, nullptr, nullptr,
+                                             (unsigned long long*)ctx->d_keys.p, (float*)ctx->d_w2map.p, (int*)ctx->d_cov.p, rows, cols, rs));
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_raster_done, rs));  // (the last readers of the canonical pos / w1 / w2: see interpolate_mesh_begin)
+    ctx->raster_inflight = true;
+  }
+  LAUNCHCHK(ctx, flame_hip::launch_debug_images(a, (const float*)ctx->r_img.p, (const float*)ctx->d_w1map.p, (const float*)ctx->d_w2map.p,
+                                                want_id ? (uint8_t*)ctx->d_idimg.p : nullptr, want_n ? (uint8_t*)ctx->d_nimg.p : nullptr, rs));
+  if (want_id) HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_idimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
+  if (want_n) {
+    HIPCHK(ctx, hipMemcpyAsync(h + dp.off_nimg, ctx->d_nimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + dp.off_w1, ctx->d_w1map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + dp.off_w2, ctx->d_w2map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev_dbg1, rs));
+  dp.active = true;
+  ctx->debug_pending = dp;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_debug_images_end(flame_nltgv2_ctx* ctx, flame_nltgv2_debug_images_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_debug_images_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::DebugPending& dp = ctx->debug_pending;
+  if (!out || !ctx->h_dbg || !dp.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  const char* h = ctx->h_dbg;
+  out->rows = dp.rows, out->cols = dp.cols;
+  out->idepthmap_img = dp.want_idepth ? (const uint8_t*)h : nullptr;
+  out->normals_img = dp.want_normals ? (const uint8_t*)(h + dp.off_nimg) : nullptr;
+  out->w1_map = dp.want_normals ? (const float*)(h + dp.off_w1) : nullptr;
+  out->w2_map = dp.want_normals ? (const float*)(h + dp.off_w2) : nullptr;
+  out->device_ms = 0.0f;
+  if (hipEventElapsedTime(&out->device_ms, ctx->ev_dbg0, ctx->ev_dbg1) != hipSuccess) (void)hipGetLastError(), out->device_ms = 0.0f;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_debug_images(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes, const float* K,
+                              const flame_nltgv2_debug_image_params* params, int rows, int cols, uint8_t* idepthmap_img_out,
+                              uint8_t* normals_img_out, float* w1_map_out, float* w2_map_out) {
+  int rc = flame_nltgv2_debug_images_begin(ctx, img_host, img_device, step_bytes, K, params, rows, cols);
+  if (rc) return rc;
+  flame_nltgv2_debug_images_view v;
+  rc = flame_nltgv2_debug_images_end(ctx, &v);
+  if (rc) return rc;
+  const size_t n = (size_t)v.rows * (size_t)v.cols;
+  if (idepthmap_img_out && v.idepthmap_img) std::memcpy(idepthmap_img_out, v.idepthmap_img, 3 * n);
+  if (normals_img_out && v.normals_img) std::memcpy(normals_img_out, v.normals_img, 3 * n);
+  if (w1_map_out && v.w1_map) std::memcpy(w1_map_out, v.w1_map, sizeof(float) * n);
+  if (w2_map_out && v.w2_map) std::memcpy(w2_map_out, v.w2_map, sizeof(float) * n);
   return FLAME_NLTGV2_OK;
 }
 

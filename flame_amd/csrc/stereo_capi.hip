@@ -15,6 +15,7 @@
 #include "flame_stereo.h"
 #include "stereo_kernels.h"
 #include "feature_kernels.h"
+#include "debug_kernels.h"
 #include "roctx_ranges.hpp"
 
 using namespace flame_hip;
@@ -93,6 +94,11 @@ struct flame_stereo_ctx {
   int* h_sel = nullptr;  // pinned, the same
   size_t h_sel_cap = 0;
   int graph_copy = 0;  // FLAME_STEREO_OPT_GRAPH_COPY
+  // draw_features (debug_kernels.hip): per-pixel owner words + the two counters behind them, and the image
+  uint32_t* d_owner = nullptr;
+  size_t owner_cap = 0;
+  uint8_t* d_draw = nullptr;
+  size_t draw_cap = 0;
 };
 
 namespace {
@@ -485,7 +491,7 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   if (ctx->d_res) (void)hipFree(ctx->d_res);
   for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
                   (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_keep_ids, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
-                  (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel})
+                  (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel, (void*)ctx->d_owner, (void*)ctx->d_draw})
     if (p) (void)hipFree(p);
   if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
   if (ctx->h_sel) (void)hipHostFree(ctx->h_sel);
@@ -749,6 +755,51 @@ int flame_stereo_projected_device(flame_stereo_ctx* ctx, void** feats_device, in
   if (!ctx) return FLAME_NLTGV2_ERR_INVALID_ARG;
   if (feats_device) *feats_device = ctx->d_proj;
   if (n_feats) *n_feats = ctx->n_proj;
+  return 0;
+}
+
+int flame_stereo_frame_image_device(flame_stereo_ctx* ctx, uint32_t frame_id, const void** img, int* step_bytes) {
+  if (!ctx || !img || !step_bytes || !ctx->have_camera) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  auto it = ctx->frames.find(frame_id);
+  if (it == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int pitch = ctx->cam.width + 2 * ctx->cam.border;
+  *img = it->second.img_pad + (size_t)ctx->cam.border * pitch + ctx->cam.border;
+  *step_bytes = pitch;
+  return 0;
+}
+
+int flame_stereo_draw_features(flame_stereo_ctx* ctx, uint32_t cur_frame_id, float idepth_var_max_graph,
+                               float scene_color_scale, int flip, uint8_t* img_out, int32_t* num_converged,
+                               int32_t* num_unconverged) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_draw_features");
+  if (int rc = enter(ctx)) return rc;
+  if (!img_out) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  auto fr = ctx->frames.find(cur_frame_id);
+  if (fr == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int width = ctx->cam.width, height = ctx->cam.height, pitch = width + 2 * ctx->cam.border;
+  const size_t px = (size_t)width * height;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated)
+  if (int rc = grow(ctx, &ctx->d_owner, &ctx->owner_cap, px + 2)) return rc;
+  if (int rc = grow(ctx, &ctx->d_draw, &ctx->draw_cap, 3 * px + 16)) return rc;
+  DebugImageArgs a;
+  a.rows = height, a.cols = width;
+  a.gray = fr->second.img_pad + (size_t)ctx->cam.border * pitch + ctx->cam.border, a.gray_step = pitch;
+  a.scene_color_scale = scene_color_scale, a.flip = flip != 0;
+  a.k00 = a.k11 = 0.0f;
+  int* d_counts = (int*)(ctx->d_owner + px);
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, (hipError_t)launch_draw_features(a, ctx->n_proj, ctx->n_proj > 0 ? (const void*)&ctx->d_proj->x : nullptr,
+                                             (int)sizeof(StereoFeature), idepth_var_max_graph, ctx->d_owner, d_counts, ctx->d_draw,
+                                             ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  int counts[2] = {0, 0};
+  SCHK(ctx, hipMemcpyAsync(img_out, ctx->d_draw, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (num_converged) *num_converged = counts[0];
+  if (num_unconverged) *num_unconverged = counts[1];
   return 0;
 }
 

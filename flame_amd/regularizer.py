@@ -80,6 +80,21 @@ class _MeshOutputsView(C.Structure):
                 ("filtered_coverage", C.c_int32), ("device_ms", C.c_float)]
 
 
+class DebugImageParams(C.Structure):
+    """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
+    drawInverseDepthMap / drawNormals are wanted."""
+
+    _fields_ = [("scene_color_scale", C.c_float), ("flip", C.c_int32), ("want_idepthmap", C.c_int32), ("want_normals", C.c_int32)]
+
+    def __init__(self, scene_color_scale=1.0, flip=False, want_idepthmap=True, want_normals=True):
+        super().__init__(scene_color_scale, int(bool(flip)), int(bool(want_idepthmap)), int(bool(want_normals)))
+
+
+class _DebugImagesView(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("idepthmap_img", C.POINTER(C.c_uint8)), ("normals_img", C.POINTER(C.c_uint8)),
+                ("w1_map", _FP), ("w2_map", _FP), ("device_ms", C.c_float)]
+
+
 class _Graph(C.Structure):
     _fields_ = (
         [("V", C.c_int32), ("E", C.c_int32), ("pos", _FP)]
@@ -137,6 +152,8 @@ ABI_SYMBOLS = (
     "flame_delaunay_triangulate",
     "flame_nltgv2_default_mesh_filter_params", "flame_nltgv2_oblique_cos_bound", "flame_nltgv2_mesh_outputs_begin",
     "flame_nltgv2_mesh_outputs_end", "flame_nltgv2_mesh_outputs",
+    "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
+    "flame_nltgv2_debug_images",
 )
 
 
@@ -214,6 +231,12 @@ def load_library():
         "flame_nltgv2_mesh_outputs_end": (C.c_int, [ctx, C.POINTER(_MeshOutputsView)]),
         "flame_nltgv2_mesh_outputs": (C.c_int, [ctx, _IP, C.c_int32, _FP, C.POINTER(MeshFilterParams), C.c_int, C.c_int, C.c_float,
                                                 C.POINTER(C.c_uint8), _FP, _FP, _IP, _FP, _IP]),
+        "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
+        "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
+                                                      C.c_int]),
+        "flame_nltgv2_debug_images_end": (C.c_int, [ctx, C.POINTER(_DebugImagesView)]),
+        "flame_nltgv2_debug_images": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int, C.c_int,
+                                                C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _FP, _FP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -574,6 +597,43 @@ class Regularizer:
         """mesh_outputs_begin; mesh_outputs_end."""
         self.mesh_outputs_begin(triangles, Kinv, rows, cols, graph_scale, filter, want_filtered_map)
         return self.mesh_outputs_end()
+
+    # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
+    def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):
+        """Enqueues drawInverseDepthMap / the w1, w2 maps / drawNormals over the resident map of the last interpolate_mesh[_begin] on
+        the side stream and returns.  The grey image: `img`, a (rows, cols) u8 array whose rows are contiguous (a view with a larger
+        row stride is passed as it is), or img=None and img_device = a device address with step_bytes (e.g.
+        FeatureTracker.frame_image_device)."""
+        k = np.ascontiguousarray(K, np.float32).reshape(9)
+        p = params if params is not None else DebugImageParams()
+        if img is not None:
+            if not (isinstance(img, np.ndarray) and _rows_contiguous_u8(img) and img.shape == (rows, cols)):
+                img = np.ascontiguousarray(img, np.uint8).reshape(rows, cols)
+            host, dev, step = C.c_void_p(img.ctypes.data), None, int(img.strides[0]) if step_bytes is None else int(step_bytes)
+        else:
+            host, dev, step = None, (C.c_void_p(int(img_device)) if img_device else None), int(step_bytes if step_bytes is not None else cols)
+        self._chk(self._L.flame_nltgv2_debug_images_begin(self._ctx, host, dev, step, k.ctypes.data_as(_FP), C.byref(p), rows, cols),
+                  "debug_images_begin")
+
+    def debug_images_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(device_ms and, as asked for, idepthmap_img (rows,cols,3) u8, normals_img (rows,cols,3) u8,
+        w1_map, w2_map (rows,cols) f32).  copy=False: views of the context's pinned memory, valid until the next begin."""
+        v = _DebugImagesView()
+        self._chk(self._L.flame_nltgv2_debug_images_end(self._ctx, C.byref(v)), "debug_images_end")
+        take = (lambda a: a.copy()) if copy else (lambda a: a)
+        out = dict(device_ms=float(v.device_ms))
+        if v.idepthmap_img:
+            out["idepthmap_img"] = take(np.ctypeslib.as_array(v.idepthmap_img, shape=(v.rows, v.cols, 3)))
+        if v.normals_img:
+            out["normals_img"] = take(np.ctypeslib.as_array(v.normals_img, shape=(v.rows, v.cols, 3)))
+            out["w1_map"] = take(np.ctypeslib.as_array(v.w1_map, shape=(v.rows, v.cols)))
+            out["w2_map"] = take(np.ctypeslib.as_array(v.w2_map, shape=(v.rows, v.cols)))
+        return out
+
+    def debug_images(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None) -> dict:
+        """debug_images_begin; debug_images_end."""
+        self.debug_images_begin(img, K, rows, cols, params, img_device, step_bytes)
+        return self.debug_images_end()
 
     def interpolate_mesh_arrays(self, triangles, vertices, values, rows, cols, vtx_valid=None, tri_valid=None):
         tr = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)

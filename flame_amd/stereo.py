@@ -116,6 +116,7 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_projected_device", "flame_stereo_detect_features", "flame_stereo_prune_pose_frames",
     "flame_stereo_prune_features", "flame_stereo_clear_features", "flame_stereo_default_graph_params",
     "flame_stereo_select_graph_features", "flame_stereo_select_graph_features_arrays",
+    "flame_stereo_draw_features", "flame_stereo_frame_image_device",
 )
 OPT_LANES_PER_FEATURE = 1
 OPT_GRAPH_COPY = 2
@@ -172,6 +173,9 @@ def _lib():
             "flame_stereo_select_graph_features_arrays": (C.c_int, [ctx, C.POINTER(GraphParams), C.c_float, C.c_int,
                                                                     C.POINTER(_WorldPose), C.c_int, C.c_void_p, C.c_void_p,
                                                                     C.POINTER(_GraphInputs)]),
+            "flame_stereo_draw_features": (C.c_int, [ctx, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+            "flame_stereo_frame_image_device": (C.c_int, [ctx, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -333,6 +337,23 @@ class FeatureTracker:
         p, n = C.c_void_p(), C.c_int(0)
         self._chk(self._L.flame_stereo_projected_device(self._ctx, C.byref(p), C.byref(n)), "projected_device")
         return p.value or 0, n.value
+
+    def draw_features(self, cur_frame_id: int, idepth_var_max_graph: float, scene_color_scale: float = 1.0, flip: bool = False):
+        """Flame::drawFeatures (flame.cc:2459-2510) on the projected set of the last project_features over resident frame
+        `cur_frame_id`.  Returns (img (height, width, 3) u8, num_converged, num_unconverged)."""
+        img = np.empty((self.height, self.width, 3), np.uint8)
+        nc, nu = C.c_int32(0), C.c_int32(0)
+        self._chk(self._L.flame_stereo_draw_features(self._ctx, cur_frame_id, C.c_float(idepth_var_max_graph),
+                                                     C.c_float(scene_color_scale), int(bool(flip)), img.ctypes.data, C.byref(nc),
+                                                     C.byref(nu)), "draw_features")
+        return img, int(nc.value), int(nu.value)
+
+    def frame_image_device(self, frame_id: int):
+        """(device address, step_bytes) of the unpadded image of a resident frame: Regularizer.debug_images(None, ...,
+        img_device=, step_bytes=).  Valid until the frame is dropped or replaced."""
+        p, step = C.c_void_p(), C.c_int(0)
+        self._chk(self._L.flame_stereo_frame_image_device(self._ctx, frame_id, C.byref(p), C.byref(step)), "frame_image_device")
+        return p.value or 0, int(step.value)
 
     def detect_features(self, params: StereoParams, dparams: DetectParams, ref_frame_id: int, q_ref_to_prev,
                         t_ref_to_prev, idepthmap=None, mask_xy=None, first_id: int = 0, raise_on_error: bool = True):

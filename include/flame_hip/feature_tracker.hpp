@@ -261,6 +261,33 @@ class FeatureTracker {
           "flame_stereo_get_features");
   }
 
+  // ---- getDebugImageFeatures ----
+  // == Flame::drawFeatures(params, fnew_->img[0], feats_in_curr_, &stats_, &debug_img_features_) (flame.cc:2459-2510, call site
+  // flame.cc:292-295) on the projected set of the last projectFeatures over the resident frame `fcur_id`; the image never
+  // comes down and goes up again.  debug_img: height * width * 3 bytes (cv::Vec3b, c[0], c[1], c[2]).  The text overlay
+  // (debug_draw_text_overlay) is not drawn; its two counters are returned instead.
+  void drawFeatures(uint32_t fcur_id, float idepth_var_max_graph, float scene_color_scale, bool debug_flip_images,
+                    uint8_t* debug_img, int* num_converged = nullptr, int* num_unconverged = nullptr) {
+    int32_t nc = 0, nu = 0;
+    check(flame_stereo_draw_features(ctx_, fcur_id, idepth_var_max_graph, scene_color_scale, debug_flip_images ? 1 : 0, debug_img,
+                                     &nc, &nu), -1, "flame_stereo_draw_features");
+    if (num_converged) *num_converged = nc;
+    if (num_unconverged) *num_unconverged = nu;
+  }
+  template <class FlameParams>
+  void drawFeatures(const FlameParams& params, uint32_t fcur_id, uint8_t* debug_img, int* num_converged = nullptr,
+                    int* num_unconverged = nullptr) {
+    drawFeatures(fcur_id, params.idepth_var_max_graph, params.scene_color_scale, params.debug_flip_images, debug_img,
+                 num_converged, num_unconverged);
+  }
+  // fnew_->img[0] of a resident frame in device memory (address, pitch): what DeviceGraph::debugImagesBegin takes as
+  // img_device.  Valid until the frame is dropped or replaced.
+  const void* frameImageDevice(uint32_t frame_id, int* step_bytes) {
+    const void* img = nullptr;
+    check(flame_stereo_frame_image_device(ctx_, frame_id, &img, step_bytes), -1, "flame_stereo_frame_image_device");
+    return img;
+  }
+
   // ---- which features become vertices of the graph ----
   // == the preprocessing of Flame::syncGraph (flame.cc:1954-1980) on the resident and the projected set, which must be
   // index-aligned: call it after projectFeatures(params, pfs, fcur).  pfs: the pose-frames, whose pose (camera -> world,

@@ -202,6 +202,27 @@ struct MeshOutputs {
   int filtered_coverage = 0;
 };
 
+// == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
+// layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
+struct DebugImageParams {
+  float scene_color_scale = 1.0f;
+  int32_t debug_flip_images = 0;
+  int32_t debug_draw_idepthmap = 1;
+  int32_t debug_draw_normals = 1;
+};
+static_assert(sizeof(DebugImageParams) == sizeof(flame_nltgv2_debug_image_params), "DebugImageParams must mirror the C-ABI struct");
+
+// What the "Draw stuff" block of Flame::update() (flame.cc:490-511) leaves for getDebugImageInverseDepthMap / getDebugImageNormals
+// (flame.h:294-306), under the reference's member names.  Pointers into pinned memory of the DeviceGraph, valid until its next
+// debugImagesBegin(); a picture that was not asked for is nullptr.  Pixels are cv::Vec3b: 3 bytes, c[0], c[1], c[2].
+struct DebugImages {
+  int rows = 0, cols = 0;
+  const uint8_t* debug_img_idepthmap = nullptr;  // [rows * cols * 3]
+  const uint8_t* debug_img_normals = nullptr;    // [rows * cols * 3]
+  const float* w1_map = nullptr;                 // [rows * cols] w1_map_, NaN where uncovered (with the normals only)
+  const float* w2_map = nullptr;                 // [rows * cols] w2_map_
+};
+
 // Device image of ONE Graph: what the pipeline keeps next to `Graph graph_` (flame.h:536).  Not
 // thread-safe -- hold graph_mtx_ (flame.h:539) around every call exactly as the reference does around
 // step() and the graph edits (flame.cc:103, 302, 309, 329, 365).
@@ -330,6 +351,30 @@ class DeviceGraph {
     m.num_valid_triangles = v.n_valid;
     m.rows = v.rows, m.cols = v.cols, m.filtered_idepthmap = v.filtered_map, m.filtered_coverage = v.filtered_coverage;
     return m;
+  }
+
+  // drawInverseDepthMap (flame.cc:2699-2719) and interpolateMesh(w1), interpolateMesh(w2), drawNormals (flame.cc:497-506, 2667-2697) over
+  // the dense map, the triangles and the state the last interpolateMesh[Begin] left on the device, on the side stream
+  // (flame_nltgv2_debug_images_begin / _end).  The grey image fnew_->img[0] (rows of cols bytes, step_bytes apart): in host memory
+  // (img_host) or in device memory (img_device, e.g. FeatureTracker::frameImageDevice: nothing is uploaded) -- exactly one of the two.
+  void debugImagesBegin(const uint8_t* img_host, const void* img_device, int step_bytes, const float K[9], const DebugImageParams& params,
+                        int rows, int cols) {
+    flame_nltgv2_debug_image_params c;
+    std::memcpy(&c, &params, sizeof(c));
+    check(flame_nltgv2_debug_images_begin(ctx_, img_host, img_device, step_bytes, K, &c, rows, cols), "debug_images_begin");
+  }
+  DebugImages debugImagesEnd() {
+    flame_nltgv2_debug_images_view v;
+    check(flame_nltgv2_debug_images_end(ctx_, &v), "debug_images_end");
+    DebugImages d;
+    d.rows = v.rows, d.cols = v.cols;
+    d.debug_img_idepthmap = v.idepthmap_img, d.debug_img_normals = v.normals_img, d.w1_map = v.w1_map, d.w2_map = v.w2_map;
+    return d;
+  }
+  DebugImages debugImages(const uint8_t* img_host, const void* img_device, int step_bytes, const float K[9], const DebugImageParams& params,
+                          int rows, int cols) {
+    debugImagesBegin(img_host, img_device, step_bytes, K, params, rows, cols);
+    return debugImagesEnd();
   }
 
   // utils::interpolateMesh (utils/image_utils.cc:373-396) at its call site flame.cc:409-415: rasterises

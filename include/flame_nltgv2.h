@@ -349,6 +349,72 @@ int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
                               uint8_t* tri_valid_out, float* normals_out, float* vtx_idepth_out, int32_t* n_valid_out,
                               float* filtered_map_out, int32_t* filtered_coverage_out);
 
+/* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
+ * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
+ * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
+ * flame_stereo.h.)  Every byte is meant to equal the reference's; tests/debug_ref.py restates the operations and is the checker.
+ *
+ * NOT covered, on purpose:
+ *   drawWireframe      blends cv::LineIterator pixels sequentially, in triangle order: a pixel's value depends on every earlier draw
+ *                      that touched it.  On the device that needs a per-pixel ordered list and a restated OpenCV line walk.
+ *   cv::putText        debug_draw_text_overlay is treated as false.
+ *   drawDetections, debug_draw_matches, debug_draw_photo_error   feed on commented-out code in the reference.
+ *
+ * Pixel bytes are the reference's cv::Vec3b c[0], c[1], c[2] in that order; cvtColor(GRAY2RGB) is three equal bytes.
+ *   idepth image   drawInverseDepthMap, flame.cc:2699-2719: a NaN of the map leaves the grey pixel, every other value v gives
+ *                  jet(v * scene_color_scale, 0, 2) (utils/visualization.h:142-167) with C++'s promotions as written there: the first
+ *                  branch is float arithmetic, the other three go through double (their 0.25 * dv, 0.5 * dv, 0.75 * dv literals); the
+ *                  result is truncated to uint8_t.
+ *   w1 / w2 maps   w1_map_ / w2_map_, flame.cc:498-503: interpolateMesh(triangles, vtx, vtx_w1 [vtx_w2], all valid, all valid), NaN where
+ *                  no triangle covers the pixel.  The winning triangle of a pixel is the same for every attribute and its index stands in
+ *                  the rasteriser's key image, so they cost no second and third rasterisation -- unless the resident map was rasterised
+ *                  with a validity mask (tri_valid != NULL): then the rasteriser runs twice into buffers of this stage.  Same values.
+ *   normals image  drawNormals, flame.cc:2667-2697: planeParamToNormal (flame.cc:2643-2663) at u = (col, row), evaluated AS WRITTEN, its
+ *                  quirks included: K(0,0) and K(1,1) stand where one would expect the principal point.  Float subexpressions stay
+ *                  float; a, b, d, nx, ny, nz are double; the normal is cast to float, normalised (a no-op unless the squared norm is
+ *                  > 0, sums left to right: the conventions of flame_nltgv2_mesh_outputs) and negated.  normalMap
+ *                  (utils/visualization.h:119-130) is painted only where normal(2) > 0.0f; a NaN anywhere leaves the grey pixel.
+ *   flip           debug_flip_images, cv::flip(img, img, -1): the unflipped image in reversed linear pixel order.  The w maps are not
+ *                  images and are never flipped. */
+typedef struct flame_nltgv2_debug_image_params {
+  float   scene_color_scale;  /* 1.0  params.h:109 */
+  int32_t flip;               /* 0    debug_flip_images */
+  int32_t want_idepthmap;     /* 1    drawInverseDepthMap, flame.cc:2699-2719 */
+  int32_t want_normals;       /* 1    flame.cc:497-506 + drawNormals, flame.cc:2667-2697 */
+} flame_nltgv2_debug_image_params;
+void flame_nltgv2_default_debug_image_params(flame_nltgv2_debug_image_params* p);
+
+/* Pointers into pinned memory of the context, valid until the next flame_nltgv2_debug_images_begin. */
+typedef struct flame_nltgv2_debug_images_view {
+  int32_t rows, cols;
+  const uint8_t* idepthmap_img;  /* [rows * cols * 3] debug_img_idepthmap_; NULL: not asked for */
+  const uint8_t* normals_img;    /* [rows * cols * 3] debug_img_normals_; NULL: not asked for */
+  const float* w1_map;           /* [rows * cols] w1_map_, NaN where uncovered; NULL without want_normals */
+  const float* w2_map;           /* [rows * cols] w2_map_ */
+  float device_ms;               /* measurement aid: HIP-event time of the stage on the side stream, kernels and copies out */
+} flame_nltgv2_debug_images_view;
+
+/* begin  checks the arguments -- an error (no graph; no resident map, or one of another size than rows x cols; no resident triangles for
+ *        the current topology; both or neither image pointer; step_bytes < cols; K or params NULL) is reported before anything is enqueued
+ *        and leaves the outputs of an earlier begin as they are --, then enqueues everything on the context's side stream, beside a running
+ *        solver, and returns.
+ *        The grey image is fnew_->img[0]: rows of cols bytes, step_bytes apart, in host memory (img_host: staged through pinned memory;
+ *        the caller's buffer is free when begin returns) or in device memory (img_device, e.g. flame_stereo_frame_image_device: nothing
+ *        is uploaded; it must stay valid until _end).  Exactly one of the two is non-NULL.  K: 9 floats row-major (Flame::K_).
+ *        WHICH MAP AND WHICH STATE: the inverse-depth map is the resident unfiltered map the last flame_nltgv2_interpolate_mesh[_begin]
+ *        left on the device, the triangles are the ones that call left there (as flame_nltgv2_mesh_outputs_begin(triangles = NULL) uses
+ *        them), and w1 / w2 are read from the state flame_nltgv2_interpolate_mesh_begin would read (FLAME_NLTGV2_OPT_MESH_STATE decides
+ *        in the same way) -- so a debug_images_begin right behind an interpolate_mesh_begin describes the state of that map.
+ *        The resident map, the pinned map of interpolate_mesh_end, the buffers of mesh_outputs and the key image are only read.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_debug_images == begin; end; copies into the caller's arrays (each may be NULL). */
+int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
+                                    const float* K, const flame_nltgv2_debug_image_params* params, int rows, int cols);
+int flame_nltgv2_debug_images_end(flame_nltgv2_ctx* ctx, flame_nltgv2_debug_images_view* out);
+int flame_nltgv2_debug_images(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes, const float* K,
+                              const flame_nltgv2_debug_image_params* params, int rows, int cols, uint8_t* idepthmap_img_out,
+                              uint8_t* normals_img_out, float* w1_map_out, float* w2_map_out);
+
 /* 2-D Delaunay triangulation of float32 points: the counterpart of utils::Delaunay
  * (src/flame/utils/delaunay.{h,cc}, a wrapper of the vendored Shewchuk Triangle called with "zneQB",
  * delaunay.cc:66-68) that feeds Flame::syncGraph its edge list (flame.cc:2073-2104) and interpolateMesh its

@@ -368,6 +368,28 @@ int flame_stereo_select_graph_features_arrays(flame_stereo_ctx* ctx, const flame
                                               const flame_stereo_feature* feats, const flame_stereo_feature* feats_in_curr,
                                               flame_stereo_graph_inputs* out);
 
+/* ---- getDebugImageFeatures (flame.h:294-306) ------------------------------------------------------------------------
+ * Flame::drawFeatures (flame.cc:2459-2510) on the projected set of the last project_features, over the image of resident
+ * frame `cur_frame_id`: the grey image as three equal bytes, then, in index order, every feature with
+ * idepth_var < idepth_var_max_graph (strict; a NaN is not drawn) fills the rectangle [xi - 2, xi + 2] x [yi - 2, yi + 2],
+ * both corners inclusive, clipped to the image, xi = (int)(x + 0.5f), yi = (int)(y + 0.5f) (C truncation), with
+ * jet(idepth_mu * scene_color_scale, 0, 2) (utils/visualization.h:142-167; bytes c[0], c[1], c[2]).  Where rectangles
+ * overlap the feature with the higher index wins, as in the sequential loop.  flip != 0: cv::flip(img, img, -1), the
+ * image in reversed linear pixel order.  debug_draw_text_overlay (cv::putText) is treated as false.
+ *   *num_converged    the features drawn (the reference's num_converged)
+ *   *num_unconverged  the others (the counter the reference calls num_valid); either pointer may be NULL
+ * UNPINNED: cv::rectangle's fill rule (thickness -1) is restated here, not checked against OpenCV.  UNPINNED too: a NaN
+ * idepth_mu is undefined in the reference (it casts a NaN to uint8_t); this library's colour for it is (0, 0, 255), which
+ * is what x86 produces.  A coordinate that does not fit an int saturates (the reference's cast is undefined there).
+ * img_out: height * width * 3 bytes of host memory.  Enqueues on the context's stream and waits once. */
+int flame_stereo_draw_features(flame_stereo_ctx* ctx, uint32_t cur_frame_id, float idepth_var_max_graph,
+                               float scene_color_scale, int flip, uint8_t* img_out, int32_t* num_converged,
+                               int32_t* num_unconverged);
+/* Address and pitch of the unpadded image (fnew_->img[0]) of a resident frame, inside its padded device image: what
+ * flame_nltgv2_debug_images_begin takes as img_device, so a frame loop uploads no image twice.  Valid until the frame is
+ * dropped or replaced (add_frame with the same id, set_camera). */
+int flame_stereo_frame_image_device(flame_stereo_ctx* ctx, uint32_t frame_id, const void** img, int* step_bytes);
+
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
  * bit for bit.  GRAPH_COPY: how select_graph_features brings its arrays down: 0 (default) the whole output block in one
