@@ -1,4 +1,4 @@
-// nltgv2_device.hpp -- device functions shared by the solver's kernel files (nltgv2_kernels.hip, nltgv2_persistent.hip): the
+// nltgv2_device.hpp -- device functions shared by the solver's kernel files (nltgv2_kernels.hip, nltgv2_persistent*.hip): the
 // reference's scalar arithmetic, kept expression for expression.
 //
 // Reference arithmetic: /root/reference/src/flame/optimizers/nltgv2_l1_graph_regularizer.{h,cc} (cited per function).  Every

@@ -110,12 +110,14 @@ struct FusedArgs {
   int* abort_flag = nullptr;
   int* err = nullptr;
 };
+// bytes of one copy of a persistent run's records (S of the exchange buffer [R0|L0|R1|L1|XCC], nltgv2_device.hpp)
+inline int persistent_rec_bytes(const FusedArgs& a) { return (a.n_rec > a.n_slices * 64 ? a.n_rec : a.n_slices * 64) * 16; }
 
 int launch_fused_step(const FusedArgs& a, const SolverParams& p, int parity, bool write_prev, int unroll,
                       int waves_per_block, hipStream_t stream);
 int launch_persistent_run(const FusedArgs& a, const SolverParams& p, int form, int wave_begin, int n_waves,
                           int parity_in, unsigned tag0, int n_iters, int waves_per_block, unsigned max_spins,
-                          int presleep, int dual, int tv_static_in_lds, int xcds, const RunTail* tail, bool cooperative,
+                          int presleep, int dual, int xcds, const RunTail* tail, bool cooperative,
                           hipStream_t stream);
 // Record placement (nltgv2_layout.hip): calibrate a pool of 2 x kPlacePages pages, then per topology give the records read
 // across XCDs a slot on a page that suits their pair of XCDs
@@ -187,7 +189,7 @@ int pv2_patches_per_cu(int lcap, bool verify);
 int launch_persistent_pv2(const FusedArgs& a, const Pv2Args& w, const SolverParams& p, int wg_begin, int n_wgs, int parity_in, unsigned tag0,
                           int n_iters, unsigned max_spins, int poll_gap, int dual, const RunTail* tail, bool cooperative, hipStream_t stream);
 int pv_real_waves_per_simd(bool verify_or_probe);
-const void* persistent_tv_kernel(bool static_in_lds, int waves_per_block, unsigned* lds_bytes);  // nltgv2_persistent_tv.hip
+const void* persistent_tv_kernel(int waves_per_block, unsigned* lds_bytes);  // nltgv2_persistent_tv.hip
 // device-side expansion of the layout arrays (nltgv2_layout.hip)
 int launch_build_sell(const CanonArgs& c, const FusedArgs& a, const int32_t* iperm, hipStream_t s);
 int launch_build_patches(const CanonArgs& c, const FusedArgs& a, const int32_t* wg_v0, const int32_t* order_m,

@@ -1,8 +1,8 @@
 // nltgv2_persistent.hip -- the persistent single-launch kernels of the NLTGV2-L1 solver for gfx950 (MI355X, CDNA4): n steps in ONE
 // launch as pure dataflow between resident waves -- k_persistent_pv (a patch per wave, a lane per half-edge: the dominant kernel
 // of the bench); k_persistent_tv (a vertex per lane) is in nltgv2_persistent_tv.hip -- their launcher and the residency rule.
-// Arithmetic and its citations: nltgv2_device.hpp; compiled with -ffp-contract=off like nltgv2_kernels.hip.
-#include "nltgv2_device.hpp"
+// What the three kernels share: nltgv2_persistent_common.hpp.  Arithmetic and its citations: nltgv2_device.hpp; compiled with -ffp-contract=off like nltgv2_kernels.hip.
+#include "nltgv2_persistent_common.hpp"
 
 namespace flame_hip {
 
@@ -74,42 +74,10 @@ namespace {
 // Protocol (tags, two parity buffers, remote / XCD-local copies chosen from the true XCC ids, bounded waits,
 // transactional outputs): see above.
 // ------------------------------------------------------------------------------------------------
-constexpr unsigned kWgActiveBit = 1u << 25, kWgValidBit = 1u << 26, kWgPublishBit = 1u << 27, kWgHeadBit = 1u << 28;
-typedef float v2f_t __attribute__((ext_vector_type(2)));
-typedef float v4f_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void lds_wave_sync() {  // LDS operations of one wave are processed in issue order
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-__device__ __forceinline__ unsigned read_hw_id() {
-  unsigned v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
-
-// Which wait of a persistent run expired, for the host's trace (FLAME_NLTGV2_TRACE) and flame_nltgv2_info: the first wave
-// to give up leaves {which wait, patch, step, lanes still waiting, the foreign record of the first of them, tag seen / wanted,
-// XCC and HW ids} in err[1..10] (err[0] stays the flag word).  which: 1 rotation word, 2 XCC table, 3 a step's records.
-__device__ __forceinline__ void report_expired(int* err, int which, int wg, int it, unsigned long long pend, int frid, unsigned seen,
-                                               unsigned want) {
-  if (atomicCAS(&err[1], 0, which) == 0) {
-    err[2] = wg, err[3] = it, err[4] = (int)(unsigned)pend, err[5] = (int)(unsigned)(pend >> 32), err[6] = frid;
-    err[7] = (int)seen, err[8] = (int)want, err[9] = (int)read_xcc_id(), err[10] = (int)read_hw_id();
-  }
-}
-
 // amdgpu_num_sgpr(92): 90 SGPRs as built -> 96 + the trap handler's 16 = 112 per wave, SEVEN waves per SIMD really resident (at the
 // compiler's own choice, 106, it is six: "Round 3" in docs/DESIGN_r3.md section 4); the scalar spills this costs stay outside the hand-off path
 // (640x480: 0.962 against 0.962 us per iteration, profiles/r03_priority.txt (7)) and a 1080p frame's 25 patches per CU fit one launch.
-// OPEN (round 6): a run that goes on until the host needs the state.  n_iters is then an upper bound; ONE patch (the middle one of the
-// launch) looks at a word the host sets to this run's tag0 (a 4-byte copy on a stream of its own; a request for an earlier run means nothing, so the
-// word is never cleared) every kOpenCheck iterations and, when it says so, publishes the iteration every
-// patch leaves at -- its own plus kOpenMargin, more than any patch can be ahead of it (a patch is ahead of another by at most their
-// distance in the patch graph) -- in err[12] as tag0 + iteration (tags grow from run to run: a stale word of an earlier run is below
-// this run's tag0 and means nothing).  Every patch reads that word every kOpenCheck iterations.  A patch that saw the word too late has no neighbours left to wait for: its
-// wait expires and the run is taken back and redone like any other (nltgv2_run.hip finish()).  The patch that decides leaves the
-// number of iterations done in err[13] (tag0 + n) on its way out.
-constexpr unsigned kOpenMargin = 128u, kOpenCheck = 64u;  // (both even: an open run does an even number of iterations)
+// OPEN: the instance of an open run, one that goes on until the host needs the state (nltgv2_persistent_common.hpp).
 template <bool PROBE, bool VERIFY, bool OPEN = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(92)))
 k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, const int lcap, const int slab_slots,
@@ -144,8 +112,7 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
       if ((v & ~15u) == want) break;
       if (spins > (max_spins_arg & 0x7fffffffu)) {
         if (lane == 0) {
-          __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          atomicOr(err, 2);
+          give_up(abort_flag, err, false);
           report_expired(err, 1, (int)blockIdx.x, -1, 0ull, -1, v, want);
         }
         return;
@@ -215,7 +182,7 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
   const float beta = q.w;
   float q1 = q.x;
   v2f_t q23 = {q.y, q.z};
-  // signed per-lane constants: see k_persistent_wg
+  // signed per-lane constants: the per-role selects of the dual update folded in ("step" above)
   const float as = is_target ? -alpha : alpha, bs = is_target ? -beta : beta, ac = is_target ? alpha : -alpha;
   const v2f_t P12 = {alpha * dx, alpha * dy};
   // (a lane without a half-edge has all-zero constants and q = +0 for good: its (cx, a, b) come out as (-0, a, -0) with
@@ -253,6 +220,8 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
   // ---- where this lane's polls read: the remote copy of its foreign record, or the copy in this XCD's L2 ------------
   int off0 = (frid >= 0) ? (frid << 4) : 0;
   bool fetch_remote = frid >= 0;
+  // (the XCC-table exchange below is in nltgv2_persistent_pv2.hip once more, word for word but for fetch_remote: as a shared function, in every
+  //  shape tried, it changed the register allocation of the whole kernel -- profiles/persistent_common.txt)
   if (dual) {
     const unsigned my_xcc = read_xcc_id();
     if (state_lane && publishes)
@@ -416,17 +385,7 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
 #undef PV_POLL_U
     }
     if (VERIFY && verify && !timed_out) {
-      // Every fetch lane reads its foreign record once more, with an ordinary load, and compares all four dwords with
-      // what the LDS-DMA left in its slot: a record is final once its tag is visible, so a difference means a torn
-      // 16-byte access (memory side or LDS side) -- reported, the run is taken back and redone per step.
-      v4i_t g2 = {0, 0, 0, 0};
-      if (frid >= 0) {
-        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(g2) : "v"(src) : "memory");
-      }
-      const float4 l4 = lds[fetch_area + lane];
-      if ((verify & 2) && it == 2 && wg == wg_begin && lane == 0) g2.x ^= 0x00400000;  // test hook
-      const bool bad = frid >= 0 && (g2.x != __float_as_int(l4.x) || g2.y != __float_as_int(l4.y) || g2.z != __float_as_int(l4.z) ||
-                                     (unsigned)g2.w != s || __float_as_uint(l4.w) != s);
+      const bool bad = fetch_record_torn(frid, src, &lds[fetch_area + lane], s, verify, it, wg, wg_begin, lane);
       if (__any(bad)) torn = timed_out = true;
     }
     unsigned pr_t1 = 0;
@@ -562,17 +521,10 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
 #undef PV_ADDS
       Wa = v2f_t{W1, W2};
     }
-    // ---- vertex update: proxL1 (cc:147-151, h:179-197), extragradient (cc:160-171) --------------------------
-    // (both shifted values up front and two selects: as branches this was three exec-masked blocks in the hand-off path)
-    const float diff = X - data, x_dn = X - thr, x_up = X + thr;
-    float xn = (diff < -thr) ? x_up : data;
-    xn = (diff > thr) ? x_dn : xn;
-    xn = (xn < p.x_min) ? p.x_min : xn;
-    xn = (xn > p.x_max) ? p.x_max : xn;
-    float nb = xn + p.theta * (xn - x);
-    nb = (nb < p.x_min) ? p.x_min : nb;
-    nb = (nb > p.x_max) ? p.x_max : nb;
-    const v2f_t wbn = Wa + p.theta * (Wa - w12);
+    // ---- vertex update: proxL1, extragradient ---------------------------------------------------------------
+    const VertexNext vn = vertex_update(p, X, Wa, x, w12, data, thr);
+    const float xn = vn.xn, nb = vn.nb;
+    const v2f_t wbn = vn.wbn;
     if (pub_lane) {
       v4i_t o;
       o.x = __float_as_int(nb), o.y = __float_as_int(wbn.x), o.z = __float_as_int(wbn.y), o.w = (int)(s + 1u);
@@ -616,25 +568,7 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
     unsigned* const stop_word = reinterpret_cast<unsigned*>(err) + 12;
     unsigned stop_at = 0u;  // tag0 + the iteration to leave at, once known
     for (; it + 1 < n_iters && !timed_out; it += 2) {
-      // Every kOpenCheck iterations -- all patches at the same ones: the network runs in lock step, so the ~0.5 us this load takes are
-      // spent by everybody at once, 1-2 % of the time -- the word is looked at; the deciding patch first looks at the host's request.
-      // (Asked for every trip and looked at a trip later it cost 17 %: the compiler waits for the publish stores in front of the
-      //  load, and the step's polls never wait for vmcnt, so nothing hides it.)
-      if (((unsigned)it & (kOpenCheck - 1u)) == 0u) {
-        if (decides && stop_at == 0u && stop_req &&
-            (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(stop_req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == tag0) {
-          stop_at = tag0 + (unsigned)it + kOpenMargin;
-          if (lane == 0) {
-            __hip_atomic_store(stop_word, stop_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // (taken: tags start over with every topology, the next graph's first run has this tag0 again)
-            __hip_atomic_store(const_cast<unsigned*>(stop_req), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        if (stop_at == 0u) {
-          const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(stop_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-          if (w > tag0 && w - tag0 <= (unsigned)n_iters + kOpenMargin) stop_at = w;  // (a word of an earlier run is below this run's tag0)
-        }
-      }
+      if (((unsigned)it & (kOpenCheck - 1u)) == 0u) open_run_check(stop_at, decides, stop_req, stop_word, tag0, it, n_iters, lane);
       if (stop_at != 0u && stop_at - tag0 <= (unsigned)it) break;
       step(tag0 + (unsigned)it, rdA_nbr, dstA, wrB_rec, areaA + lcap, it, srcA, pubB, wrA_rec);
       if (timed_out) break;
@@ -653,30 +587,14 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
 
   if (timed_out) {
     if (lane == 0) {
-      __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      atomicOr(err, torn ? 4 : 2);
+      give_up(abort_flag, err, torn);
       unsigned* const pg = tail->progress;  // (trace runs only) the step this patch was in when it left
       if (pg) pg[wg - wg_begin] = 0x80000000u | (unsigned)(it + 1);
     }
     return;
   }
 
-  if (state_lane) {
-    vstate_out[pv] = make_float4(x, w12.x, w12.y, data);
-    bar_out[pv] = make_float4(xb, wb12.x, wb12.y, 0.0f);
-    vprev[pv] = make_float4(x_prev, w_prev.x, w_prev.y, 0.0f);
-    float* const export_out = tail->export_out;
-    float* const photo_err = tail->photo.err;
-    if (export_out || photo_err) {
-      const int o = perm[pv];  // the caller's vertex index
-      if (o >= 0 && export_out) export_out[o] = x * tail->export_scale;
-      if (o >= 0 && photo_err) {
-        const PhotoFuse& photo = tail->photo;
-        photo_err[o] = photo_residual_at(photo.pos[o], x * photo.graph_scale, photo.geo, photo.ref, photo.cmp, photo.rows,
-                                         photo.cols, photo.step, photo.border);
-      }
-    }
-  }
+  if (state_lane) write_back_vertex(pv, x, w12, xb, wb12, x_prev, w_prev, data, vstate_out, bar_out, vprev, perm, tail);
   if (active) hq_out[slot] = make_float4(q1, q23.x, q23.y, beta);
   if (!ok && active) atomicOr(err, 1);
 }
@@ -700,9 +618,13 @@ int pv_real_waves_per_simd(bool verify_or_probe) {
   return verify_or_probe ? 5 : 7;
 }
 
+// Dynamic LDS of one patch of k_persistent_pv (its "LDS map", float4 units: two record areas of lcap local + 64 fetch slots, the
+// slab, 64 spare entries): the occupancy query and the launch must ask for the same.
+static unsigned pv_lds_bytes(int lcap, int slab_slots) { return 16u * (unsigned)(2 * (lcap + 64) + slab_slots + 64); }
+
 int pv_patches_per_cu(const FusedArgs& a, bool verify) {
   if (!a.wg_rowpack) return 0;  // (not row-packed: the lane-per-half-edge form's layout)
-  const size_t ldsv = 16u * (size_t)(2 * (a.wg_lcap + 64) + a.wg_slab_slots + 64);
+  const size_t ldsv = pv_lds_bytes(a.wg_lcap, a.wg_slab_slots);
   int n = 0;
   const void* fv = verify ? (const void*)k_persistent_pv<false, true> : (const void*)k_persistent_pv<false, false>;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fv, 64, ldsv) != hipSuccess) {
@@ -717,7 +639,7 @@ int pv_patches_per_cu(const FusedArgs& a, bool verify) {
 // so the caller can fall back to per-step launches.
 int launch_persistent_run(const FusedArgs& a, const SolverParams& p, int form, int wave_begin, int n_waves,
                           int parity_in, unsigned tag0, int n_iters, int waves_per_block, unsigned max_spins,
-                          int presleep, int dual, int tv_static_in_lds, int xcds, const RunTail* tail, bool cooperative,
+                          int presleep, int dual, int xcds, const RunTail* tail, bool cooperative,
                           hipStream_t stream) {
   if (n_waves <= 0 || n_iters <= 0) return (int)hipSuccess;
   // Workgroup b runs on XCD b & 7.  With xcds < 8 only the first `xcds` XCDs get waves (the workgroups of the
@@ -741,7 +663,7 @@ int launch_persistent_run(const FusedArgs& a, const SolverParams& p, int form, i
   float4* bout = a.bar[parity_in ^ 1];  // always the other buffer: the input of a failed run stays intact
   float4* vprev = a.vprev;
   void* xbuf = a.xbuf;
-  int rec_bytes = (a.n_rec > a.n_slices * 64 ? a.n_rec : a.n_slices * 64) * 16;
+  int rec_bytes = persistent_rec_bytes(a);
   SolverParams pp = p;
   int* err = a.err;
   int* abort_flag = a.abort_flag;
@@ -760,7 +682,7 @@ int launch_persistent_run(const FusedArgs& a, const SolverParams& p, int form, i
     const int32_t* rec_off = a.rec_off;
     int rec_off_stride = a.rec_off_stride;
     unsigned* rot_word = place_pool ? a.rot_word : nullptr;
-    const unsigned ldsv = 16u * (unsigned)(2 * (lcap + 64) + slab_slots + 64);
+    const unsigned ldsv = pv_lds_bytes(lcap, slab_slots);
     void* vargs[] = {&wave_begin, &n_waves, &wgx, &lcap, &slab_slots, &w0, &w1, &w2, &w3, &w4, &w5, &hrec, &hq, &vstate,
                      &hq_out, &vstate_out, &vaux, &bin, &bout, &vprev, &xbuf, &rec_bytes, &dual, &tag0, &n_iters,
                      &max_spins, &poll_gap, &pp, &err, &abort_flag, &perm, &tail, &probe, &place_pool, &rec_off, &rec_off_stride, &rot_word};
@@ -773,7 +695,7 @@ int launch_persistent_run(const FusedArgs& a, const SolverParams& p, int form, i
     return (int)hipExtLaunchKernel(fv, gv, bv, vargs, ldsv, stream, nullptr, a.stop_event, 0);
   }
   unsigned lds_bytes = 0u;
-  const void* fn = persistent_tv_kernel(tv_static_in_lds != 0, waves_per_block, &lds_bytes);
+  const void* fn = persistent_tv_kernel(waves_per_block, &lds_bytes);
   // The first launch of a topology is cooperative: the runtime verifies that the whole grid is
   // resident (hipErrorCooperativeLaunchTooLarge otherwise).  The same grid is then launched plainly
   // (identical residency, ~15 us less launch overhead per call).

@@ -5,29 +5,11 @@
 // on"): this form is for graphs that fill the chip in the one-half-edge-per-lane form (a 1920x1080 frame: 25 waves per CU there,
 // 12.6 here).  Against k_persistent_pv it has no cycle probe, no placed records and takes no vertex of more than 32 edges (the planner
 // keeps such graphs on the other forms); the record verification (FLAME_NLTGV2_OPT_VERIFY_RECORDS) is a second instance.
-#include "nltgv2_device.hpp"
+#include "nltgv2_persistent_common.hpp"
 
 namespace flame_hip {
 
 namespace {
-
-constexpr unsigned kWgActiveBit = 1u << 25, kWgValidBit = 1u << 26, kWgPublishBit = 1u << 27, kWgHeadBit = 1u << 28;
-typedef float v2f_t __attribute__((ext_vector_type(2)));
-typedef float v4f_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void lds_wave_sync2() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned read_hw_id2() {
-  unsigned v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
-__device__ __forceinline__ void report_expired2(int* err, int which, int wg, int it, unsigned long long pend, int frid, unsigned seen,
-                                                unsigned want) {
-  if (atomicCAS(&err[1], 0, which) == 0) {
-    err[2] = wg, err[3] = it, err[4] = (int)(unsigned)pend, err[5] = (int)(unsigned)(pend >> 32), err[6] = frid;
-    err[7] = (int)seen, err[8] = (int)want, err[9] = (int)read_xcc_id(), err[10] = (int)read_hw_id2();
-  }
-}
 
 // The per-half-edge constants of one slot (see k_persistent_pv: the role selects folded into signed constants)
 struct SlotConst {
@@ -36,7 +18,7 @@ struct SlotConst {
   v2f_t P12, C2;
 };
 
-// OPEN: the open run's instance (nltgv2_persistent.hip, k_persistent_pv: the same words of the error block, the same margin and interval)
+// OPEN: the open run's instance (nltgv2_persistent_common.hpp: the same words of the error block, margin and interval as k_persistent_pv)
 template <bool VERIFY, bool OPEN = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(92)))
 k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, const int lcap, const int32_t* __restrict__ wg_slot,
@@ -136,7 +118,7 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
   lds[rec_stride + lcap + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
 
   int off0 = (frid >= 0) ? (frid << 4) : 0;
-  if (dual) {
+  if (dual) {  // (k_persistent_pv's XCC-table exchange, kept as a copy: see the note there)
     const unsigned my_xcc = read_xcc_id();
     if (state_lane && publishes)
       __builtin_amdgcn_raw_buffer_store_b32((int)(xcc_want | my_xcc), rx, tab_off + (my_off >> 2), 0, kAuxSc1);
@@ -157,7 +139,7 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
           const int fl = __ffsll((long long)pm) - 1;
           const int ff = __shfl(frid, fl, 64);
           const unsigned gs = (unsigned)__shfl((int)g0, fl, 64);
-          if (lane == 0) report_expired2(err, 2, wg, -1, pm, ff, gs, xcc_want);
+          if (lane == 0) report_expired(err, 2, wg, -1, pm, ff, gs, xcc_want);
           break;
         }
         __builtin_amdgcn_s_sleep(2);
@@ -186,7 +168,7 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
       publish(o, p0 ? pa1 : pa0, (int)(tag0 & (kPar - 1)) * par);
     }
   }
-  lds_wave_sync2();
+  lds_wave_sync();
   const unsigned lds_addr0 = (unsigned)(size_t)(lds);
 
   auto step = [&](const unsigned s, const unsigned rd_n0, const unsigned rd_n1, const unsigned dst, const int wr_rec, const int it,
@@ -205,34 +187,8 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
 // the records gathered from scattered slots -- is what the polling waves of a CU load its LDS pipe with.  All a round has to find out
 // is whether the patch's FOREIGN records have arrived (the local ones were written by this wave before the wait, in program order):
 // one tag word per lane from its own fetch slot; the neighbour records are read once, when the last of them is in.
-#ifdef FLAME_PV2_FULL_POLL
-#define PV2_ROUND_READS                                                                                  \
-               "ds_read_b32 %[ta], %[ra] offset:12\n\t"                                                 \
-               "ds_read_b32 %[tb], %[rb] offset:12\n\t"                                                 \
-               "ds_read_b32 %[t2], %[fa] offset:12\n\t"                                                 \
-               "ds_read_b128 %[na], %[ra]\n\t"                                                          \
-               "ds_read_b128 %[nb], %[rb]\n\t"
-#define PV2_ROUND_PENDING                                                                                \
-               "v_cmp_ne_u32_e32 vcc, %[tag], %[ta]\n\t"                                                \
-               "s_mov_b64 %[wt], vcc\n\t"                                                               \
-               "v_cmp_ne_u32_e32 vcc, %[tag], %[tb]\n\t"                                                \
-               "s_or_b64 %[wt], %[wt], vcc\n\t"
-#define PV2_AFTER_WAIT
-#else
-// (only the fetch lanes that still wait read -- a lane that has seen its record keeps the matching tag in its register: -1 % more)
-#define PV2_ROUND_READS                                                                                  \
-               "s_mov_b64 exec, %[pn]\n\t"                                                              \
-               "ds_read_b32 %[t2], %[fa] offset:12\n\t"                                                 \
-               "s_mov_b64 exec, %[ex]\n\t"
-#define PV2_ROUND_PENDING                                                                                \
-               "s_mov_b64 %[wt], %[pn]\n\t"
-#define PV2_AFTER_WAIT                                                                                   \
-               "ds_read_b128 %[na], %[ra]\n\t"                                                          \
-               "ds_read_b128 %[nb], %[rb]\n\t"                                                          \
-               "v_mov_b32 %[ta], %[tag]\n\t"                                                            \
-               "v_mov_b32 %[tb], %[tag]\n\t"                                                            \
-               "s_waitcnt lgkmcnt(0)\n\t"
-#endif
+// Only the fetch lanes that still wait read -- a lane that has seen its record keeps the matching tag in its register: -1 % more.
+// (The poll that read every lane's tags and records in every round was retired with that: profiles/r04_pv2_light_poll.txt.)
 #define PV2_POLL                                                                                          \
   asm volatile("s_setprio 0\n\t"                                                                        \
                "s_mov_b64 %[ex], exec\n\t"                                                             \
@@ -252,12 +208,14 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
                "s_sub_u32 %[k], %[k], 1\n\t"                                                            \
                "s_branch 4b\n\t"                                                                        \
                "3:\n\t"                                                                                 \
-               PV2_ROUND_READS                                                                          \
+               "s_mov_b64 exec, %[pn]\n\t"                                                              \
+               "ds_read_b32 %[t2], %[fa] offset:12\n\t"                                                 \
+               "s_mov_b64 exec, %[ex]\n\t"                                                              \
                "s_add_u32 %[cnt], %[cnt], 1\n\t"                                                        \
                "s_waitcnt lgkmcnt(0)\n\t"                                                               \
                "v_cmp_ne_u32_e32 vcc, %[tag], %[t2]\n\t"                                                \
                "s_and_b64 %[pn], vcc, %[fm]\n\t"                                                        \
-               PV2_ROUND_PENDING                                                                        \
+               "s_mov_b64 %[wt], %[pn]\n\t"                                                             \
                "s_cmp_eq_u32 %[fn], 0\n\t"                                                              \
                "s_cselect_b64 %[pn], %[fm], %[pn]\n\t"                                                  \
                "s_cmp_eq_u64 %[wt], 0\n\t"                                                              \
@@ -266,7 +224,11 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
                "s_cbranch_scc1 1b\n\t"                                                                  \
                "2:\n\t"                                                                                 \
                "s_setprio 3\n\t"                                                                        \
-               PV2_AFTER_WAIT                                                                           \
+               "ds_read_b128 %[na], %[ra]\n\t"                                                          \
+               "ds_read_b128 %[nb], %[rb]\n\t"                                                          \
+               "v_mov_b32 %[ta], %[tag]\n\t"                                                            \
+               "v_mov_b32 %[tb], %[tag]\n\t"                                                            \
+               "s_waitcnt lgkmcnt(0)\n\t"                                                               \
                "s_mov_b32 m0, %[keep]"                                                                   \
                : [keep] "=&s"(keep), [cnt] "=&s"(cnt), [na] "=&v"(nbv0), [nb] "=&v"(nbv1), [ta] "=&v"(tag_a), [tb] "=&v"(tag_b),   \
                  [t2] "=&v"(tagf), [pn] "=&s"(pnarrow), [k] "=&s"(gapk), [ex] "=&s"(exec_saved), [wt] "=&s"(waiting)                \
@@ -284,7 +246,7 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
               const unsigned long long pm = __ballot(tag_a != s || tag_b != s || (frid >= 0 && tagf != s));
               const int fl = __ffsll((long long)pm) - 1;
               const unsigned gs = (unsigned)__shfl((int)tag_a, fl, 64);
-              if (lane == 0) report_expired2(err, 3, wg, it, pm, -1, gs, s);
+              if (lane == 0) report_expired(err, 3, wg, it, pm, -1, gs, s);
             }
             break;
           }
@@ -296,16 +258,7 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
 #undef PV2_POLL
     }
     if (VERIFY && verify && !timed_out) {
-      // every fetch lane reads its foreign record once more, with an ordinary load, and compares all four dwords with what the
-      // LDS-DMA left in its slot (k_persistent_pv): a difference is a torn 16-byte access -- reported, the run is taken back
-      v4i_t g2 = {0, 0, 0, 0};
-      if (frid >= 0) {
-        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(g2) : "v"(src) : "memory");
-      }
-      const float4 l4 = lds[fetch_area + lane];
-      if ((verify & 2) && it == 2 && wg == wg_begin && lane == 0) g2.x ^= 0x00400000;  // test hook
-      const bool bad = frid >= 0 && (g2.x != __float_as_int(l4.x) || g2.y != __float_as_int(l4.y) || g2.z != __float_as_int(l4.z) ||
-                                     (unsigned)g2.w != s || __float_as_uint(l4.w) != s);
+      const bool bad = fetch_record_torn(frid, src, &lds[fetch_area + lane], s, verify, it, wg, wg_begin, lane);
       if (__any(bad)) torn = timed_out = true;
     }
     xb = own.x, wb12 = v2f_t{own.y, own.z};
@@ -388,16 +341,10 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
 #undef PV2_ADDS
     }
     const v2f_t Wa = {W1, W2};
-    // ---- vertex update: proxL1 (cc:147-151, h:179-197), extragradient (cc:160-171) ----
-    const float diff = X - data, x_dn = X - thr, x_up = X + thr;
-    float xn = (diff < -thr) ? x_up : data;
-    xn = (diff > thr) ? x_dn : xn;
-    xn = (xn < p.x_min) ? p.x_min : xn;
-    xn = (xn > p.x_max) ? p.x_max : xn;
-    float nb = xn + p.theta * (xn - x);
-    nb = (nb < p.x_min) ? p.x_min : nb;
-    nb = (nb > p.x_max) ? p.x_max : nb;
-    const v2f_t wbn = Wa + p.theta * (Wa - w12);
+    // ---- vertex update: proxL1, extragradient ----
+    const VertexNext vn = vertex_update(p, X, Wa, x, w12, data, thr);
+    const float xn = vn.xn, nb = vn.nb;
+    const v2f_t wbn = vn.wbn;
     if (pub_lane) {
       v4i_t o;
       o.x = __float_as_int(nb), o.y = __float_as_int(wbn.x), o.z = __float_as_int(wbn.y), o.w = (int)(s + 1u);
@@ -425,27 +372,12 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
   char* const pubB = p0 ? pa0 : pa1;
   int it = 0;
   if (OPEN) {
-    constexpr unsigned kOpenMargin = 128u, kOpenCheck = 64u;  // (as in k_persistent_pv)
     const bool decides = wg == wg_begin + n_wgs / 2;
     const unsigned* const stop_req = tail->stop_req;
     unsigned* const stop_word = reinterpret_cast<unsigned*>(err) + 12;
     unsigned stop_at = 0u;
     for (; it + 1 < n_iters && !timed_out; it += 2) {
-      if (((unsigned)it & (kOpenCheck - 1u)) == 0u) {
-        if (decides && stop_at == 0u && stop_req &&
-            (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(stop_req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == tag0) {
-          stop_at = tag0 + (unsigned)it + kOpenMargin;
-          if (lane == 0) {
-            __hip_atomic_store(stop_word, stop_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // (taken: tags start over with every topology, the next graph's first run has this tag0 again)
-            __hip_atomic_store(const_cast<unsigned*>(stop_req), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        if (stop_at == 0u) {
-          const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(stop_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-          if (w > tag0 && w - tag0 <= (unsigned)n_iters + kOpenMargin) stop_at = w;
-        }
-      }
+      if (((unsigned)it & (kOpenCheck - 1u)) == 0u) open_run_check(stop_at, decides, stop_req, stop_word, tag0, it, n_iters, lane);
       if (stop_at != 0u && stop_at - tag0 <= (unsigned)it) break;
       step(tag0 + (unsigned)it, rdA0, rdA1, dstA, wrB_rec, it, srcA, pubB, wrA_rec, areaA + lcap);
       if (timed_out) break;
@@ -463,28 +395,10 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   if (timed_out) {
-    if (lane == 0) {
-      __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      atomicOr(err, torn ? 4 : 2);
-    }
+    if (lane == 0) give_up(abort_flag, err, torn);
     return;
   }
-  if (state_lane) {
-    vstate_out[pv] = make_float4(x, w12.x, w12.y, data);
-    bar_out[pv] = make_float4(xb, wb12.x, wb12.y, 0.0f);
-    vprev[pv] = make_float4(x_prev, w_prev.x, w_prev.y, 0.0f);
-    float* const export_out = tail->export_out;
-    float* const photo_err = tail->photo.err;
-    if (export_out || photo_err) {
-      const int o = perm[pv];
-      if (o >= 0 && export_out) export_out[o] = x * tail->export_scale;
-      if (o >= 0 && photo_err) {
-        const PhotoFuse& photo = tail->photo;
-        photo_err[o] = photo_residual_at(photo.pos[o], x * photo.graph_scale, photo.geo, photo.ref, photo.cmp, photo.rows,
-                                         photo.cols, photo.step, photo.border);
-      }
-    }
-  }
+  if (state_lane) write_back_vertex(pv, x, w12, xb, wb12, x_prev, w_prev, data, vstate_out, bar_out, vprev, perm, tail);
   if (active0) hq_out[slot0] = make_float4(q1_0, q23_0.x, q23_0.y, c0.beta);
   if (active1) hq_out[slot1] = make_float4(q1_1, q23_1.x, q23_1.y, c1.beta);
   if (!ok && (active0 || active1)) atomicOr(err, 1);
@@ -495,8 +409,10 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
 // Patches of k_persistent_pv2 really co-resident per CU (see pv_real_waves_per_simd in nltgv2_persistent.hip): from the kernel's
 // register counts as built -- <= 96 VGPRs, <= 96 SGPRs: five waves per SIMD; the instance with the record verification
 // <= 112 VGPRs: four (tests/test_abi.py re-derives both from the compiler's resource report).
+static unsigned pv2_lds_bytes(int lcap) { return 16u * (unsigned)(2 * (lcap + 64) + 64); }  // (the kernel's "LDS map": query and launch ask for the same)
+
 int pv2_patches_per_cu(int lcap, bool verify) {
-  const size_t ldsv = 16u * (size_t)(2 * (lcap + 64) + 64);
+  const size_t ldsv = pv2_lds_bytes(lcap);
   int n = 0;
   const void* fn = verify ? (const void*)k_persistent_pv2<true> : (const void*)k_persistent_pv2<false>;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64, ldsv) != hipSuccess) {
@@ -525,12 +441,12 @@ int launch_persistent_pv2(const FusedArgs& a, const Pv2Args& w, const SolverPara
   float4* bout = a.bar[parity_in ^ 1];
   float4* vprev = a.vprev;
   void* xbuf = a.xbuf;
-  int rec_bytes = (a.n_rec > a.n_slices * 64 ? a.n_rec : a.n_slices * 64) * 16;
+  int rec_bytes = persistent_rec_bytes(a);
   SolverParams pp = p;
   int* err = a.err;
   int* abort_flag = a.abort_flag;
   const int32_t* perm = a.perm;
-  const unsigned ldsv = 16u * (unsigned)(2 * (lcap + 64) + 64);
+  const unsigned ldsv = pv2_lds_bytes(lcap);
   void* vargs[] = {&wg_begin, &n_wgs, &wgx, &lcap, &w0, &w1, &w2, &w3, &w4, &w5, &hrec, &hq, &vstate, &hq_out, &vstate_out, &vaux, &bin, &bout,
                    &vprev, &xbuf, &rec_bytes, &dual, &tag0, &n_iters, &max_spins, &poll_gap, &pp, &err, &abort_flag, &perm, &tail};
   const void* fn = (dual >> 1) != 0 ? (const void*)k_persistent_pv2<true> : a.open_run ? (const void*)k_persistent_pv2<false, true> : (const void*)k_persistent_pv2<false>;

@@ -1,14 +1,14 @@
 // nltgv2_persistent_tv.hip -- the vertex-per-lane persistent kernel of the NLTGV2-L1 solver (throughput form: batches of frames);
 // launched by launch_persistent_run (nltgv2_persistent.hip).  Compiled with -ffp-contract=off; arithmetic and its citations:
 // nltgv2_device.hpp.
-#include "nltgv2_device.hpp"
+#include "nltgv2_persistent_common.hpp"
 
 namespace flame_hip {
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// Persistent run, throughput form: same dataflow protocol as k_persistent_he (tagged 16-byte bar
+// Persistent run, throughput form: same dataflow protocol as k_persistent_pv (tagged 16-byte bar
 // records, two parity buffers, bounded waits), but one VERTEX per lane with up to 8 half-edge slots
 // held in registers -- ~5x fewer instructions per half-edge than the lane-per-half-edge form, at the
 // price of a longer serial chain per wave.  It is the better choice when many waves share a CU
@@ -19,7 +19,6 @@ namespace {
 // accumulation still follows ascending edge id exactly.  The last lane of a chain owns the vertex:
 // it applies proxL1 / extragradient, publishes the record and hands the state back to its chain.
 // ------------------------------------------------------------------------------------------------
-typedef float v2f_t __attribute__((ext_vector_type(2)));
 constexpr int kTvS = 8;
 constexpr unsigned kTvOwnerBit = 1u << 16, kTvValidBit = 1u << 17;
 
@@ -37,7 +36,6 @@ __device__ __forceinline__ float dpp_shr1(float v) {  // lane l <- lane l-1; lan
 // (profiles/r04_counters.json: SQ_ACTIVE_INST_VALU = 0.24 of every wave's cycles, four waves per SIMD).  An unused slot holds
 // (as, bs, dx, dy) = (+0, +0, -0, -0) and reads a zero record: every contribution of it then is exactly -0.0, and x + (-0.0) == x
 // for every x -- no predicate in the accumulation.
-template <bool LDS_STATIC>
 __global__ void __launch_bounds__(256, 4)
 k_persistent_tv(const int wave_begin, const int n_waves, const int waves_per_xcd, const int32_t* __restrict__ tv_slot,
                 const int32_t* __restrict__ tv_vid, const uint32_t* __restrict__ tv_meta,
@@ -46,9 +44,8 @@ k_persistent_tv(const int wave_begin, const int n_waves, const int waves_per_xcd
                 float4* vprev, void* xbuf, const int rec_bytes, const int dual_arg, const unsigned tag0, const int n_iters,
                 const unsigned max_spins_arg, const int presleep, const SolverParams p, int* __restrict__ err,
                 int* __restrict__ abort_flag, const int32_t* __restrict__ perm, const RunTail* __restrict__ tail) {
-  static_assert(LDS_STATIC, "the register instance was retired in round 4");
   const unsigned max_spins = max_spins_arg & 0x7fffffffu;
-  const int dual = dual_arg & 1, verify = dual_arg >> 1;  // as in k_persistent_he
+  const int dual = dual_arg & 1, verify = dual_arg >> 1;  // (bit 0: same-XCD exchange through L2; bits 1..: record verification and its test hook)
   const int lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   const int b = blockIdx.x;
@@ -173,7 +170,7 @@ k_persistent_tv(const int wave_begin, const int n_waves, const int waves_per_xcd
     }
   }
 
-  const bool mute = (max_spins_arg >> 31) != 0u && w == wave_begin;  // test hook, see k_persistent_he
+  const bool mute = (max_spins_arg >> 31) != 0u && w == wave_begin;  // test hook (FLAME_NLTGV2_OPT_FAULT_INJECT): the first wave never publishes its first record
   if (is_owner && !timed_out && !mute) {
     v4i_t o;
     o.x = __float_as_int(xb), o.y = __float_as_int(wb12.x), o.z = __float_as_int(wb12.y), o.w = (int)tag0;
@@ -227,10 +224,7 @@ k_persistent_tv(const int wave_begin, const int n_waves, const int waves_per_xcd
           break;
         }
       }
-#ifndef TV_SPIN_SLEEP
-#define TV_SPIN_SLEEP 1
-#endif
-      __builtin_amdgcn_s_sleep(TV_SPIN_SLEEP);
+      __builtin_amdgcn_s_sleep(1);
     }
     if (timed_out) break;
     if (verify) {  // a record is final once its tag is visible: a second read must return the same 16 bytes
@@ -336,28 +330,10 @@ k_persistent_tv(const int wave_begin, const int n_waves, const int waves_per_xcd
   }
 
   if (timed_out || torn) {
-    if (lane == 0) {
-      __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      atomicOr(err, torn ? 4 : 2);
-    }
+    if (lane == 0) give_up(abort_flag, err, torn);
     return;
   }
-  if (is_owner) {  // into the other copies of the state arrays, see k_persistent_he
-    vstate_out[pv] = make_float4(x, w12.x, w12.y, data);
-    bar_out[pv] = make_float4(xb, wb12.x, wb12.y, 0.0f);
-    vprev[pv] = make_float4(x_prev, w_prev.x, w_prev.y, 0.0f);
-    float* const export_out = tail->export_out;
-    float* const photo_err = tail->photo.err;
-    if (export_out || photo_err) {
-      const int o = perm[pv];
-      if (o >= 0 && export_out) export_out[o] = x * tail->export_scale;
-      if (o >= 0 && photo_err) {
-        const PhotoFuse& photo = tail->photo;
-        photo_err[o] = photo_residual_at(photo.pos[o], x * photo.graph_scale, photo.geo, photo.ref, photo.cmp, photo.rows,
-                                         photo.cols, photo.step, photo.border);
-      }
-    }
-  }
+  if (is_owner) write_back_vertex(pv, x, w12, xb, wb12, x_prev, w_prev, data, vstate_out, bar_out, vprev, perm, tail);
 #pragma unroll
   for (int k = 0; k < kTvS; ++k) {
     if (k < nslots) hq_out[tv_slot[((size_t)w * kTvS + k) * 64 + lane]] = make_float4(q1[k], q23[k].x, q23[k].y, __builtin_fabsf(BS(k)));
@@ -373,18 +349,17 @@ k_persistent_tv(const int wave_begin, const int n_waves, const int waves_per_xcd
 
 }  // namespace
 
-// The kernel instance and its dynamic LDS bytes per workgroup.  Since round 4 only the instance with the per-slot constants in LDS is
-// built (the register instance, LDS_STATIC = false, ran 11-15 frame batches 9 % faster per wave at half the residency; those batches
-// now run as two groups of k_persistent_pv2, 9-18 % faster still: profiles/r04_large_batches.txt).
-const void* persistent_tv_kernel(bool static_in_lds, int waves_per_block, unsigned* lds_bytes) {
-  (void)static_in_lds;
+// The kernel and its dynamic LDS bytes per workgroup.  Since round 4 the per-slot constants live in LDS only (an instance that kept
+// them in registers ran 11-15 frame batches 9 % faster per wave at half the residency; those batches now run as two groups of
+// k_persistent_pv2, 9-18 % faster still: profiles/r04_large_batches.txt).
+const void* persistent_tv_kernel(int waves_per_block, unsigned* lds_bytes) {
   *lds_bytes = (unsigned)(waves_per_block * 5 * kTvS * 64 * sizeof(int));
-  return (const void*)k_persistent_tv<true>;
+  return (const void*)k_persistent_tv;
 }
 
 void warm_module_persistent_tv() {
   unsigned lds = 0;
   hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, persistent_tv_kernel(true, 4, &lds)) != hipSuccess) (void)hipGetLastError();
+  if (hipFuncGetAttributes(&fa, persistent_tv_kernel(4, &lds)) != hipSuccess) (void)hipGetLastError();
 }
 }  // namespace flame_hip

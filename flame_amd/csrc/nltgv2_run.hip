@@ -52,9 +52,8 @@ bool cooperative_allowed() {
 
 // `consume`: the call plans a run that is about to be enqueued (enqueue_run) -- only then does a planned-around run count against
 // the back-off after an expired wait; a query (persistent_eligible, prepare_run) leaves the bookkeeping alone.
-int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups, int* use_tv_lds = nullptr, bool consume = false) {
+int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups, bool consume = false) {
   groups->clear();
-  if (use_tv_lds) *use_tv_lds = 0;
   if (!ctx->opt_persistent || n < 4 || n > (1 << 24) || !ctx->prop.cooperativeLaunch) return 0;
   if (ctx->persist_refused_topo == ctx->topo || ctx->replaying == 2) return 0;
   const bool retry = ctx->replaying == 1;  // the first replay of an expired chain: persistent once more, with room left on every CU
@@ -117,9 +116,7 @@ int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups
   // vertex-per-lane form: the per-slot constants in LDS (16 waves per CU: 30 frames of 640x480 resident in one launch).  (The
   // instance that kept them in registers -- 8 waves per CU, 9 % faster per wave -- was retired in round 4: the batches it ran, 11 to
   // 15 frames, are faster as two groups of the two-half-edges patch form: profiles/r04_large_batches.txt.)
-  const bool tv_lds = form == 2;
   const int tv_cap = kTvLdsWavesPerCu * cus;
-  if (use_tv_lds) *use_tv_lds = tv_lds ? 1 : 0;
   if (form == 0) return 0;
   const int total = form == 4 ? L.wg2_count : form == 3 ? L.wg_count : L.tv_waves;
   const int cap = form == 4 ? wg2_cap : form == 3 ? wg_cap : tv_cap;
@@ -135,7 +132,6 @@ int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups
     for (size_t c = 0; ok2 && c + 1 < c2.size(); ++c) ok2 = c2[c + 1] - c2[c] <= cap;
     if (!ok2) {
       if (ensure_form_rows(ctx, 2) != 0 || !L.tv_ok) return 0;
-      if (use_tv_lds) *use_tv_lds = 1;
       groups->clear();
       return plan_groups(ctx, 2, L.tv_waves, kTvLdsWavesPerCu * cus, L.comp_tv_wave, groups);
     }
@@ -512,8 +508,7 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
   int unroll, wpb;
   pick_config(ctx, &unroll, &wpb);
   std::vector<WaveGroup> groups;
-  int tv_lds = 0;
-  const int form = plan_persistent(ctx, n, &groups, &tv_lds, /*consume=*/true);
+  const int form = plan_persistent(ctx, n, &groups, /*consume=*/true);
   // an open run: the patch-per-wave form as ONE launch of its plain instance, the first run of a chain -- anything else is run as asked
   // for (n iterations), the caller sees that from flame_nltgv2_run_open's `opened`
   const bool open_run = ctx->want_open != 0 && open_run_applies(ctx, form, groups) && !ctx->pending.active && ctx->opt_probe == 0 &&
@@ -540,7 +535,7 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
     // by per-step launches or host uploads) can never satisfy a wait of this one
     const uint32_t tag0 = ctx->tag_next + 2;
     // (topology, form, kernel instance): a new instance -- other registers, other LDS -- gets a cooperative first launch
-    const uint64_t key = ctx->topo * 1024 + (uint64_t)form * 64 + (uint64_t)tv_lds * 32 + (ctx->opt_verify != 0 ? 16 : 0) + (ctx->opt_probe != 0 ? 8 : 0) +
+    const uint64_t key = ctx->topo * 1024 + (uint64_t)form * 64 + (ctx->opt_verify != 0 ? 16 : 0) + (ctx->opt_probe != 0 ? 8 : 0) +
                          (ctx->opt_dual == 2 ? 4 : ctx->opt_dual == 1 ? 2 : 0) + (ctx->opt_xcds > 0 ? 1 : 0);
     const RunTail* tail_dev = nullptr;
     {  // standing outputs: the small block the kernels read in their epilogue, (re)sent when no slot holds it
@@ -650,7 +645,7 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
       }
       ctx->f.open_run = open_run ? 1 : 0;
       e = launch_persistent_run(ctx->f, to_sp(p), form, gr.begin, gr.count, ctx->parity, tag0, n, pw, spins_arg, presleep, dual,
-                                tv_lds, xcds, tail_dev, cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
+                                xcds, tail_dev, cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
       ctx->f.open_run = 0;
       if (e != 0) break;
     }
@@ -958,8 +953,7 @@ int flame_nltgv2_run_open(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, i
   if (max_iters == 0) return 0;
   if (ctx->pending.active) {  // applicable at all?  Asked BEFORE anything is settled: a loop that falls back to rounds must not have them waited for here
     std::vector<WaveGroup> groups;
-    int tv_lds = 0;
-    const int form = plan_persistent(ctx, max_iters, &groups, &tv_lds, /*consume=*/false);
+    const int form = plan_persistent(ctx, max_iters, &groups, /*consume=*/false);
     if (!open_run_applies(ctx, form, groups) || ctx->opt_probe != 0 || ctx->opt_verify != 0 || !ctx->h_stop || !ctx->ctl_stream) return 0;
   }
   if (ctx->pending.active) {  // an open run is the first of its chain

@@ -1,6 +1,6 @@
 """tools/patch_lead.py [SIZE...] -- how far the patches of the patch-per-wave kernel are apart while it runs: the probe stamps the end of every step
 of every patch with the 100 MHz wall clock; for every step the spread of its end over the patches, in periods, is how many iterations the first
-patch is AHEAD of the last one at that moment -- the number an open run's margin (kOpenMargin, nltgv2_persistent.hip) has to exceed together with the
+patch is AHEAD of the last one at that moment -- the number an open run's margin (kOpenMargin, nltgv2_persistent_common.hpp) has to exceed together with the
 interval of its checks.  GPU box."""
 import os
 import sys
