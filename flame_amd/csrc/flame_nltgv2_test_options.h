@@ -21,9 +21,15 @@ enum {
                                           with one launch per step) is exercised; 0 (default) = off.  The chain is first replayed in a
                                           persistent form at reduced residency, where the fault is off; 2^22 + n = the fault hits that
                                           replay as well, so the chain ends on the one-launch-per-step path */
-  FLAME_NLTGV2_OPT_POLL_GAP = 113      /* patch-per-wave form: 0 (default) = chosen from the patches per CU, 1 = no pause between
+  FLAME_NLTGV2_OPT_POLL_GAP = 113,     /* patch-per-wave form: 0 (default) = chosen from the patches per CU, 1 = no pause between
                                           the poll rounds of a wait, 2 = one s_sleep (64 cycles); 3 / 4 = the same with the polls
                                           narrowed to the records that have not arrived yet */
+  FLAME_NLTGV2_OPT_PV_LEAN = 114       /* patch-per-wave form, the lean kernel for few patches per CU (k_persistent_pv_lean): 0 (default)
+                                          = wherever it applies, 1 = never (the general kernel), 2 = required: a run it does not
+                                          apply to fails with FLAME_NLTGV2_ERR_INVALID_ARG and nothing is run.  2 is for tests only:
+                                          it also lets runs of 1-3 iterations go persistent, which the planner otherwise never does
+                                          (under 0 and 1 such runs take the per-step path), and a replay of an expired chain, which
+                                          the lean kernel never runs, fails with the same error instead of going down the ladder */
 };
 
 #endif /* FLAME_NLTGV2_TEST_OPTIONS_H_ */

@@ -542,7 +542,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
     static std::once_flag warm;
     if (!std::getenv("FLAME_NLTGV2_NO_WARM"))
     std::call_once(warm, [ctx] {
-      warm_module_kernels(), warm_module_persistent(ctx->own_stream, cooperative_allowed()), warm_module_persistent_tv(), warm_module_persistent_pv2();
+      warm_module_kernels(), warm_module_persistent(ctx->own_stream, cooperative_allowed()), warm_module_persistent_tv(), warm_module_persistent_pv2(), warm_module_persistent_lean();
       warm_module_layout(), warm_module_topo();
     });
     if (!std::getenv("FLAME_NLTGV2_LAZY_CALIBRATION") && ctx->prop.multiProcessorCount >= 64 && place_calibrate_at_create(device) && place_calibrate(ctx) != 0) {
@@ -678,6 +678,10 @@ int flame_nltgv2_set_option(flame_nltgv2_ctx* ctx, int option, int value) {
     case FLAME_NLTGV2_OPT_PRESLEEP:
       if (value < 0 || value > 256) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
       ctx->opt_presleep = value;
+      return 0;
+    case FLAME_NLTGV2_OPT_PV_LEAN:
+      if (value < 0 || value > 2) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      ctx->opt_pv_lean = value;
       return 0;
     case FLAME_NLTGV2_OPT_MESH_STATE:
       if (value < 0 || value > 1) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);

@@ -175,6 +175,9 @@ struct flame_nltgv2_ctx {
   int opt_fault = 0;     // test hook: > 0 = the next persistent runs time out after this many spins
   int opt_presleep = 0;  // 0: auto (kPreSleep*); n > 0: (n - 1) x 64 cycles
   int opt_poll_gap = 0;  // patch-per-wave form: 0 = default (kPvPollGap), 1 = no sleep between polls, 2 = one s_sleep, 3 / 4 = the same, narrowed
+  int opt_pv_lean = 0;   // k_persistent_pv_lean: 0 = wherever it applies, 1 = never, 2 = required or the run fails
+  mutable int pv_lean_occ = 0;       // ... its patches really resident per CU for the current layout
+  mutable uint64_t pv_lean_occ_topo = ~0ull;
   mutable int pv_occ = 0;            // patches of k_persistent_pv the runtime keeps resident per CU for the current layout
   mutable uint64_t pv_occ_topo = ~0ull;
   int opt_probe = 0;     // > 0: k_persistent_pv records a per-patch, per-step cycle probe (flame_nltgv2_read_probe)

@@ -189,6 +189,11 @@ int pv2_patches_per_cu(int lcap, bool verify);
 int launch_persistent_pv2(const FusedArgs& a, const Pv2Args& w, const SolverParams& p, int wg_begin, int n_wgs, int parity_in, unsigned tag0,
                           int n_iters, unsigned max_spins, int poll_gap, int dual, const RunTail* tail, bool cooperative, hipStream_t stream);
 int pv_real_waves_per_simd(bool verify_or_probe);
+// k_persistent_pv_lean (nltgv2_persistent_lean.hip): the patch-per-wave kernel's instance for few patches per CU
+int pv_lean_real_waves_per_simd();
+int pv_lean_patches_per_cu(const FusedArgs& a);
+int launch_persistent_pv_lean(const FusedArgs& a, const SolverParams& p, int wave_begin, int n_waves, int parity_in, unsigned tag0, int n_iters,
+                              unsigned max_spins, int xcds, const RunTail* tail, bool cooperative, hipStream_t stream);
 const void* persistent_tv_kernel(int waves_per_block, unsigned* lds_bytes);  // nltgv2_persistent_tv.hip
 // device-side expansion of the layout arrays (nltgv2_layout.hip)
 int launch_build_sell(const CanonArgs& c, const FusedArgs& a, const int32_t* iperm, hipStream_t s);
@@ -267,6 +272,7 @@ void warm_module_kernels();
 void warm_module_persistent(hipStream_t stream, bool cooperative);
 void warm_module_persistent_tv();
 void warm_module_persistent_pv2();
+void warm_module_persistent_lean();
 void warm_module_layout();
 void warm_module_topo();
 

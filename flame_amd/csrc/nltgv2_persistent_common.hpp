@@ -1,6 +1,6 @@
 // nltgv2_persistent_common.hpp -- what the persistent kernels share, once: the patch rows' meta bits, the wait report, the open
 // run's stop decision, the vertex update, the record verification, the give-up epilogue and the write-back of a run's state.
-// Included by nltgv2_persistent.hip (k_persistent_pv), nltgv2_persistent_pv2.hip (k_persistent_pv2) and nltgv2_persistent_tv.hip
+// Included by nltgv2_persistent.hip (k_persistent_pv), nltgv2_persistent_lean.hip (k_persistent_pv_lean), nltgv2_persistent_pv2.hip (k_persistent_pv2) and nltgv2_persistent_tv.hip
 // (k_persistent_tv).  The protocol these pieces belong to is described at the top of nltgv2_persistent.hip; the step bodies (the
 // poll statements, the DPP accumulations, the dual updates, the two-step loops) are what differs and stay with their kernels.
 // Everything here is inlined: the compiler's scheduling of these kernels is sensitive to how code is factored, so a change is

@@ -50,11 +50,29 @@ bool cooperative_allowed() {
   return ok;
 }
 
+// Where the lean patch kernel (k_persistent_pv_lean, nltgv2_persistent_lean.hip) runs instead of k_persistent_pv: a run of the patch-per-wave form
+// as ONE launch of what would be the plain instance -- no probe, no verification, not an open run, not a replay, no fault injection -- with
+// the default poll gap and pre-sleep, the same-XCD exchange on, below the paced regime, every patch resident under ITS register counts,
+// and no vertex of more than 16 edges.  Everything else runs the general kernel exactly as before.  (FLAME_NLTGV2_OPT_PV_LEAN: 1 = never,
+// 2 = or the run fails.)
+static bool pv_lean_applies(const flame_nltgv2_ctx* ctx, int form, const std::vector<WaveGroup>& groups, bool open_run) {
+  if (form != 3 || groups.size() != 1 || ctx->opt_pv_lean == 1) return false;
+  if (ctx->opt_probe != 0 || ctx->opt_verify != 0 || open_run || ctx->replaying != 0 || ctx->opt_fault != 0) return false;
+  if (ctx->opt_poll_gap != 0 || ctx->opt_presleep != 0) return false;
+  const int cus = ctx->prop.multiProcessorCount, count = groups[0].count;
+  const bool dual_on = ctx->opt_dual == 2 || (ctx->opt_dual == 1 && count > kDualMinWavesPerCu * cus);
+  if (!dual_on || count > kPvPaceAbovePerCu * cus) return false;
+  if (ctx->L.max_degree > 16 || !ctx->L.wg_rowpack) return false;
+  if (ctx->pv_lean_occ_topo != ctx->topo) ctx->pv_lean_occ = pv_lean_patches_per_cu(ctx->f), ctx->pv_lean_occ_topo = ctx->topo;
+  return count <= ctx->pv_lean_occ * cus;
+}
+
 // `consume`: the call plans a run that is about to be enqueued (enqueue_run) -- only then does a planned-around run count against
 // the back-off after an expired wait; a query (persistent_eligible, prepare_run) leaves the bookkeeping alone.
 int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups, bool consume = false) {
   groups->clear();
-  if (!ctx->opt_persistent || n < 4 || n > (1 << 24) || !ctx->prop.cooperativeLaunch) return 0;
+  // (fewer than four steps are not worth a persistent launch -- unless the test option asks for the lean kernel or nothing)
+  if (!ctx->opt_persistent || n < (ctx->opt_pv_lean == 2 ? 1 : 4) || n > (1 << 24) || !ctx->prop.cooperativeLaunch) return 0;
   if (ctx->persist_refused_topo == ctx->topo || ctx->replaying == 2) return 0;
   const bool retry = ctx->replaying == 1;  // the first replay of an expired chain: persistent once more, with room left on every CU
   if (!retry && ctx->persist_backoff_topo == ctx->topo && (ctx->persist_backoff_left > 0 || ctx->opt_fault > 0)) {  // (the test hook's fault does not pass)
@@ -517,6 +535,8 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
     ctx->want_open = 0;
     return 0;
   }
+  const bool lean = pv_lean_applies(ctx, form, groups, open_run);
+  if (ctx->opt_pv_lean == 2 && !lean) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (test option: the lean kernel or nothing)
   if (form != 0) {
     // tags must stay unique: clear the record buffers long before the 28-bit tag of the XCC table wraps -- and when the
     // form changes (the forms lay the buffers out differently: one's XCC table is another's record area)
@@ -536,7 +556,7 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
     const uint32_t tag0 = ctx->tag_next + 2;
     // (topology, form, kernel instance): a new instance -- other registers, other LDS -- gets a cooperative first launch
     const uint64_t key = ctx->topo * 1024 + (uint64_t)form * 64 + (ctx->opt_verify != 0 ? 16 : 0) + (ctx->opt_probe != 0 ? 8 : 0) +
-                         (ctx->opt_dual == 2 ? 4 : ctx->opt_dual == 1 ? 2 : 0) + (ctx->opt_xcds > 0 ? 1 : 0);
+                         (ctx->opt_dual == 2 ? 4 : ctx->opt_dual == 1 ? 2 : 0) + (ctx->opt_xcds > 0 ? 1 : 0) + (lean ? 32 : 0);
     const RunTail* tail_dev = nullptr;
     {  // standing outputs: the small block the kernels read in their epilogue, (re)sent when no slot holds it
       RunTail want;
@@ -640,6 +660,12 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
         e = launch_persistent_pv2(ctx->f, ctx->pv2_args, to_sp(p), gr.begin, gr.count, ctx->parity, tag0, n, spins_arg, poll_gap, dual,
                                   tail_dev, cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
         ctx->f.open_run = 0;
+        if (e != 0) break;
+        continue;
+      }
+      if (lean) {  // (the same launch but for the kernel: placement, XCDs and the cooperative first launch as for the general one)
+        e = launch_persistent_pv_lean(ctx->f, to_sp(p), gr.begin, gr.count, ctx->parity, tag0, n, spins_arg, xcds, tail_dev,
+                                      cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
         if (e != 0) break;
         continue;
       }
