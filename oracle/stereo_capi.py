@@ -53,6 +53,9 @@ class FrameRef(C.Structure):
                 ("q_to_pf", C.c_float * 4), ("t_to_pf", C.c_float * 3)]
 
 
+# columns of the optional walk trace (stereo_oracle.c, line_match_walk); a row of -1 = the match was never reached
+TRACE_COLS = ("steps", "c_best", "c_second", "n_ties", "tie16", "second_eq_best", "subpixel", "match_rc")
+
 _READY = False
 
 
@@ -90,6 +93,16 @@ def lib():
                                                     C.POINTER(FrameRef), C.c_void_p, _FP, _FP, C.c_uint32, C.c_int,
                                                     C.c_void_p, C.POINTER(C.c_int32)]
         L.stereo_update_feature_idepths.restype = C.c_long
+        L.stereo_update_feature_idepths_traced.argtypes = L.stereo_update_feature_idepths.argtypes + [C.POINTER(C.c_int32)]
+        L.stereo_update_feature_idepths_traced.restype = C.c_long
+        L.stereo_trace_cols.argtypes = []
+        L.stereo_trace_cols.restype = C.c_int
+        assert L.stereo_trace_cols() == len(TRACE_COLS)
+        L.stereo_search_region.argtypes = [C.POINTER(Params), GP, C.c_int, C.c_int, f, f, f, f] + [_FP] * 6
+        L.stereo_search_region.restype = C.c_int
+        L.stereo_line_match.argtypes = [C.POINTER(Params), f, _FP, C.c_void_p, C.c_int, C.c_int, C.c_int, f, f, f, f,
+                                        _FP, _FP, _FP]
+        L.stereo_line_match.restype = C.c_int
         L.stereo_make_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, _FP, _FP]
         L.stereo_make_frame.restype = None
         _READY = True
@@ -196,9 +209,32 @@ def make_frame(img: np.ndarray, border: int):
     return pad, gx, gy
 
 
-def update_feature_idepths(params: Params, K, Kinv, width, height, pad, frames, new_frame, curr_pf_id, feats):
+def search_region(params: Params, g, width, height, ux, uy, mu, var):
+    """inverse_depth_filter::getSearchRegion: (rc, start.x, start.y, end.x, end.y, epi.x, epi.y); rc 1 = region found,
+    0 = none, -1 = reference assert.  The outputs are meaningful for rc == 1 only."""
+    v = [C.c_float() for _ in range(6)]
+    rc = lib().stereo_search_region(C.byref(params), C.byref(g), width, height, ux, uy, mu, var, *[C.byref(x) for x in v])
+    return (int(rc),) + tuple(np.float32(x.value) for x in v)
+
+
+def line_match(params: Params, rescale_factor, ref_patch, img_pad, sx, sy, ex, ey):
+    """line_stereo::match on a padded u8 image: (rc, match.x, match.y, residual); rc 0 success, 1 ambiguous, 2 max
+    cost, -1 reference assert.  match is meaningful for rc == 0 only."""
+    patch = _f32(ref_patch, 5)
+    img = np.ascontiguousarray(img_pad, dtype=np.uint8)
+    rows, cols = img.shape
+    mx, my, res = C.c_float(), C.c_float(), C.c_float()
+    rc = lib().stereo_line_match(C.byref(params), rescale_factor, _fp(patch), img.ctypes.data, rows, cols, cols, sx, sy,
+                                 ex, ey, C.byref(mx), C.byref(my), C.byref(res))
+    return int(rc), np.float32(mx.value), np.float32(my.value), np.float32(res.value)
+
+
+def update_feature_idepths(params: Params, K, Kinv, width, height, pad, frames, new_frame, curr_pf_id, feats, trace=None):
     """frames: list of dicts {id, img_pad, q_to_new, t_to_new, q_to_pf, t_to_pf}; new_frame = (img_pad, gradx_pad,
-    grady_pad).  `feats` (FEATURE_DTYPE) is updated in place.  Returns (rc, stats[7])."""
+    grady_pad).  `feats` (FEATURE_DTYPE) is updated in place.  `trace`: None, or a C-contiguous int32 [n, 8] array that
+    receives one row of TRACE_COLS per feature (outputs are the same bits either way).  Returns (rc, stats[7])."""
+    if trace is not None:
+        assert trace.dtype == np.int32 and trace.flags.c_contiguous and trace.shape == (feats.shape[0], len(TRACE_COLS))
     assert feats.dtype == FEATURE_DTYPE and feats.flags.c_contiguous
     K, Kinv = _f32(K, 9), _f32(Kinv, 9)
     arr = (FrameRef * len(frames))()
@@ -216,7 +252,10 @@ def update_feature_idepths(params: Params, K, Kinv, width, height, pad, frames, 
     ip, gx, gy = (np.ascontiguousarray(new_frame[0], np.uint8), np.ascontiguousarray(new_frame[1], np.float32),
                   np.ascontiguousarray(new_frame[2], np.float32))
     stats = (C.c_int32 * 7)()
-    rc = lib().stereo_update_feature_idepths(C.byref(params), _fp(K), _fp(Kinv), width, height, pad, len(frames), arr,
-                                             ip.ctypes.data, _fp(gx), _fp(gy), int(curr_pf_id), feats.shape[0],
-                                             feats.ctypes.data, stats)
+    args = (C.byref(params), _fp(K), _fp(Kinv), width, height, pad, len(frames), arr, ip.ctypes.data, _fp(gx), _fp(gy),
+            int(curr_pf_id), feats.shape[0], feats.ctypes.data, stats)
+    if trace is None:
+        rc = lib().stereo_update_feature_idepths(*args)
+    else:
+        rc = lib().stereo_update_feature_idepths_traced(*args, trace.ctypes.data_as(C.POINTER(C.c_int32)))
     return int(rc), np.array(list(stats), dtype=np.int32)

@@ -398,10 +398,25 @@ int stereo_search_region(const stereo_params* P, const stereo_geometry* g, int w
   return 1;
 }
 
-/* line_stereo.h:73-385.  Returns 0 success, 1 ambiguous, 2 max cost, -1 reference assert (sample outside image). */
-int stereo_line_match(const stereo_params* P, float rescale_factor, const float* ref_patch, const uint8_t* img,
-                      int rows, int cols, int step, float sx, float sy, float ex, float ey, float* mx, float* my,
-                      float* residual) {
+/* ---- walk trace (optional, off unless a caller passes rows to stereo_update_feature_idepths_traced) ------------
+ * One row of STEREO_TRACE_COLS int32 per feature, written by the sequential walk below and by nothing else; it
+ * classifies what a walk went through (for the tests' coverage counts) and changes no output.
+ *   [0] steps walked            (-1 in every column: the feature never reached the match)
+ *   [1] cBest   [2] cSecond     (as the walk left them; -1 = none)
+ *   [3] how many other steps cost exactly the final best (they all come after it: the best is the first minimum)
+ *   [4] 1 when one of those lies a multiple of 16 steps after the best
+ *   [5] 1 when second_err == best_err
+ *   [6] sub-pixel branch: 0 none, 1 pre, 2 post
+ *   [7] the match's return value (0 success, 1 ambiguous, 2 max cost, -1 reference assert) */
+#define STEREO_TRACE_COLS 8
+int stereo_trace_cols(void) { return STEREO_TRACE_COLS; }
+
+/* line_stereo.h:73-385.  Returns 0 success, 1 ambiguous, 2 max cost, -1 reference assert (sample outside image).
+ * `tr`: trace row or NULL. */
+static int line_match_walk(const stereo_params* P, float rescale_factor, const float* ref_patch, const uint8_t* img,
+                           int rows, int cols, int step, float sx, float sy, float ex, float ey, float* mx, float* my,
+                           float* residual, int32_t* tr) {
+  int n_ties = 0, tie16 = 0;
   const float rm2 = ref_patch[0], rm1 = ref_patch[1], r0 = ref_patch[2], rp1 = ref_patch[3], rp2 = ref_patch[4];
   float incx = ex - sx, incy = ey - sy;
   const float epl = sqrtf(incx * incx + incy * incy);
@@ -436,6 +451,10 @@ int stereo_line_match(const stereo_params* P, float rescale_factor, const float*
     e[2] = v0 - r0, ee += e[2] * e[2];
     e[3] = vm1 - rm1, ee += e[3] * e[3];
     e[4] = vm2 - rm2, ee += e[4] * e[4];
+    if (tr) {
+      if (ee < best_err) n_ties = 0, tie16 = 0;
+      else if (ee == best_err) ++n_ties, tie16 |= ((loop - cBest) % 16 == 0);
+    }
     if (ee < best_err) {
       second_err = best_err;
       cSecond = cBest;
@@ -464,6 +483,7 @@ int stereo_line_match(const stereo_params* P, float rescale_factor, const float*
     ++loop;
   }
 #undef SAMPLE
+  if (tr) tr[0] = loop, tr[1] = cBest, tr[2] = cSecond, tr[3] = n_ties, tr[4] = tie16, tr[5] = (second_err == best_err);
   *residual = best_err;
   if (best_err > 4.0f * P->max_cost) return 2;
   {
@@ -485,6 +505,7 @@ int stereo_line_match(const stereo_params* P, float rescale_factor, const float*
     } else if ((gPost_post < 0) ^ (gPost_this < 0)) {
       interpPost = 1;
     }
+    if (tr) tr[6] = interpPre ? 1 : interpPost ? 2 : 0;
     if (interpPre) {
       const float d = gPre_this / (gPre_this - gPre_pre);
       best_x -= d * incx;
@@ -513,10 +534,28 @@ int stereo_line_match(const stereo_params* P, float rescale_factor, const float*
   return 0;
 }
 
+static int line_match_traced(const stereo_params* P, float rescale_factor, const float* ref_patch, const uint8_t* img,
+                             int rows, int cols, int step, float sx, float sy, float ex, float ey, float* mx, float* my,
+                             float* residual, int32_t* tr) {
+  if (tr) {
+    for (int k = 0; k < STEREO_TRACE_COLS; ++k) tr[k] = 0;
+    tr[1] = tr[2] = -1;
+  }
+  const int r = line_match_walk(P, rescale_factor, ref_patch, img, rows, cols, step, sx, sy, ex, ey, mx, my, residual, tr);
+  if (tr) tr[7] = r;
+  return r;
+}
+
+int stereo_line_match(const stereo_params* P, float rescale_factor, const float* ref_patch, const uint8_t* img,
+                      int rows, int cols, int step, float sx, float sy, float ex, float ey, float* mx, float* my,
+                      float* residual) {
+  return line_match_traced(P, rescale_factor, ref_patch, img, rows, cols, step, sx, sy, ex, ey, mx, my, residual, 0);
+}
+
 /* inverse_depth_filter.cc:178-263.  Status 0..3, or -1 on a reference assert.  u_* in padded coordinates. */
-int stereo_search(const stereo_params* P, const stereo_geometry* g, float rescale_factor, const uint8_t* img_ref,
-                  const uint8_t* img_cmp, int rows, int cols, int step, float ux, float uy, float sx, float sy,
-                  float ex, float ey, float* mx, float* my) {
+static int search_traced(const stereo_params* P, const stereo_geometry* g, float rescale_factor, const uint8_t* img_ref,
+                         const uint8_t* img_cmp, int rows, int cols, int step, float ux, float uy, float sx, float sy,
+                         float ex, float ey, float* mx, float* my, int32_t* tr) {
   float rx, ry;
   if (stereo_reference_epiline(g, ux, uy, &rx, &ry)) return -1;
   if (P->win_size != 5) return -1;
@@ -537,11 +576,17 @@ int stereo_search(const stereo_params* P, const stereo_geometry* g, float rescal
   }
   if (gmax < P->min_grad_mag) return 1;
   float residual = 3.402823466e+38f;
-  const int r = stereo_line_match(P, rescale_factor, patch, img_cmp, rows, cols, step, sx, sy, ex, ey, mx, my, &residual);
+  const int r = line_match_traced(P, rescale_factor, patch, img_cmp, rows, cols, step, sx, sy, ex, ey, mx, my, &residual, tr);
   if (r < 0) return -1;
   if (r == 1) return 2;
   if (r == 2) return 3;
   return 0;
+}
+
+int stereo_search(const stereo_params* P, const stereo_geometry* g, float rescale_factor, const uint8_t* img_ref,
+                  const uint8_t* img_cmp, int rows, int cols, int step, float ux, float uy, float sx, float sy,
+                  float ex, float ey, float* mx, float* my) {
+  return search_traced(P, g, rescale_factor, img_ref, img_cmp, rows, cols, step, ux, uy, sx, sy, ex, ey, mx, my, 0);
 }
 
 /* inverse_depth_filter.cc:265-303; 1 = fused, 0 = rejected */
@@ -621,7 +666,7 @@ typedef struct stereo_frame_ref {
 /* flame.cc:1538-1752.  1 tracked, 0 not, -1 reference assert */
 static int track_feature(const stereo_params* P, const float* K, const float* Kinv, const stereo_frame_ref* fr,
                          const stereo_geometry* epigeo, int width, int height, int pad, const uint8_t* new_img_pad,
-                         uint32_t curr_pf_id, stereo_feature* f, float* flow_x, float* flow_y) {
+                         uint32_t curr_pf_id, stereo_feature* f, float* flow_x, float* flow_y, int32_t* tr) {
   float ucx, ucy, idepth_cmp, var_cmp;
   const int pr = stereo_predict(epigeo, P->process_var_factor, f->x, f->y, f->idepth_mu, f->idepth_var, &ucx, &ucy,
                                 &idepth_cmp, &var_cmp);
@@ -665,8 +710,8 @@ static int track_feature(const stereo_params* P, const float* K, const float* Ki
   if (!rect_contains(vx, vy, vw, vh, f->x, f->y)) return 0;
   float mx = ucx, my = ucy;
   const int rows = height + 2 * pad, cols = width + 2 * pad;
-  const int st = stereo_search(P, epigeo, rescale, fr->img_pad, new_img_pad, rows, cols, cols, f->x + off, f->y + off,
-                               sx + off, sy + off, ex + off, ey + off, &mx, &my);
+  const int st = search_traced(P, epigeo, rescale, fr->img_pad, new_img_pad, rows, cols, cols, f->x + off, f->y + off,
+                               sx + off, sy + off, ex + off, ey + off, &mx, &my, tr);
   if (st < 0) return -1;
   f->search_status = st;
   if (st != 0) return 0;
@@ -690,12 +735,17 @@ static void fail_feature(const stereo_params* P, stereo_feature* f, int32_t* sta
 /* flame.cc:1280-1536.  stats[0..5] = num_idepth_updates, num_fail_max_var, num_fail_max_dropouts,
  * num_fail_ref_patch_grad, num_fail_ambiguous_match, num_fail_max_cost; stats[6] = the function's bool.
  * Returns 0, -(1 + i) when feature i hits a reference assert, or 1 + i when its frame id is unknown
- * (pfs.at() would throw). */
-long stereo_update_feature_idepths(const stereo_params* P, const float* K, const float* Kinv, int width, int height,
-                                   int pad, int n_frames, const stereo_frame_ref* frames, const uint8_t* new_img_pad,
-                                   const float* new_gradx_pad, const float* new_grady_pad, uint32_t curr_pf_id, int n,
-                                   stereo_feature* feats, int32_t* stats) {
+ * (pfs.at() would throw).
+ * `trace`: NULL, or n rows of STEREO_TRACE_COLS int32 (see line_match_walk); every row is written, also those of
+ * the features behind an early return. */
+long stereo_update_feature_idepths_traced(const stereo_params* P, const float* K, const float* Kinv, int width,
+                                          int height, int pad, int n_frames, const stereo_frame_ref* frames,
+                                          const uint8_t* new_img_pad, const float* new_gradx_pad,
+                                          const float* new_grady_pad, uint32_t curr_pf_id, int n, stereo_feature* feats,
+                                          int32_t* stats, int32_t* trace) {
   for (int k = 0; k < 7; ++k) stats[k] = 0;
+  if (trace)
+    for (long k = 0; k < (long)n * STEREO_TRACE_COLS; ++k) trace[k] = -1;
   const int rows = height + 2 * pad, cols = width + 2 * pad;
   for (int i = 0; i < n; ++i) {
     stereo_feature* f = &feats[i];
@@ -712,7 +762,8 @@ long stereo_update_feature_idepths(const stereo_params* P, const float* K, const
     const float baseline = sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
     if (baseline < P->min_baseline) continue;
     float flow_x = 0, flow_y = 0;
-    const int tr = track_feature(P, K, Kinv, fr, &epigeo, width, height, pad, new_img_pad, curr_pf_id, f, &flow_x, &flow_y);
+    const int tr = track_feature(P, K, Kinv, fr, &epigeo, width, height, pad, new_img_pad, curr_pf_id, f, &flow_x, &flow_y,
+                                 trace ? trace + (long)i * STEREO_TRACE_COLS : 0);
     if (tr < 0) return -(1 + (long)i);
     if (f->search_status == 1) ++stats[3];
     else if (f->search_status == 2) ++stats[4];
@@ -748,6 +799,14 @@ long stereo_update_feature_idepths(const stereo_params* P, const float* K, const
     stats[6] = 1;
   }
   return 0;
+}
+
+long stereo_update_feature_idepths(const stereo_params* P, const float* K, const float* Kinv, int width, int height,
+                                   int pad, int n_frames, const stereo_frame_ref* frames, const uint8_t* new_img_pad,
+                                   const float* new_gradx_pad, const float* new_grady_pad, uint32_t curr_pf_id, int n,
+                                   stereo_feature* feats, int32_t* stats) {
+  return stereo_update_feature_idepths_traced(P, K, Kinv, width, height, pad, n_frames, frames, new_img_pad, new_gradx_pad,
+                                              new_grady_pad, curr_pf_id, n, feats, stats, 0);
 }
 
 /* utils::Frame::create, level 0 (frame.cc:33-71): padded image (BORDER_REFLECT_101) and padded central
