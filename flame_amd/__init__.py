@@ -13,6 +13,7 @@ from .regularizer import (  # noqa: F401
     NLTGV2Error,
     Params,
     Regularizer,
+    WireframeParams,
     delaunay,
     library_path,
     load_library,

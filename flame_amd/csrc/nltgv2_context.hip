@@ -521,6 +521,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   ok = ok && hipEventCreateWithFlags(&ctx->ev_topo_ready, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreate(&ctx->ev_mesh0) == hipSuccess && hipEventCreate(&ctx->ev_mesh1) == hipSuccess;
   ok = ok && hipEventCreate(&ctx->ev_dbg0) == hipSuccess && hipEventCreate(&ctx->ev_dbg1) == hipSuccess;
+  ok = ok && hipEventCreate(&ctx->ev_wire0) == hipSuccess && hipEventCreate(&ctx->ev_wire1) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_expanded, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[0], hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[1], hipEventDisableTiming) == hipSuccess;
@@ -569,6 +570,8 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
                     &ctx->m_incident, &ctx->m_keys, &ctx->m_img, &ctx->m_cov})
     ctx->all.push_back(b);
   for (DevBuf* b : {&ctx->d_gray, &ctx->d_idimg, &ctx->d_nimg, &ctx->d_w1map, &ctx->d_w2map, &ctx->d_keys, &ctx->d_cov}) ctx->all.push_back(b);
+  for (DevBuf* b : {&ctx->w_draws, &ctx->w_cnt, &ctx->w_off, &ctx->w_fill, &ctx->w_entries, &ctx->w_counts, &ctx->w_img, &ctx->w_gray, &ctx->w_tvalid})
+    ctx->all.push_back(b);
   ctx->all.push_back(&ctx->stop_dev);
   ctx->all.push_back(&ctx->place_patch_nx), ctx->all.push_back(&ctx->place_fill_nx);
   for (auto& b : ctx->sp_v) ctx->all.push_back(&b);
@@ -610,6 +613,9 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
   if (ctx->h_dbg) (void)hipHostFree(ctx->h_dbg);
   if (ctx->ev_dbg0) (void)hipEventDestroy(ctx->ev_dbg0);
   if (ctx->ev_dbg1) (void)hipEventDestroy(ctx->ev_dbg1);
+  if (ctx->h_wire) (void)hipHostFree(ctx->h_wire);
+  if (ctx->ev_wire0) (void)hipEventDestroy(ctx->ev_wire0);
+  if (ctx->ev_wire1) (void)hipEventDestroy(ctx->ev_wire1);
   if (ctx->h_dims) (void)hipHostFree(ctx->h_dims);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -340,6 +340,25 @@ struct flame_nltgv2_ctx {
     size_t off_nimg = 0, off_w1 = 0, off_w2 = 0, off_gray = 0;  // byte offsets in h_dbg (idepth image at 0)
   } debug_pending;
   hipEvent_t ev_dbg0 = nullptr, ev_dbg1 = nullptr;
+  // flame_nltgv2_debug_wireframe_begin / _end (wireframe_kernels.hip): buffers, pinned outputs, pending record and timing events of
+  // its own.  tvalid_*: for which upload into r_tris (tris_gen), how many triangles and which topology the last mesh_outputs_begin
+  // wrote m_tvalid (validity == 2).  w_cap: entries w_entries holds; w_last_total: the entries of the last finished call.
+  bool tvalid_have = false;
+  uint64_t tvalid_gen = 0, tvalid_topo = 0;
+  int32_t tvalid_T = -1;
+  DevBuf w_draws, w_cnt, w_off, w_fill, w_entries, w_counts, w_img, w_gray, w_tvalid;
+  size_t w_cap = 0, w_last_total = 0;
+  char* h_wire = nullptr;             // pinned: the picture | the counters | staging of a host grey image
+  size_t h_wire_cap = 0;
+  struct WirePending {
+    bool active = false;
+    int rows = 0, cols = 0, flip = 0, gray_step = 0;
+    int32_t T = 0;
+    float scene_color_scale = 1.0f;
+    const uint8_t* gray = nullptr;    // device memory: what fill + fold read if _end has to repeat them
+    size_t off_counts = 0, off_gray = 0;  // byte offsets in h_wire (the picture at 0)
+  } wire_pending;
+  hipEvent_t ev_wire0 = nullptr, ev_wire1 = nullptr;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

@@ -6,6 +6,7 @@
 #include "debug_kernels.h"
 #include "mesh_kernels.h"
 #include "nltgv2_context.hpp"
+#include "wireframe_kernels.h"
 
 // Which state a mesh stage on the side stream describes (interpolate_mesh_begin, mesh_outputs_begin), and the wait that lets `rs` read
 // it in the canonical arrays.  FLAME_NLTGV2_OPT_MESH_STATE = 1 and runs enqueued since the last settle: the state that settle left,
@@ -293,6 +294,7 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
   mb.P = (float4*)ctx->m_P.p, mb.vtx_idepth = (float*)ctx->m_idepth.p, mb.normals = (float*)ctx->m_normals.p;
   mb.tri_valid = (uint8_t*)ctx->m_tvalid.p, mb.n_valid = (int*)ctx->m_nvalid.p, mb.tri_normal = (float4*)ctx->m_tnormal.p;
   mb.offset = (int*)ctx->m_offset.p, mb.cursor = (int*)ctx->m_cursor.p, mb.incident = (int32_t*)ctx->m_incident.p;
+  ctx->tvalid_have = true, ctx->tvalid_gen = ctx->tris_gen, ctx->tvalid_T = T, ctx->tvalid_topo = ctx->topo;  // (flame_nltgv2_debug_wireframe_begin, validity == 2)
   rc = mesh_state_on(ctx, rs);
   if (rc) return rc;
   HIPCHK(ctx, hipEventRecord(ctx->ev_mesh0, rs));
@@ -490,6 +492,168 @@ int flame_nltgv2_debug_images(flame_nltgv2_ctx* ctx, const uint8_t* img_host, co
   if (normals_img_out && v.normals_img) std::memcpy(normals_img_out, v.normals_img, 3 * n);
   if (w1_map_out && v.w1_map) std::memcpy(w1_map_out, v.w1_map, sizeof(float) * n);
   if (w2_map_out && v.w2_map) std::memcpy(w2_map_out, v.w2_map, sizeof(float) * n);
+  return FLAME_NLTGV2_OK;
+}
+
+void flame_nltgv2_default_wireframe_params(flame_nltgv2_wireframe_params* p) {
+  if (!p) return;
+  p->scene_color_scale = 1.0f;  // params.h:109
+  p->flip = 0;
+  p->validity = 0;
+}
+
+// fill + fold + the picture's way out, on the side stream: the second half of a wireframe call, which _end repeats with a larger
+// entry buffer where the entries did not fit
+static int wireframe_second_half(flame_nltgv2_ctx* ctx, const flame_nltgv2_ctx::WirePending& wp) {
+  flame_hip::WireBuffers wb;
+  wb.draws = (flame_hip::WireDraw*)ctx->w_draws.p, wb.cnt = (uint32_t*)ctx->w_cnt.p, wb.offset = (uint32_t*)ctx->w_off.p;
+  wb.fill = (uint32_t*)ctx->w_fill.p, wb.entries = (uint64_t*)ctx->w_entries.p, wb.capacity = (uint32_t)ctx->w_cap;
+  wb.counts = (int*)ctx->w_counts.p;
+  flame_hip::WireImageArgs a;
+  a.rows = wp.rows, a.cols = wp.cols, a.gray = wp.gray, a.gray_step = wp.gray_step;
+  a.scene_color_scale = wp.scene_color_scale, a.flip = wp.flip;
+  hipStream_t rs = ctx->raster_stream;
+  LAUNCHCHK(ctx, flame_hip::launch_wireframe_paint(wp.T, wb, a, (uint8_t*)ctx->w_img.p, rs));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_wire, ctx->w_img.p, 3 * (size_t)wp.rows * (size_t)wp.cols, hipMemcpyDeviceToHost, rs));
+  return FLAME_NLTGV2_OK;
+}
+
+// The wireframe image on the side stream (see flame_nltgv2.h).  Like debug_images_begin: everything is checked before the stream or a
+// buffer is touched, so an error leaves what an earlier begin put into the pinned outputs, and its pending _end, as they are.
+int flame_nltgv2_debug_wireframe_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
+                                       const uint8_t* tri_valid, const flame_nltgv2_wireframe_params* params, int rows, int cols,
+                                       float graph_scale) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_debug_wireframe_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  if (rows <= 0 || cols <= 0 || rows > 32767 || cols > 32767) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (int16 endpoints)
+  if (ctx->tris_T < 0 || ctx->tris_topo != ctx->topo) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if ((img_host != nullptr) == (img_device != nullptr) || step_bytes < cols || !params) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (params->validity < 0 || params->validity > 2 || (tri_valid != nullptr) != (params->validity == 1)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t T = ctx->tris_T;
+  if (params->validity == 2 && !(ctx->tvalid_have && ctx->tvalid_gen == ctx->tris_gen && ctx->tvalid_T == T && ctx->tvalid_topo == ctx->topo))
+    return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  // every draw visits at most max(rows, cols) pixels: the entries, their offsets and the draw ids are 32-bit
+  if ((uint64_t)3 * (uint64_t)T * (uint64_t)(rows > cols ? rows : cols) >= (1ull << 31)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const size_t n = (size_t)rows * (size_t)cols;
+  hipStream_t rs = ctx->raster_stream;
+  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned outputs and the device buffers are about to be reused)
+  // pinned: the picture | the counters | the grey image on its way up
+  flame_nltgv2_ctx::WirePending wp;
+  auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+  wp.rows = rows, wp.cols = cols, wp.flip = params->flip != 0, wp.T = T, wp.scene_color_scale = params->scene_color_scale;
+  wp.off_counts = up16(3 * n);
+  wp.off_gray = wp.off_counts + 16;
+  const size_t h_bytes = wp.off_gray + up16(img_host ? n : 0) + 16;
+  if (ctx->h_wire_cap < h_bytes) {
+    request_open_stop(ctx);  // (the pinned allocator waits for the device)
+    void* h = nullptr;
+    if (hipHostMalloc(&h, h_bytes + h_bytes / 2, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
+    }
+    if (ctx->h_wire) (void)hipHostFree(ctx->h_wire);
+    ctx->h_wire = (char*)h, ctx->h_wire_cap = h_bytes + h_bytes / 2;
+    ctx->wire_pending.active = false;
+  }
+  size_t want = 2 * n, grown = ctx->w_last_total + ctx->w_last_total / 4 + 1;
+  if (grown > want) want = grown;
+  if (want < ctx->w_cap) want = ctx->w_cap;  // (never shrinks)
+  if (want > 0xffffffffull) want = 0xffffffffull;
+  rc = ensure(ctx, ctx->w_draws, sizeof(flame_hip::WireDraw) * 3 * (size_t)T);
+  if (!rc) rc = ensure(ctx, ctx->w_cnt, sizeof(uint32_t) * n);
+  if (!rc) rc = ensure(ctx, ctx->w_off, sizeof(uint32_t) * n);
+  if (!rc) rc = ensure(ctx, ctx->w_fill, sizeof(uint32_t) * n);
+  if (!rc) rc = ensure(ctx, ctx->w_entries, sizeof(uint64_t) * want);
+  if (!rc) rc = ensure(ctx, ctx->w_counts, flame_hip::kWireCounts * sizeof(int));
+  if (!rc) rc = ensure(ctx, ctx->w_img, 3 * n + 16);
+  if (!rc && img_host) rc = ensure(ctx, ctx->w_gray, n + 16);
+  if (!rc && tri_valid) rc = ensure(ctx, ctx->w_tvalid, (size_t)T + 16);
+  if (rc) return rc;
+  ctx->w_cap = want;
+  ctx->wire_pending.active = false;  // (from here on the pinned outputs are being rewritten)
+  char* h = ctx->h_wire;
+  wp.gray = (const uint8_t*)img_device, wp.gray_step = step_bytes;
+  if (img_host) {  // through pinned memory, rows packed: the caller's buffer is free again when this returns
+    for (int r = 0; r < rows; ++r) std::memcpy(h + wp.off_gray + (size_t)r * cols, img_host + (size_t)r * step_bytes, (size_t)cols);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->w_gray.p, h + wp.off_gray, n, hipMemcpyHostToDevice, rs));
+    wp.gray = (const uint8_t*)ctx->w_gray.p, wp.gray_step = cols;
+  }
+  const uint8_t* d_tv = nullptr;
+  if (params->validity == 1 && T > 0) {  // (pageable memory: the copy holds the host until the bytes have left the caller's array)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->w_tvalid.p, tri_valid, (size_t)T, hipMemcpyHostToDevice, rs));
+    d_tv = (const uint8_t*)ctx->w_tvalid.p;
+  } else if (params->validity == 2) {
+    d_tv = (const uint8_t*)ctx->m_tvalid.p;
+  }
+  rc = mesh_state_on(ctx, rs);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_wire0, rs));
+  flame_hip::WireBuffers wb;
+  wb.draws = (flame_hip::WireDraw*)ctx->w_draws.p, wb.cnt = (uint32_t*)ctx->w_cnt.p, wb.offset = (uint32_t*)ctx->w_off.p;
+  wb.fill = (uint32_t*)ctx->w_fill.p, wb.entries = (uint64_t*)ctx->w_entries.p, wb.capacity = (uint32_t)ctx->w_cap;
+  wb.counts = (int*)ctx->w_counts.p;
+  // the setup kernel is the last reader of the canonical pos / x (see interpolate_mesh_begin): ev_raster_done goes right behind it
+  LAUNCHCHK(ctx, flame_hip::launch_wireframe_lists(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.x, graph_scale, d_tv, wb, rows, cols,
+                                                   ctx->ev_raster_done, rs));
+  ctx->raster_inflight = true;
+  HIPCHK(ctx, hipMemcpyAsync(h + wp.off_counts, ctx->w_counts.p, flame_hip::kWireCounts * sizeof(int), hipMemcpyDeviceToHost, rs));
+  rc = wireframe_second_half(ctx, wp);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_wire1, rs));
+  wp.active = true;
+  ctx->wire_pending = wp;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_debug_wireframe_end(flame_nltgv2_ctx* ctx, flame_nltgv2_wireframe_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_debug_wireframe_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::WirePending wp = ctx->wire_pending;
+  if (!out || !ctx->h_wire || !wp.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  int32_t counts[flame_hip::kWireCounts];
+  std::memcpy(counts, ctx->h_wire + wp.off_counts, sizeof(counts));
+  const size_t total = (size_t)(uint32_t)counts[flame_hip::kWireTotal];
+  out->device_ms = 0.0f;
+  if (hipEventElapsedTime(&out->device_ms, ctx->ev_wire0, ctx->ev_wire1) != hipSuccess) (void)hipGetLastError(), out->device_ms = 0.0f;
+  out->refilled = 0;
+  if (total > ctx->w_cap) {  // the entries did not fit: a larger buffer, then fill and fold once more (the records, cnt and offsets stand)
+    const size_t want = total + total / 4 + 1;
+    rc = ensure(ctx, ctx->w_entries, sizeof(uint64_t) * want);
+    if (rc) return rc;
+    ctx->w_cap = want;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_wire0, ctx->raster_stream));
+    rc = wireframe_second_half(ctx, wp);
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_wire1, ctx->raster_stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+    float again = 0.0f;
+    if (hipEventElapsedTime(&again, ctx->ev_wire0, ctx->ev_wire1) != hipSuccess) (void)hipGetLastError(), again = 0.0f;
+    out->device_ms += again;
+    out->refilled = 1;
+  }
+  ctx->w_last_total = total;
+  out->rows = wp.rows, out->cols = wp.cols;
+  out->wireframe_img = (const uint8_t*)ctx->h_wire;
+  out->lines_drawn = counts[flame_hip::kWireDrawn], out->lines_skipped = counts[flame_hip::kWireSkipped];
+  out->entries = (int64_t)total;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_debug_wireframe(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
+                                 const uint8_t* tri_valid, const flame_nltgv2_wireframe_params* params, int rows, int cols,
+                                 float graph_scale, uint8_t* wireframe_img_out, int32_t* lines_drawn_out, int32_t* lines_skipped_out) {
+  int rc = flame_nltgv2_debug_wireframe_begin(ctx, img_host, img_device, step_bytes, tri_valid, params, rows, cols, graph_scale);
+  if (rc) return rc;
+  flame_nltgv2_wireframe_view v;
+  rc = flame_nltgv2_debug_wireframe_end(ctx, &v);
+  if (rc) return rc;
+  if (wireframe_img_out) std::memcpy(wireframe_img_out, v.wireframe_img, 3 * (size_t)v.rows * (size_t)v.cols);
+  if (lines_drawn_out) *lines_drawn_out = v.lines_drawn;
+  if (lines_skipped_out) *lines_skipped_out = v.lines_skipped;
   return FLAME_NLTGV2_OK;
 }
 

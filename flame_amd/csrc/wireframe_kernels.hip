@@ -1,0 +1,230 @@
+// wireframe_kernels.hip -- getDebugImageWireframe from what the pipeline leaves on the device:
+//   drawWireframe                flame.cc:2414-2457
+//   drawColorMappedWireframe     utils/image_utils.h:693-719
+//   applyColorMapLine            utils/visualization.h:235-260
+// The reference draws sequentially: triangle by triangle, three lines each, pixel by pixel along cv::LineIterator, and every pixel
+// it visits becomes the mean of the line's colour and what the pixel held.  A pixel's final value is a fold over the draws that
+// touched it, in draw order.  Here (include/flame_nltgv2.h states the rule in full; tests/wireframe_ref.py restates it):
+//   setup     one lane per line: endpoints rounded, validity and the outside rule applied -> a 16-byte draw record (the only
+//             reader of pos / x / tri_valid)
+//   count     one lane per draw walks its line: cnt[pixel] += 1
+//   offsets   every touched pixel takes a range of cnt[pixel] entries from one cursor, 1024 pixels of a wave at a time (placement is
+//             not deterministic and need not be: the fold orders by id)
+//   fill      one lane per draw walks again: (id << 32 | colour) into the pixel's range
+//   fold      per OUTPUT pixel, four per thread: the grey value, then the entries in increasing id, (c + v) >> 1 per channel
+// The fold takes the entries in order by selection (the smallest id above the last one taken) instead of sorting a copy: no
+// scratch memory, any list length, and a list of one or two entries -- nearly all of them -- costs one or four reads.
+// Built with -ffp-contract=off like the rest of the library: val = A + ii * slope0 is a product and a sum.
+#include <hip/hip_runtime.h>
+
+#include "debug_pixel.hpp"
+#include "wireframe_kernels.h"
+
+namespace flame_hip {
+namespace {
+
+// cvRound of an endpoint coordinate and whether it lies in [0, hi]: a NaN, an infinity and anything that rounds outside fail.
+__device__ __forceinline__ bool round_inside(float v, int hi, int* out) {
+  const float r = rintf(v);  // round half to even, as __float2int_rn; compared as a float first: no cast of a huge value
+  if (!(r >= 0.0f && r <= (float)hi)) return false;
+  *out = (int)r;
+  return true;
+}
+
+__global__ void __launch_bounds__(256)
+k_wire_setup(int n_draws, const int32_t* __restrict__ tris, const float2* __restrict__ vtx, const float* __restrict__ x,
+             float value_scale, const uint8_t* __restrict__ tri_valid, int rows, int cols, WireDraw* __restrict__ draws,
+             int* __restrict__ counts) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool valid = false, drawn = false;
+  if (i < n_draws) {
+    const int t = i / 3, k = i - 3 * t;
+    valid = tri_valid ? tri_valid[t] != 0 : true;
+    WireDraw d;
+    d.x1 = -1, d.y1 = d.x2 = d.y2 = 0, d.a_val = d.b_val = 0.0f;
+    if (valid) {
+      const int va = tris[3 * t + (k == 1 ? 1 : 0)], vb = tris[3 * t + (k == 0 ? 1 : 2)];  // v0 -> v1, v1 -> v2, v0 -> v2
+      const float2 pa = vtx[va], pb = vtx[vb];
+      int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+      const bool in_a = round_inside(pa.x, cols - 1, &x1) && round_inside(pa.y, rows - 1, &y1);
+      drawn = in_a && round_inside(pb.x, cols - 1, &x2) && round_inside(pb.y, rows - 1, &y2);
+      if (drawn) {
+        d.x1 = (int16_t)x1, d.y1 = (int16_t)y1, d.x2 = (int16_t)x2, d.y2 = (int16_t)y2;
+        d.a_val = x[va] * value_scale, d.b_val = x[vb] * value_scale;
+      }
+    }
+    draws[i] = d;
+  }
+  const int n_drawn = __popcll(__ballot(drawn)), n_skipped = __popcll(__ballot(valid && !drawn));
+  if ((threadIdx.x & 63) == 0) {
+    if (n_drawn) atomicAdd(&counts[kWireDrawn], n_drawn);
+    if (n_skipped) atomicAdd(&counts[kWireSkipped], n_skipped);
+  }
+}
+
+// cv::LineIterator (OpenCV 3.2, connectivity 8) from (x1, y1) to (x2, y2), restated (UNPINNED): f(ii, count, x, y) for each of
+// its count = max(|dx|, |dy|) + 1 pixels.  Every pixel lies in the endpoints' bounding box.
+template <class F>
+__device__ __forceinline__ void walk_line(const WireDraw& d, F f) {
+  int x = d.x1, y = d.y1;
+  int dx = (int)d.x2 - (int)d.x1, dy = (int)d.y2 - (int)d.y1;
+  const int sx = dx < 0 ? -1 : 1, sy = dy < 0 ? -1 : 1;
+  dx = dx < 0 ? -dx : dx, dy = dy < 0 ? -dy : dy;
+  int major_x = sx, major_y = 0, minor_x = 0, minor_y = sy;
+  if (dy > dx) {  // y is the major axis
+    const int t = dx;
+    dx = dy, dy = t;
+    major_x = 0, major_y = sy, minor_x = sx, minor_y = 0;
+  }
+  int err = dx - 2 * dy;
+  const int count = dx + 1;
+  for (int ii = 0; ii < count; ++ii) {
+    f(ii, count, x, y);
+    const bool m = err < 0;
+    err += -2 * dy + (m ? 2 * dx : 0);
+    x += major_x + (m ? minor_x : 0), y += major_y + (m ? minor_y : 0);
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_wire_count(int n_draws, const WireDraw* __restrict__ draws, int rows, int cols, uint32_t* __restrict__ cnt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_draws) return;
+  const WireDraw d = draws[i];
+  if (d.x1 < 0) return;
+  walk_line(d, [&](int, int, int x, int y) {
+    if ((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows) atomicAdd(&cnt[(long)y * cols + x], 1u);
+  });
+}
+
+// offset[p] = the sum of cnt over the pixels that came before p at the cursor.  A lane sums kOffsetsPerLane consecutive pixels, the
+// wave scans its 64 sums with shuffles and takes its range with ONE atomicAdd: atomics on one address follow each other at about
+// 11 ns, and a wave per 64 pixels made this kernel the longest of the five (370 us at 1080p); a wave per 1024 pixels takes 2025.
+// No lane leaves before the shuffles.
+constexpr int kOffsetsPerLane = 16;
+
+__global__ void __launch_bounds__(256)
+k_wire_offsets(long n, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ offset, int* __restrict__ counts) {
+  const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * kOffsetsPerLane;
+  const int lane = threadIdx.x & 63;
+  uint32_t c[kOffsetsPerLane];
+  uint32_t sum = 0u;
+#pragma unroll
+  for (int k = 0; k < kOffsetsPerLane; ++k) {
+    c[k] = i0 + k < n ? cnt[i0 + k] : 0u;
+    sum += c[k];
+  }
+  uint32_t incl = sum;
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const uint32_t v = __shfl_up(incl, s, 64);
+    if (lane >= s) incl += v;
+  }
+  uint32_t base = 0u;
+  if (lane == 63 && incl != 0u) base = atomicAdd((uint32_t*)&counts[kWireTotal], incl);
+  base = __shfl(base, 63, 64);
+  uint32_t at = base + (incl - sum);
+#pragma unroll
+  for (int k = 0; k < kOffsetsPerLane; ++k) {
+    if (i0 + k < n) offset[i0 + k] = at;
+    at += c[k];
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_wire_fill(int n_draws, const WireDraw* __restrict__ draws, int rows, int cols, float scene_color_scale,
+            const uint32_t* __restrict__ offset, uint32_t* __restrict__ fill, uint64_t* __restrict__ entries, uint32_t capacity) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_draws) return;
+  const WireDraw d = draws[i];
+  if (d.x1 < 0) return;
+  const float a_val = d.a_val, b_val = d.b_val;
+  walk_line(d, [&](int ii, int count, int x, int y) {
+    if (!((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows)) return;
+    const float slope0 = (b_val - a_val) / (float)count;
+    const float val = a_val + (float)ii * slope0;
+    uint8_t c[3];
+    jet02(val * scene_color_scale, c);
+    const long p = (long)y * cols + x;
+    const uint32_t at = offset[p] + atomicAdd(&fill[p], 1u);
+    if (at < capacity) entries[at] = ((uint64_t)(uint32_t)i << 32) | (uint64_t)pack3(c);
+  });
+}
+
+__global__ void __launch_bounds__(256)
+k_wire_fold(WireImageArgs a, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ offset,
+            const uint64_t* __restrict__ entries, uint32_t capacity, uint8_t* __restrict__ img) {
+  const long n = (long)a.rows * a.cols;
+  const long o0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * kPixelsPerThread;
+  if (o0 >= n) return;
+  uint32_t px[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int k = 0; k < kPixelsPerThread; ++k) {
+    const long o = o0 + k;
+    if (o >= n) continue;
+    const long i = a.flip ? n - 1 - o : o;  // the source pixel of output pixel o
+    const int row = (int)(i / a.cols), col = (int)(i % a.cols);
+    const uint32_t g = a.gray[(long)row * a.gray_step + col];  // cvtColor(GRAY2RGB): three equal bytes
+    uint32_t c0 = g, c1 = g, c2 = g;
+    const uint32_t c = cnt[i], off = offset[i];
+    // (a list that does not fit the entry buffer is left alone: the total says so and the host repeats fill and fold)
+    if (c != 0u && (uint64_t)off + c <= (uint64_t)capacity) {
+      const uint64_t* e = entries + off;
+      int64_t last = -1;
+      for (uint32_t j = 0; j < c; ++j) {
+        uint64_t best = ~0ull;
+        if (c == 1u) {
+          best = e[0];
+        } else {
+          for (uint32_t m = 0; m < c; ++m) {
+            const uint64_t v = e[m];
+            if ((int64_t)(v >> 32) > last && v < best) best = v;
+          }
+        }
+        if (best == ~0ull) break;
+        last = (int64_t)(best >> 32);
+        c0 = (c0 + ((uint32_t)best & 255u)) >> 1;
+        c1 = (c1 + ((uint32_t)(best >> 8) & 255u)) >> 1;
+        c2 = (c2 + ((uint32_t)(best >> 16) & 255u)) >> 1;
+      }
+    }
+    px[k] = c0 | (c1 << 8) | (c2 << 16);
+  }
+  store_pixels(img, o0, n, px);
+}
+
+}  // namespace
+
+int launch_wireframe_lists(int T, const int32_t* tris, const float2* vtx, const float* x, float value_scale, const uint8_t* tri_valid,
+                           const WireBuffers& b, int rows, int cols, hipEvent_t after_setup, hipStream_t s) {
+  const long n = (long)rows * cols;
+  const int n_draws = 3 * T;
+  if (n <= 0) return 0;
+  (void)hipMemsetAsync(b.cnt, 0, sizeof(uint32_t) * (size_t)n, s);
+  (void)hipMemsetAsync(b.counts, 0, kWireCounts * sizeof(int), s);
+  if (n_draws > 0)
+    hipLaunchKernelGGL(k_wire_setup, grid1d(n_draws), dim3(256), 0, s, n_draws, tris, vtx, x, value_scale, tri_valid, rows, cols,
+                       b.draws, b.counts);
+  if (after_setup) {
+    const hipError_t e = hipEventRecord(after_setup, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  if (n_draws > 0) hipLaunchKernelGGL(k_wire_count, grid1d(n_draws), dim3(256), 0, s, n_draws, b.draws, rows, cols, b.cnt);
+  hipLaunchKernelGGL(k_wire_offsets, grid1d((n + kOffsetsPerLane - 1) / kOffsetsPerLane), dim3(256), 0, s, n, b.cnt, b.offset, b.counts);
+  return (int)hipGetLastError();
+}
+
+int launch_wireframe_paint(int T, const WireBuffers& b, const WireImageArgs& a, uint8_t* img, hipStream_t s) {
+  const long n = (long)a.rows * a.cols;
+  const int n_draws = 3 * T;
+  if (n <= 0) return 0;
+  (void)hipMemsetAsync(b.fill, 0, sizeof(uint32_t) * (size_t)n, s);
+  if (n_draws > 0)
+    hipLaunchKernelGGL(k_wire_fill, grid1d(n_draws), dim3(256), 0, s, n_draws, b.draws, a.rows, a.cols, a.scene_color_scale, b.offset,
+                       b.fill, b.entries, b.capacity);
+  hipLaunchKernelGGL(k_wire_fold, grid1d((n + kPixelsPerThread - 1) / kPixelsPerThread), dim3(256), 0, s, a, b.cnt, b.offset,
+                     b.entries, b.capacity, img);
+  return (int)hipGetLastError();
+}
+
+}  // namespace flame_hip

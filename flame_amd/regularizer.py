@@ -95,6 +95,21 @@ class _DebugImagesView(C.Structure):
                 ("w1_map", _FP), ("w2_map", _FP), ("device_ms", C.c_float)]
 
 
+class WireframeParams(C.Structure):
+    """== flame_nltgv2_wireframe_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and where the triangle
+    validity comes from (0: all valid, 1: a host array, 2: what the last mesh_outputs_begin left on the device)."""
+
+    _fields_ = [("scene_color_scale", C.c_float), ("flip", C.c_int32), ("validity", C.c_int32)]
+
+    def __init__(self, scene_color_scale=1.0, flip=False, validity=0):
+        super().__init__(scene_color_scale, int(bool(flip)), int(validity))
+
+
+class _WireframeView(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wireframe_img", C.POINTER(C.c_uint8)), ("lines_drawn", C.c_int32),
+                ("lines_skipped", C.c_int32), ("entries", C.c_int64), ("refilled", C.c_int32), ("device_ms", C.c_float)]
+
+
 class _Graph(C.Structure):
     _fields_ = (
         [("V", C.c_int32), ("E", C.c_int32), ("pos", _FP)]
@@ -154,6 +169,8 @@ ABI_SYMBOLS = (
     "flame_nltgv2_mesh_outputs_end", "flame_nltgv2_mesh_outputs",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
+    "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
+    "flame_nltgv2_debug_wireframe",
 )
 
 
@@ -237,6 +254,12 @@ def load_library():
         "flame_nltgv2_debug_images_end": (C.c_int, [ctx, C.POINTER(_DebugImagesView)]),
         "flame_nltgv2_debug_images": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int, C.c_int,
                                                 C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _FP, _FP]),
+        "flame_nltgv2_default_wireframe_params": (None, [C.POINTER(WireframeParams)]),
+        "flame_nltgv2_debug_wireframe_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(WireframeParams),
+                                                         C.c_int, C.c_int, C.c_float]),
+        "flame_nltgv2_debug_wireframe_end": (C.c_int, [ctx, C.POINTER(_WireframeView)]),
+        "flame_nltgv2_debug_wireframe": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(WireframeParams), C.c_int,
+                                                   C.c_int, C.c_float, C.POINTER(C.c_uint8), _IP, _IP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -634,6 +657,36 @@ class Regularizer:
         """debug_images_begin; debug_images_end."""
         self.debug_images_begin(img, K, rows, cols, params, img_device, step_bytes)
         return self.debug_images_end()
+
+    # -- getDebugImageWireframe, drawWireframe flame.cc:2414-2457 (flame_nltgv2_debug_wireframe*) -------------------------------------
+    def debug_wireframe_begin(self, img, rows, cols, graph_scale=1.0, params=None, tri_valid=None, img_device=None, step_bytes=None):
+        """Enqueues drawWireframe over the resident triangles and the state's pos / x on the side stream and returns.  The grey image
+        as in debug_images_begin.  tri_valid: a (T,) u8 array, for params.validity == 1 (given without params, it selects that)."""
+        if params is None:
+            params = WireframeParams(validity=0 if tri_valid is None else 1)
+        tv = None if tri_valid is None else np.ascontiguousarray(tri_valid, np.uint8)
+        if img is not None:
+            if not (isinstance(img, np.ndarray) and _rows_contiguous_u8(img) and img.shape == (rows, cols)):
+                img = np.ascontiguousarray(img, np.uint8).reshape(rows, cols)
+            host, dev, step = C.c_void_p(img.ctypes.data), None, int(img.strides[0]) if step_bytes is None else int(step_bytes)
+        else:
+            host, dev, step = None, (C.c_void_p(int(img_device)) if img_device else None), int(step_bytes if step_bytes is not None else cols)
+        self._chk(self._L.flame_nltgv2_debug_wireframe_begin(self._ctx, host, dev, step, None if tv is None else C.c_void_p(tv.ctypes.data),
+                                                             C.byref(params), rows, cols, C.c_float(graph_scale)), "debug_wireframe_begin")
+
+    def debug_wireframe_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(wireframe_img (rows,cols,3) u8, lines_drawn, lines_skipped, entries, refilled, device_ms).
+        copy=False: a view of the context's pinned memory, valid until the next begin."""
+        v = _WireframeView()
+        self._chk(self._L.flame_nltgv2_debug_wireframe_end(self._ctx, C.byref(v)), "debug_wireframe_end")
+        img = np.ctypeslib.as_array(v.wireframe_img, shape=(v.rows, v.cols, 3))
+        return dict(wireframe_img=img.copy() if copy else img, lines_drawn=int(v.lines_drawn), lines_skipped=int(v.lines_skipped),
+                    entries=int(v.entries), refilled=int(v.refilled), device_ms=float(v.device_ms))
+
+    def debug_wireframe(self, img, rows, cols, graph_scale=1.0, params=None, tri_valid=None, img_device=None, step_bytes=None) -> dict:
+        """debug_wireframe_begin; debug_wireframe_end."""
+        self.debug_wireframe_begin(img, rows, cols, graph_scale, params, tri_valid, img_device, step_bytes)
+        return self.debug_wireframe_end()
 
     def interpolate_mesh_arrays(self, triangles, vertices, values, rows, cols, vtx_valid=None, tri_valid=None):
         tr = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)

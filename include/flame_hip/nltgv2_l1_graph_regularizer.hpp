@@ -223,6 +223,24 @@ struct DebugImages {
   const float* w2_map = nullptr;                 // [rows * cols] w2_map_
 };
 
+// == the members of flame::Params drawWireframe reads (params.h:109, debug_flip_images) and where the triangle validity comes from:
+// layout-identical to flame_nltgv2_wireframe_params, same defaults.  debug_draw_text_overlay is treated as false.
+struct WireframeParams {
+  float scene_color_scale = 1.0f;
+  int32_t debug_flip_images = 0;
+  int32_t validity = 0;  // 0: every triangle valid; 1: tri_validity is a host array; 2: what the last meshOutputsBegin left on the device
+};
+static_assert(sizeof(WireframeParams) == sizeof(flame_nltgv2_wireframe_params), "WireframeParams must mirror the C-ABI struct");
+
+// What drawWireframe (flame.cc:2414-2457) leaves for getDebugImageWireframe, under the reference's member name.  The pointer goes into
+// pinned memory of the DeviceGraph, valid until its next debugWireframeBegin().  Pixels are cv::Vec3b: 3 bytes, c[0], c[1], c[2].
+struct Wireframe {
+  int rows = 0, cols = 0;
+  const uint8_t* debug_img_wireframe = nullptr;  // [rows * cols * 3]
+  int lines_drawn = 0, lines_skipped = 0;        // lines of valid triangles: walked / left out (an endpoint outside the image)
+  bool refilled = false;                         // the stage's entry buffer had to grow: the second half ran twice
+};
+
 // Device image of ONE Graph: what the pipeline keeps next to `Graph graph_` (flame.h:536).  Not
 // thread-safe -- hold graph_mtx_ (flame.h:539) around every call exactly as the reference does around
 // step() and the graph edits (flame.cc:103, 302, 309, 329, 365).
@@ -375,6 +393,25 @@ class DeviceGraph {
                           int rows, int cols) {
     debugImagesBegin(img_host, img_device, step_bytes, K, params, rows, cols);
     return debugImagesEnd();
+  }
+
+  // drawWireframe (flame.cc:2414-2457) over the triangles the last interpolateMesh[Begin] / meshOutputsBegin left on the device and the
+  // state's positions and x * graph_scale, on the side stream (flame_nltgv2_debug_wireframe_begin / _end).  The grey image as in
+  // debugImagesBegin.  tri_validity: a host array of one byte per triangle with params.validity == 1, else nullptr.
+  void debugWireframeBegin(const uint8_t* img_host, const void* img_device, int step_bytes, const uint8_t* tri_validity,
+                           const WireframeParams& params, int rows, int cols, float graph_scale) {
+    flame_nltgv2_wireframe_params c;
+    std::memcpy(&c, &params, sizeof(c));
+    check(flame_nltgv2_debug_wireframe_begin(ctx_, img_host, img_device, step_bytes, tri_validity, &c, rows, cols, graph_scale),
+          "debug_wireframe_begin");
+  }
+  Wireframe debugWireframeEnd() {
+    flame_nltgv2_wireframe_view v;
+    check(flame_nltgv2_debug_wireframe_end(ctx_, &v), "debug_wireframe_end");
+    Wireframe w;
+    w.rows = v.rows, w.cols = v.cols, w.debug_img_wireframe = v.wireframe_img;
+    w.lines_drawn = v.lines_drawn, w.lines_skipped = v.lines_skipped, w.refilled = v.refilled != 0;
+    return w;
   }
 
   // utils::interpolateMesh (utils/image_utils.cc:373-396) at its call site flame.cc:409-415: rasterises

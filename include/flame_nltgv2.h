@@ -354,9 +354,9 @@ int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
  * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
  * flame_stereo.h.)  Every byte is meant to equal the reference's; tests/debug_ref.py restates the operations and is the checker.
  *
+ * (getDebugImageWireframe: flame_nltgv2_debug_wireframe_begin, below this block.)
+ *
  * NOT covered, on purpose:
- *   drawWireframe      blends cv::LineIterator pixels sequentially, in triangle order: a pixel's value depends on every earlier draw
- *                      that touched it.  On the device that needs a per-pixel ordered list and a restated OpenCV line walk.
  *   cv::putText        debug_draw_text_overlay is treated as false.
  *   drawDetections, debug_draw_matches, debug_draw_photo_error   feed on commented-out code in the reference.
  *
@@ -414,6 +414,72 @@ int flame_nltgv2_debug_images_end(flame_nltgv2_ctx* ctx, flame_nltgv2_debug_imag
 int flame_nltgv2_debug_images(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes, const float* K,
                               const flame_nltgv2_debug_image_params* params, int rows, int cols, uint8_t* idepthmap_img_out,
                               uint8_t* normals_img_out, float* w1_map_out, float* w2_map_out);
+
+/* ---- getDebugImageWireframe (flame.h, drawWireframe flame.cc:2414-2457 at its call site flame.cc:491-494) ---------------------------------
+ * drawColorMappedWireframe (utils/image_utils.h:693-719) over applyColorMapLine (utils/visualization.h:235-260), from the resident
+ * triangles, the canonical pos / x and the frame's grey image.  The reference draws SEQUENTIALLY and blends: a pixel's final value
+ * depends on every draw that touched it, in draw order.  OpenCV is not part of this tree, so the rule is stated here in full; every byte
+ * follows from it, and tests/wireframe_ref.py restates it sequentially and is the checker.
+ *   1 endpoints   cv::Point2f -> cv::Point is cvRound, round half to even (2.5 -> 2, 3.5 -> 4), per coordinate, as the rasteriser does it.
+ *   2 the walk    cv::LineIterator(img, pt1, pt2), OpenCV 3.2, connectivity 8, starting AT pt1 (not left to right), restated -- UNPINNED:
+ *                 dx = x2 - x1, dy = y2 - y1; sx, sy their signs; dx, dy their absolute values; if dy > dx (strict) y is the major axis
+ *                 and dx, dy are swapped; err = dx - 2 dy; count = dx + 1.  After visiting a pixel: m = err < 0;
+ *                 err += -2 dy + (m ? 2 dx : 0); one pixel along the major axis and, if m, also one along the minor axis.
+ *                 (0,0)->(2,1) visits (0,0) (1,0) (2,1); (2,1)->(0,0) visits (2,1) (1,1) (0,0): direction matters.
+ *   3 value       slope0 = (B_val - A_val) / (float)count; pixel ii (0 .. count - 1) has val = A_val + (float)ii * slope0, in float
+ *                 without FMA (B's value is never reached); its colour is jet(val * scene_color_scale, 0, 2) exactly as in the idepth
+ *                 image above, the NaN colour (0, 0, 255) included (UNPINNED).  A_val, B_val are x * graph_scale (vtx_idepths_).
+ *   4 blend       alpha = 0.5 (flame.cc:2432): color * 0.5f + old * 0.5f is exact in float and the store into a uchar truncates, so per
+ *                 channel new = (color + old) >> 1.  A pixel starts at its grey value and folds its draws in increasing draw id,
+ *                 id = 3 * triangle + k, k = 0: v0 -> v1, k = 1: v1 -> v2, k = 2: v0 -> v2.  One draw visits a pixel at most once.
+ *   5 validity    a triangle is drawn iff its tri_valid byte is non-zero (the reference's vtx_validity is all true).
+ *   6 outside     DEVIATES from the reference, which clips with cv::clipLine -- UNPINNED; the pipeline never needs it (projectGraph drops
+ *                 out-of-image vertices, flame.cc:1922).  Here a line with a non-finite endpoint coordinate, or a ROUNDED endpoint outside
+ *                 [0, cols - 1] x [0, rows - 1], is not drawn at all and counted in lines_skipped; the other lines of its triangle are
+ *                 drawn.  Nothing is written outside the image for any input.
+ *   7 flip        cv::flip(img, img, -1): the finished picture in reversed linear pixel order.  No text overlay.
+ * == scene_color_scale params.h:109, debug_flip_images, and where the triangle validity comes from. */
+typedef struct flame_nltgv2_wireframe_params {
+  float   scene_color_scale;  /* 1.0 */
+  int32_t flip;               /* 0 */
+  int32_t validity;           /* 0: every triangle is valid (tri_valid must be NULL); 1: tri_valid is a host array of T bytes;
+                                 2: the validity the last flame_nltgv2_mesh_outputs_begin left on the device for the resident
+                                    triangles (tri_valid must be NULL; an error if there is none for the current triangles and topology) */
+} flame_nltgv2_wireframe_params;
+void flame_nltgv2_default_wireframe_params(flame_nltgv2_wireframe_params* p);
+
+/* Pointers into pinned memory of the context, valid until the next flame_nltgv2_debug_wireframe_begin. */
+typedef struct flame_nltgv2_wireframe_view {
+  int32_t rows, cols;
+  const uint8_t* wireframe_img;  /* [rows * cols * 3] debug_img_wireframe_ */
+  int32_t lines_drawn;           /* lines of valid triangles that were walked */
+  int32_t lines_skipped;         /* lines of valid triangles left out by rule 6; drawn + skipped = 3 * valid triangles */
+  int64_t entries;               /* pixel visits of all draws together */
+  int32_t refilled;              /* 1: the entries did not fit the stage's buffer, and _end grew it and repeated the second half */
+  float device_ms;               /* measurement aid: HIP-event time of the stage on the side stream, kernels and copy out */
+} flame_nltgv2_wireframe_view;
+
+/* begin  checks the arguments -- an error (no graph; no resident triangles for the current topology; rows / cols <= 0 or > 32767, or more
+ *        than 2^31 possible pixel visits; both or neither image pointer; step_bytes < cols; params NULL; validity outside 0..2; a tri_valid
+ *        pointer with validity != 1 or none with validity == 1; validity == 2 without a matching flame_nltgv2_mesh_outputs_begin) is
+ *        reported before anything is enqueued and leaves the outputs of an earlier begin as they are --, then enqueues everything on the
+ *        context's side stream, beside a running solver, and returns.  The triangles are the ones the last
+ *        flame_nltgv2_interpolate_mesh[_begin] or flame_nltgv2_mesh_outputs_begin left on the device; pos and x are read from the state
+ *        flame_nltgv2_interpolate_mesh_begin would read.  The grey image is given as in flame_nltgv2_debug_images_begin (a device image
+ *        must stay valid until _end).  rows x cols need not be the resident map's size: the map is not read.  The buffers, pinned outputs
+ *        and pending _end of flame_nltgv2_mesh_outputs_begin and flame_nltgv2_debug_images_begin are left alone, and they leave this
+ *        stage's alone.  Only the first kernel reads pos / x: whoever rewrites them waits for that kernel, not for the picture.
+ * end    waits for the side stream and fills *out.  The entry buffer holds max(2 * rows * cols, 1.25 * the last call's entries) and never
+ *        shrinks; where a call's entries exceed it, _end grows it, repeats fill and fold, waits again and sets refilled: the picture
+ *        is exact either way, and begin never waits for a count.
+ * flame_nltgv2_debug_wireframe == begin; end; copies into the caller's array and counters (each may be NULL). */
+int flame_nltgv2_debug_wireframe_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
+                                       const uint8_t* tri_valid, const flame_nltgv2_wireframe_params* params, int rows, int cols,
+                                       float graph_scale);
+int flame_nltgv2_debug_wireframe_end(flame_nltgv2_ctx* ctx, flame_nltgv2_wireframe_view* out);
+int flame_nltgv2_debug_wireframe(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
+                                 const uint8_t* tri_valid, const flame_nltgv2_wireframe_params* params, int rows, int cols,
+                                 float graph_scale, uint8_t* wireframe_img_out, int32_t* lines_drawn_out, int32_t* lines_skipped_out);
 
 /* 2-D Delaunay triangulation of float32 points: the counterpart of utils::Delaunay
  * (src/flame/utils/delaunay.{h,cc}, a wrapper of the vendored Shewchuk Triangle called with "zneQB",

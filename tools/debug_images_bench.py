@@ -1,7 +1,7 @@
-"""Time of the debug-image stage (flame_nltgv2_debug_images: idepth colours, w1 / w2 maps, normals; flame_stereo_draw_features) and
-of the same pictures made the way a host had to before the stage existed.
+"""Time of the debug-image stages (flame_nltgv2_debug_images: idepth colours, w1 / w2 maps, normals; flame_stereo_draw_features;
+flame_nltgv2_debug_wireframe) and of the same pictures made the way a host had to before the stages existed.
 
-    python tools/debug_images_bench.py [--reps 30] [--out profiles/debug_images.txt] [--commit HASH]
+    python tools/debug_images_bench.py [--reps 30] [--out profiles/debug_images.txt] [--commit HASH] [--no-host-wireframe]
 
 device   HIP events around the stage on the context's side stream (kernels and the copies out; flame_nltgv2_debug_images_view
          .device_ms), median over --reps calls after warm-up, with the frame's image in device memory and in host memory; `call` is
@@ -9,8 +9,11 @@ device   HIP events around the stage on the context's side stream (kernels and t
 host     what the stage replaces, in the same run: interpolate_mesh (rasteriser + the map's way down) + download_state(x, w1, w2) +
          get_projected + two host rasterisations (the raster checker, C) + numpy colouring of the three pictures
          (tests/debug_ref.py): wall time, median of 3.  The colouring is numpy, not the reference's C++: context, not a target.
-solver   iterations per microsecond of run_async beside nothing, beside ten mesh_outputs calls and beside ten debug_images calls
-         (FLAME_NLTGV2_OPT_MESH_STATE = 1, so that neither stage waits for the run).
+wireframe  flame_nltgv2_debug_wireframe with the validity mesh_outputs left on the device and the image in device memory: device and
+         call as above, the entries (pixel visits of all lines) and whether a call had to refill.  Its host path: download_state(x) +
+         mesh_outputs (validity) + the sequential Python restatement tests/wireframe_ref.py, once: context, not a target.
+solver   iterations per microsecond of run_async beside nothing, beside ten mesh_outputs calls, beside ten debug_images calls and
+         beside ten debug_wireframe calls (FLAME_NLTGV2_OPT_MESH_STATE = 1, so that no stage waits for the run).
 Sizes: 640x480 and 1920x1080 (flame_amd.synth graphs, scipy Delaunay triangles), 200 solver iterations first.
 """
 from __future__ import annotations
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
+    ap.add_argument("--no-host-wireframe", action="store_true", help="skip the sequential Python wireframe (tens of seconds at 1080p)")
     a = ap.parse_args()
 
     import torch  # noqa: F401  (one HIP runtime per process: torch's)
@@ -42,6 +46,7 @@ def main():
     from flame_amd.stereo import FEATURE_DTYPE, FeatureTracker, StereoParams
     from oracle import capi as oracle
     from tests import debug_ref as dr
+    from tests import wireframe_ref as wr
 
     commit = a.commit
     if commit is None:
@@ -97,6 +102,26 @@ def main():
                 t1 = time.perf_counter()
                 if r >= 5:
                     fk.append(tr.last_kernel_ms() * 1e3), fc.append((t1 - t0) * 1e6)
+            # the wireframe, with the validity the filters leave on the device
+            wp = flame_amd.WireframeParams(validity=2)
+            n_valid = reg.mesh_outputs(None, Kinv, h, w, graph_scale=1.1)["n_valid"]
+            wdev, wcall, wrefills = [], [], 0
+            for r in range(a.reps + 5):
+                t0 = time.perf_counter()
+                reg.debug_wireframe_begin(None, h, w, 1.1, wp, img_device=ptr, step_bytes=step)
+                wout = reg.debug_wireframe_end(copy=False)
+                t1 = time.perf_counter()
+                wrefills += wout["refilled"]
+                if r >= 5:
+                    wdev.append(wout["device_ms"] * 1e3), wcall.append((t1 - t0) * 1e6)
+            whost_ms = None
+            if not a.no_host_wireframe:
+                t0 = time.perf_counter()
+                st = reg.download_state(("x",))
+                mo = reg.mesh_outputs(None, Kinv, h, w, graph_scale=1.1)
+                wref, _, _ = wr.draw_wireframe(img, tris, g["pos"], mo["vtx_idepth"], mo["tri_valid"])
+                whost_ms = (time.perf_counter() - t0) * 1e3
+                assert st["x"].shape == mo["vtx_idepth"].shape and np.array_equal(wref, wout["wireframe_img"]), "the wireframe differs from the checker"
             host = []
             for _ in range(3):
                 t0 = time.perf_counter()
@@ -114,7 +139,8 @@ def main():
             reg.set_option(OPT_MESH_STATE, 1)
             n_iters = 30000
             rate = {}
-            for beside in ("nothing", "mesh_outputs", "debug_images"):
+            reg.mesh_outputs(None, Kinv, h, w, graph_scale=1.1)  # (interpolate_mesh above handed the triangles in again: validity for them)
+            for beside in ("nothing", "mesh_outputs", "debug_images", "debug_wireframe"):
                 best = 0.0
                 for _ in range(3):
                     reg.sync()
@@ -128,6 +154,9 @@ def main():
                         elif beside == "debug_images":
                             reg.debug_images_begin(None, K, h, w, p, img_device=ptr, step_bytes=step)
                             reg.debug_images_end(copy=False)
+                        elif beside == "debug_wireframe":
+                            reg.debug_wireframe_begin(None, h, w, 1.1, wp, img_device=ptr, step_bytes=step)
+                            reg.debug_wireframe_end(copy=False)
                     t_stage = time.perf_counter()
                     reg.sync()
                     t1 = time.perf_counter()
@@ -138,6 +167,10 @@ def main():
             lines.append(f"{config} V={g['V']} T={len(tris)} idepth + normals + w maps, image in {where} memory: device_us {d:.1f} (min {dmin:.1f}) "
                          f"call_us {c:.1f}")
         lines.append(f"{config} draw_features, {n_proj} projected features ({nc} drawn): kernels_us {np.median(fk):.1f} call_us {np.median(fc):.1f}")
+        lines.append(f"{config} wireframe, {n_valid} of {len(tris)} triangles valid, {wout['lines_drawn']} lines, {wout['entries']} entries "
+                     f"({wout['entries'] / (h * w):.2f} per pixel), image in device memory: device_us {np.median(wdev):.1f} (min {np.min(wdev):.1f}) "
+                     f"call_us {np.median(wcall):.1f}; calls that refilled: {wrefills} of {a.reps + 5}"
+                     + (f"; host path (download_state + mesh_outputs + sequential Python): host_ms {whost_ms:.0f}, same bytes" if whost_ms is not None else ""))
         total_call = res["device"][2] + float(np.median(fc))
         lines.append(f"{config} host path (three pictures): host_ms {host_ms:.1f}; ratio host / device calls {host_ms * 1e3 / total_call:.0f}x")
         lines.append(f"{config} solver, {n_iters} iterations of run_async, iterations per us (best of 3): " + ", ".join(
