@@ -16,6 +16,7 @@
 #include "stereo_kernels.h"
 #include "feature_kernels.h"
 #include "debug_kernels.h"
+#include "matches_kernels.h"
 #include "roctx_ranges.hpp"
 
 using namespace flame_hip;
@@ -99,6 +100,18 @@ struct flame_stereo_ctx {
   size_t owner_cap = 0;
   uint8_t* d_draw = nullptr;
   size_t draw_cap = 0;
+  // draw_matches (matches_kernels.hip): the draw records of the last update, and the lists of the fold
+  int record_matches = 0;  // FLAME_STEREO_OPT_RECORD_MATCHES
+  MatchRecord* d_match = nullptr;
+  size_t match_cap = 0;
+  bool match_stand = false;  // records of an enqueued update stand (whether it hit an assert shows in h_stats once the stream is idle)
+  int match_n = 0;
+  uint32_t match_frame = 0;
+  uint32_t* d_mlist = nullptr;  // cnt, offset, fill (one word per pixel each) and the kMatchCounts counters behind them
+  size_t mlist_cap = 0;
+  uint64_t* d_mentries = nullptr;
+  size_t mentries_cap = 0;
+  size_t match_last_total = 0;
 };
 
 namespace {
@@ -166,6 +179,7 @@ int pick_lanes(const flame_stereo_ctx* ctx, int n_feats) {
 
 int enqueue_update(flame_stereo_ctx* ctx, const flame_stereo_params* params, uint32_t new_frame_id, uint32_t curr_pf_id,
                    int n_poses, const flame_stereo_pose* poses, int n_feats, StereoFeature* d_feats) {
+  ctx->match_stand = false;  // (whatever this update comes to, the records of an earlier one no longer describe the last update)
   if (!params || n_poses < 0 || n_feats < 0 || (n_poses > 0 && !poses)) return FLAME_NLTGV2_ERR_INVALID_ARG;
   if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
   auto nf = ctx->frames.find(new_frame_id);
@@ -178,6 +192,11 @@ int enqueue_update(flame_stereo_ctx* ctx, const flame_stereo_params* params, uin
     ctx->h_poses_cap = want;
   }
   if (int rc = grow(ctx, &ctx->d_poses, &ctx->poses_cap, (size_t)n_poses + 1)) return rc;
+  MatchRecord* records = nullptr;
+  if (ctx->record_matches) {
+    if (int rc = grow(ctx, &ctx->d_match, &ctx->match_cap, (size_t)n_feats + 1)) return rc;
+    records = ctx->d_match;
+  }
   // the pinned table may still be in flight from the previous launch on this stream
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < n_poses; ++k) {
@@ -195,13 +214,16 @@ int enqueue_update(flame_stereo_ctx* ctx, const flame_stereo_params* params, uin
   std::memset(ctx->h_stats, 0, kStatWords * sizeof(int));
   ctx->h_stats[kStatAssert] = ctx->h_stats[kStatBadFrame] = INT_MAX;
   SCHK(ctx, hipMemcpyAsync(ctx->d_stats, ctx->h_stats, kStatWords * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  if (records && n_feats > 0)  // (all zero = nothing drawn: the early returns of the kernel need no code)
+    SCHK(ctx, hipMemsetAsync(records, 0, (size_t)n_feats * sizeof(MatchRecord), ctx->stream));
   SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   SCHK(ctx, launch_update_feature_idepths(*params, ctx->cam, n_poses, ctx->d_poses, nf->second.img_pad, nf->second.gx_pad,
                                           nf->second.gy_pad, curr_pf_id, n_feats, d_feats, ctx->d_stats, pick_lanes(ctx, n_feats),
-                                          ctx->stream));
+                                          records, ctx->stream));
   SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
   SCHK(ctx, hipMemcpyAsync(ctx->h_stats, ctx->d_stats, kStatWords * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  if (records) ctx->match_stand = true, ctx->match_n = n_feats, ctx->match_frame = new_frame_id;
   return 0;
 }
 
@@ -491,7 +513,8 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   if (ctx->d_res) (void)hipFree(ctx->d_res);
   for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
                   (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_keep_ids, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
-                  (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel, (void*)ctx->d_owner, (void*)ctx->d_draw})
+                  (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel, (void*)ctx->d_owner, (void*)ctx->d_draw,
+                  (void*)ctx->d_match, (void*)ctx->d_mlist, (void*)ctx->d_mentries})
     if (p) (void)hipFree(p);
   if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
   if (ctx->h_sel) (void)hipHostFree(ctx->h_sel);
@@ -517,6 +540,7 @@ int flame_stereo_set_camera(flame_stereo_ctx* ctx, const float K[9], const float
     return FLAME_NLTGV2_ERR_INVALID_ARG;
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
   drop_all_frames(ctx);
+  ctx->match_stand = false;
   std::memcpy(ctx->cam.K, K, sizeof ctx->cam.K);
   std::memcpy(ctx->cam.Kinv, Kinv, sizeof ctx->cam.Kinv);
   ctx->cam.width = width, ctx->cam.height = height, ctx->cam.border = border;
@@ -621,6 +645,11 @@ int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value) {
     case FLAME_STEREO_OPT_GRAPH_COPY:
       if (value != 0 && value != 1) return FLAME_NLTGV2_ERR_INVALID_ARG;
       ctx->graph_copy = value;
+      return 0;
+    case FLAME_STEREO_OPT_RECORD_MATCHES:
+      if (value != 0 && value != 1) return FLAME_NLTGV2_ERR_INVALID_ARG;
+      if (value != ctx->record_matches) ctx->match_stand = false;  // (records come from an update that ran with the option on)
+      ctx->record_matches = value;
       return 0;
     default:
       return FLAME_NLTGV2_ERR_INVALID_ARG;
@@ -800,6 +829,63 @@ int flame_stereo_draw_features(flame_stereo_ctx* ctx, uint32_t cur_frame_id, flo
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (num_converged) *num_converged = counts[0];
   if (num_unconverged) *num_unconverged = counts[1];
+  return 0;
+}
+
+int flame_stereo_draw_matches(flame_stereo_ctx* ctx, int flip, uint8_t* img_out, flame_stereo_matches_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_draw_matches");
+  if (int rc = enter(ctx)) return rc;
+  if (stats) std::memset(stats, 0, sizeof *stats);
+  if (!img_out || !ctx->record_matches || !ctx->match_stand || !ctx->have_camera) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  auto fr = ctx->frames.find(ctx->match_frame);
+  if (fr == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (an enqueue-only update has finished and reported; buffers may be reallocated)
+  if (ctx->h_stats[kStatAssert] != INT_MAX || ctx->h_stats[kStatBadFrame] != INT_MAX) {  // that update returned an error
+    ctx->match_stand = false;
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  const int width = ctx->cam.width, height = ctx->cam.height, pitch = width + 2 * ctx->cam.border, n = ctx->match_n;
+  const size_t px = (size_t)width * height;
+  auto entry_capacity = [&] { return std::max(2 * px, ctx->match_last_total + ctx->match_last_total / 4); };
+  if (int rc = grow(ctx, &ctx->d_mlist, &ctx->mlist_cap, 3 * px + kMatchCounts)) return rc;
+  if (int rc = grow(ctx, &ctx->d_mentries, &ctx->mentries_cap, entry_capacity())) return rc;
+  if (int rc = grow(ctx, &ctx->d_draw, &ctx->draw_cap, 3 * px + 16)) return rc;
+  MatchBuffers b;
+  b.cnt = ctx->d_mlist, b.offset = ctx->d_mlist + px, b.fill = ctx->d_mlist + 2 * px, b.counts = (int*)(ctx->d_mlist + 3 * px);
+  b.entries = ctx->d_mentries, b.capacity = (uint32_t)std::min<size_t>(entry_capacity(), UINT32_MAX);
+  MatchImageArgs a;
+  a.rows = height, a.cols = width;
+  a.gray = fr->second.img_pad + (size_t)ctx->cam.border * pitch + ctx->cam.border, a.gray_step = pitch;
+  a.flip = flip != 0;
+  int counts[kMatchCounts] = {0};
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, (hipError_t)launch_matches_lists(n, ctx->d_match, b, height, width, ctx->stream));
+  SCHK(ctx, hipMemcpyAsync(counts, b.counts, sizeof counts, hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, (hipError_t)launch_matches_paint(n, ctx->d_match, b, a, ctx->d_draw, ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(img_out, ctx->d_draw, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t total = (size_t)(uint32_t)counts[kMatchTotal];
+  ctx->match_last_total = total;
+  int refilled = 0;
+  if (total > (size_t)b.capacity) {  // the entry buffer was too small: grow it, repeat fill and fold (cnt and offset stand)
+    if (int rc = grow(ctx, &ctx->d_mentries, &ctx->mentries_cap, entry_capacity())) return rc;
+    b.entries = ctx->d_mentries, b.capacity = (uint32_t)std::min<size_t>(entry_capacity(), UINT32_MAX);
+    SCHK(ctx, (hipError_t)launch_matches_paint(n, ctx->d_match, b, a, ctx->d_draw, ctx->stream));
+    SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));  // (ev0 .. ev1 now spans both passes and the first picture's copy)
+    SCHK(ctx, hipMemcpyAsync(img_out, ctx->d_draw, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
+    SCHK(ctx, hipStreamSynchronize(ctx->stream));
+    refilled = 1;
+  }
+  if (stats) {
+    stats->num_features = n;
+    for (int k = 0; k < kMatchKinds; ++k) stats->kind_count[k] = counts[k];
+    stats->lines_drawn = counts[kMatchLinesDrawn], stats->lines_skipped = counts[kMatchLinesSkipped];
+    stats->rings_skipped = counts[kMatchRingsSkippedCount];
+    stats->entries = (int64_t)total;
+    stats->refilled = refilled;
+  }
   return 0;
 }
 

@@ -104,10 +104,28 @@ constexpr int kStatAssert = 6, kStatBadFrame = 7, kStatCount = 8;
 constexpr int kStatSlots = 64, kStatSlotStride = 32;
 constexpr int kStatWords = kStatCount + kStatSlots * kStatSlotStride;
 
+// What one feature draws into the matches picture (getDebugImageMatches, include/flame_stereo.h): written by the recording
+// instances of the update kernel at the branches the reference draws at, read by matches_kernels.hip.  All zero = nothing.
+struct MatchRecord {
+  int32_t rect_x, rect_y;  // centre of the filled rectangle: (int)(u_cmp + 0.5f)
+  int32_t ring_x, ring_y;  // centre of the rings: (int)(project(xy, idepth_mu) + 0.5f)
+  int16_t x1, y1, x2, y2;  // the searched segment's rounded endpoints (inside the image when kMatchLine is set)
+  uint32_t flags;          // bits 0-3: rectangle kind + 1 (0 = no rectangle), then the kMatch* bits
+  uint32_t reserved_;
+};
+static_assert(sizeof(MatchRecord) == 32, "a draw record is 32 bytes");
+// rectangle kinds, in the order of flame_stereo_matches_stats.kind_count; the two rings follow them there
+enum { kMatchMoveFailed = 0, kMatchMoved = 1, kMatchNoRegion = 2, kMatchNoGradient = 3, kMatchNoGradientFresh = 4,
+       kMatchAmbiguous = 5, kMatchMaxCost = 6, kMatchGreen = 7, kMatchBlue = 8, kMatchKinds = 9 };
+enum : uint32_t { kMatchKindMask = 15u, kMatchLine = 1u << 4, kMatchLineSkipped = 1u << 5, kMatchRingGreen = 1u << 6,
+                  kMatchRingBlue = 1u << 7, kMatchRingsSkipped = 1u << 8 };
+
+// `records` NULL: the plain instances.  Else the recording ones, which also write records[i] for every feature that draws
+// (the caller zeroes the array first); what they compute and store otherwise is the same.
 hipError_t launch_update_feature_idepths(const StereoParams& P, const StereoCamera& cam, int n_poses,
                                          const StereoPoseEntry* poses, const uint8_t* new_img, const float* new_gx,
                                          const float* new_gy, uint32_t curr_pf_id, int n, StereoFeature* feats, int* stats,
-                                         int lanes_per_feature, hipStream_t stream);
+                                         int lanes_per_feature, MatchRecord* records, hipStream_t stream);
 hipError_t launch_frame_pad_gradient(const uint8_t* img, int width, int height, int border, uint8_t* img_pad,
                                      float* gx_pad, float* gy_pad, hipStream_t stream);
 

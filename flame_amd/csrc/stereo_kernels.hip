@@ -20,6 +20,7 @@
 
 #include "stereo_kernels.h"
 #include "stereo_geometry.hpp"
+#include "draw_lists.hpp"
 
 namespace flame_hip {
 namespace {
@@ -510,14 +511,24 @@ __device__ __forceinline__ uint32_t fail_feature(const StereoParams& P, StereoFe
   return bits;
 }
 
+// The rectangle of the matches picture (flame.cc:1626-1631 and its siblings): kind and centre (C truncation; the cast saturates).
+__device__ __forceinline__ void record_rect(MatchRecord& r, uint32_t kind, V2 u_cmp) {
+  r.rect_x = (int)(u_cmp.x + 0.5f), r.rect_y = (int)(u_cmp.y + 0.5f);
+  r.flags |= kind + 1u;
+}
+
 // Returns the statistics counters this feature bumps (bit c = stats[c]); the kernel adds them up per wave.
-template <int G>
+// kRecord: the leader lane also writes what the feature draws into the matches picture (MatchRecord, stereo_kernels.h) at the
+// branches where the reference draws; nothing else differs.
+template <int G, bool kRecord>
 __device__ uint32_t update_one_feature(const StereoParams& P, const StereoCamera& cam, const int n_poses,
                                        const StereoPoseEntry* __restrict__ poses, const uint8_t* __restrict__ new_img,
                                        const float* __restrict__ new_gx, const float* __restrict__ new_gy, const uint32_t curr_pf_id,
-                                       const int i, const bool leader, StereoFeature* __restrict__ feats, int* __restrict__ stats) {
+                                       const int i, const bool leader, StereoFeature* __restrict__ feats, int* __restrict__ stats,
+                                       MatchRecord* __restrict__ records) {
   uint32_t bits = 0;
   StereoFeature f = feats[i];
+  MatchRecord rec = {};
   // pfs.at(fii.frame_id)
   int slot = -1;
   for (int k = 0; k < n_poses; ++k)
@@ -567,6 +578,7 @@ __device__ uint32_t update_one_feature(const StereoParams& P, const StereoCamera
       }
       if (mr != kYes || !rect_contains(vx, vy, vw, vh, u_pf)) {
         f.valid = 0;
+        if constexpr (kRecord) record_rect(rec, kMatchMoveFailed, u_cmp);
         break;
       }
       f.frame_id = curr_pf_id;
@@ -578,11 +590,14 @@ __device__ uint32_t update_one_feature(const StereoParams& P, const StereoCamera
       v4 *= v4;
       if ((double)idepth_pf < 1e-6) v4 = 1;
       f.idepth_var *= v4;
+      if constexpr (kRecord) record_rect(rec, kMatchMoved, u_cmp);
       break;
     }
     V2 u_start, u_end;
     const Outcome sr = search_region(P, geo, width, height, xy, f.idepth_mu, f.idepth_var, &u_start, &u_end);
     if (sr == kAssert) asserted = true;
+    if constexpr (kRecord)
+      if (sr == kNo) record_rect(rec, kMatchNoRegion, u_cmp);
     if (sr != kYes) break;
     if (!rect_contains(vx, vy, vw, vh, xy)) break;
     // inverse_depth_filter::search (inverse_depth_filter.cc:178-263), in padded coordinates
@@ -631,6 +646,16 @@ __device__ uint32_t update_one_feature(const StereoParams& P, const StereoCamera
       status = (r == 1) ? 2 : (r == 2) ? 3 : 0;
     }
     f.search_status = status;
+    if constexpr (kRecord)
+      if (status != 0) {  // (search writes u_cmp on success only: the rectangle sits at the predicted point; flame.cc:1698-1725)
+        record_rect(rec, status == 1 ? (f.num_updates == 0 ? kMatchNoGradientFresh : kMatchNoGradient)
+                                     : status == 2 ? kMatchAmbiguous : kMatchMaxCost, u_cmp);
+        int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+        const bool inside = round_inside(u_start.x, width - 1, &x1) && round_inside(u_start.y, height - 1, &y1) &&
+                            round_inside(u_end.x, width - 1, &x2) && round_inside(u_end.y, height - 1, &y2);
+        if (inside) rec.x1 = (int16_t)x1, rec.y1 = (int16_t)y1, rec.x2 = (int16_t)x2, rec.y2 = (int16_t)y2;
+        rec.flags |= inside ? kMatchLine : kMatchLineSkipped;
+      }
     if (status != 0) break;
     flow = {m.x - off, m.y - off};
     tracked = true;
@@ -721,6 +746,19 @@ __device__ uint32_t update_one_feature(const StereoParams& P, const StereoCamera
   }
   if (!updated) bits |= fail_feature(P, f);
   if (leader) feats[i] = f;
+  if constexpr (kRecord) {
+    if (bits & 6u) {  // the rings (flame.cc:1350-1357, 1365-1372): the record as it stands, the geometry loaded at :1316
+      V2 p;
+      float unused;
+      if (project_idepth(geo, cam, {f.x, f.y}, f.idepth_mu, &p, &unused)) {
+        rec.ring_x = (int)(p.x + 0.5f), rec.ring_y = (int)(p.y + 0.5f);
+        rec.flags |= ((bits & 2u) ? kMatchRingGreen : 0u) | ((bits & 4u) ? kMatchRingBlue : 0u);
+      } else {
+        rec.flags |= kMatchRingsSkipped | ((bits & 2u) ? kMatchRingGreen : 0u) | ((bits & 4u) ? kMatchRingBlue : 0u);
+      }
+    }
+    if (leader && rec.flags) records[i] = rec;
+  }
   return bits;
 }
 
@@ -730,15 +768,18 @@ __device__ uint32_t update_one_feature(const StereoParams& P, const StereoCamera
 // (ballot + popcount) and added with one atomic each into one of kStatSlots copies of the counter block: every feature
 // adding to the same six words made the kernel run at the speed of same-address atomics (2.9 ns per feature: 24 us at
 // 8.4 k features, 171 us at 57 k, whatever the rest of the kernel did).
-template <int G>
+template <int G, bool kRecord>
 __global__ __launch_bounds__(64) void k_update_feature_idepths(
     const StereoParams P, const StereoCamera cam, const int n_poses, const StereoPoseEntry* __restrict__ poses,
     const uint8_t* __restrict__ new_img, const float* __restrict__ new_gx, const float* __restrict__ new_gy,
-    const uint32_t curr_pf_id, const int n, StereoFeature* __restrict__ feats, int* __restrict__ stats) {
+    const uint32_t curr_pf_id, const int n, StereoFeature* __restrict__ feats, int* __restrict__ stats,
+    MatchRecord* __restrict__ records) {
   const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) / G);
   const bool leader = (threadIdx.x % G) == 0;
   uint32_t bits = 0;
-  if (i < n) bits = update_one_feature<G>(P, cam, n_poses, poses, new_img, new_gx, new_gy, curr_pf_id, i, leader, feats, stats);
+  if (i < n)
+    bits = update_one_feature<G, kRecord>(P, cam, n_poses, poses, new_img, new_gx, new_gy, curr_pf_id, i, leader, feats, stats,
+                                          records);
   if (!leader) bits = 0;
   int* slot = stats + kStatCount + (blockIdx.x % kStatSlots) * kStatSlotStride;
 #pragma unroll
@@ -785,15 +826,18 @@ __global__ __launch_bounds__(256) void k_frame_pad_gradient(const uint8_t* __res
 hipError_t launch_update_feature_idepths(const StereoParams& P, const StereoCamera& cam, int n_poses,
                                          const StereoPoseEntry* poses, const uint8_t* new_img, const float* new_gx,
                                          const float* new_gy, uint32_t curr_pf_id, int n, StereoFeature* feats, int* stats,
-                                         int lanes_per_feature, hipStream_t stream) {
+                                         int lanes_per_feature, MatchRecord* records, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   const int block = 64;  // one wave per workgroup, spread over the CUs: 8.5 k features are 2100 waves (133 at one lane each)
+  const dim3 grid16((n + 3) / 4), grid1((n + block - 1) / block);
+  auto launch = [&](auto kernel, dim3 grid) {
+    hipLaunchKernelGGL(kernel, grid, dim3(block), 0, stream, P, cam, n_poses, poses, new_img, new_gx, new_gy, curr_pf_id, n, feats,
+                       stats, records);
+  };
   if (lanes_per_feature == 16) {
-    hipLaunchKernelGGL(k_update_feature_idepths<16>, dim3((n + 3) / 4), dim3(block), 0, stream, P, cam, n_poses, poses, new_img,
-                       new_gx, new_gy, curr_pf_id, n, feats, stats);
+    if (records) launch(k_update_feature_idepths<16, true>, grid16); else launch(k_update_feature_idepths<16, false>, grid16);
   } else {
-    hipLaunchKernelGGL(k_update_feature_idepths<1>, dim3((n + block - 1) / block), dim3(block), 0, stream, P, cam, n_poses,
-                       poses, new_img, new_gx, new_gy, curr_pf_id, n, feats, stats);
+    if (records) launch(k_update_feature_idepths<1, true>, grid1); else launch(k_update_feature_idepths<1, false>, grid1);
   }
   return hipGetLastError();
 }

@@ -9,7 +9,8 @@
 //             reader of pos / x / tri_valid)
 //   count     one lane per draw walks its line: cnt[pixel] += 1
 //   offsets   every touched pixel takes a range of cnt[pixel] entries from one cursor, 1024 pixels of a wave at a time (placement is
-//             not deterministic and need not be: the fold orders by id)
+//             not deterministic and need not be: the fold orders by id); k_draw_offsets, draw_offsets.hpp, shared with the matches
+//             picture like the line walk (draw_lists.hpp)
 //   fill      one lane per draw walks again: (id << 32 | colour) into the pixel's range
 //   fold      per OUTPUT pixel, four per thread: the grey value, then the entries in increasing id, (c + v) >> 1 per channel
 // The fold takes the entries in order by selection (the smallest id above the last one taken) instead of sorting a copy: no
@@ -18,18 +19,12 @@
 #include <hip/hip_runtime.h>
 
 #include "debug_pixel.hpp"
+#include "draw_lists.hpp"
+#include "draw_offsets.hpp"
 #include "wireframe_kernels.h"
 
 namespace flame_hip {
 namespace {
-
-// cvRound of an endpoint coordinate and whether it lies in [0, hi]: a NaN, an infinity and anything that rounds outside fail.
-__device__ __forceinline__ bool round_inside(float v, int hi, int* out) {
-  const float r = rintf(v);  // round half to even, as __float2int_rn; compared as a float first: no cast of a huge value
-  if (!(r >= 0.0f && r <= (float)hi)) return false;
-  *out = (int)r;
-  return true;
-}
 
 __global__ void __launch_bounds__(256)
 k_wire_setup(int n_draws, const int32_t* __restrict__ tris, const float2* __restrict__ vtx, const float* __restrict__ x,
@@ -62,73 +57,15 @@ k_wire_setup(int n_draws, const int32_t* __restrict__ tris, const float2* __rest
   }
 }
 
-// cv::LineIterator (OpenCV 3.2, connectivity 8) from (x1, y1) to (x2, y2), restated (UNPINNED): f(ii, count, x, y) for each of
-// its count = max(|dx|, |dy|) + 1 pixels.  Every pixel lies in the endpoints' bounding box.
-template <class F>
-__device__ __forceinline__ void walk_line(const WireDraw& d, F f) {
-  int x = d.x1, y = d.y1;
-  int dx = (int)d.x2 - (int)d.x1, dy = (int)d.y2 - (int)d.y1;
-  const int sx = dx < 0 ? -1 : 1, sy = dy < 0 ? -1 : 1;
-  dx = dx < 0 ? -dx : dx, dy = dy < 0 ? -dy : dy;
-  int major_x = sx, major_y = 0, minor_x = 0, minor_y = sy;
-  if (dy > dx) {  // y is the major axis
-    const int t = dx;
-    dx = dy, dy = t;
-    major_x = 0, major_y = sy, minor_x = sx, minor_y = 0;
-  }
-  int err = dx - 2 * dy;
-  const int count = dx + 1;
-  for (int ii = 0; ii < count; ++ii) {
-    f(ii, count, x, y);
-    const bool m = err < 0;
-    err += -2 * dy + (m ? 2 * dx : 0);
-    x += major_x + (m ? minor_x : 0), y += major_y + (m ? minor_y : 0);
-  }
-}
-
 __global__ void __launch_bounds__(256)
 k_wire_count(int n_draws, const WireDraw* __restrict__ draws, int rows, int cols, uint32_t* __restrict__ cnt) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_draws) return;
   const WireDraw d = draws[i];
   if (d.x1 < 0) return;
-  walk_line(d, [&](int, int, int x, int y) {
+  walk_line(d.x1, d.y1, d.x2, d.y2, [&](int, int, int x, int y) {
     if ((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows) atomicAdd(&cnt[(long)y * cols + x], 1u);
   });
-}
-
-// offset[p] = the sum of cnt over the pixels that came before p at the cursor.  A lane sums kOffsetsPerLane consecutive pixels, the
-// wave scans its 64 sums with shuffles and takes its range with ONE atomicAdd: atomics on one address follow each other at about
-// 11 ns, and a wave per 64 pixels made this kernel the longest of the five (370 us at 1080p); a wave per 1024 pixels takes 2025.
-// No lane leaves before the shuffles.
-constexpr int kOffsetsPerLane = 16;
-
-__global__ void __launch_bounds__(256)
-k_wire_offsets(long n, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ offset, int* __restrict__ counts) {
-  const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * kOffsetsPerLane;
-  const int lane = threadIdx.x & 63;
-  uint32_t c[kOffsetsPerLane];
-  uint32_t sum = 0u;
-#pragma unroll
-  for (int k = 0; k < kOffsetsPerLane; ++k) {
-    c[k] = i0 + k < n ? cnt[i0 + k] : 0u;
-    sum += c[k];
-  }
-  uint32_t incl = sum;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const uint32_t v = __shfl_up(incl, s, 64);
-    if (lane >= s) incl += v;
-  }
-  uint32_t base = 0u;
-  if (lane == 63 && incl != 0u) base = atomicAdd((uint32_t*)&counts[kWireTotal], incl);
-  base = __shfl(base, 63, 64);
-  uint32_t at = base + (incl - sum);
-#pragma unroll
-  for (int k = 0; k < kOffsetsPerLane; ++k) {
-    if (i0 + k < n) offset[i0 + k] = at;
-    at += c[k];
-  }
 }
 
 __global__ void __launch_bounds__(256)
@@ -139,7 +76,7 @@ k_wire_fill(int n_draws, const WireDraw* __restrict__ draws, int rows, int cols,
   const WireDraw d = draws[i];
   if (d.x1 < 0) return;
   const float a_val = d.a_val, b_val = d.b_val;
-  walk_line(d, [&](int ii, int count, int x, int y) {
+  walk_line(d.x1, d.y1, d.x2, d.y2, [&](int ii, int count, int x, int y) {
     if (!((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows)) return;
     const float slope0 = (b_val - a_val) / (float)count;
     const float val = a_val + (float)ii * slope0;
@@ -210,7 +147,8 @@ int launch_wireframe_lists(int T, const int32_t* tris, const float2* vtx, const 
     if (e != hipSuccess) return (int)e;
   }
   if (n_draws > 0) hipLaunchKernelGGL(k_wire_count, grid1d(n_draws), dim3(256), 0, s, n_draws, b.draws, rows, cols, b.cnt);
-  hipLaunchKernelGGL(k_wire_offsets, grid1d((n + kOffsetsPerLane - 1) / kOffsetsPerLane), dim3(256), 0, s, n, b.cnt, b.offset, b.counts);
+  hipLaunchKernelGGL(k_draw_offsets, grid1d((n + kOffsetsPerLane - 1) / kOffsetsPerLane), dim3(256), 0, s, n, b.cnt, b.offset,
+                     (uint32_t*)&b.counts[kWireTotal]);
   return (int)hipGetLastError();
 }
 

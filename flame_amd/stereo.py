@@ -106,6 +106,15 @@ class _Stats(C.Structure):
                                           "success", "error_feature")]
 
 
+MATCH_KINDS = ("move_failed", "moved", "no_search_region", "no_gradient", "no_gradient_fresh", "ambiguous", "max_cost",
+               "max_var_ring", "max_dropouts_ring")  # flame_stereo_matches_stats.kind_count, in order
+
+
+class _MatchesStats(C.Structure):
+    _fields_ = [("num_features", C.c_int32), ("kind_count", C.c_int32 * 9), ("lines_drawn", C.c_int32),
+                ("lines_skipped", C.c_int32), ("rings_skipped", C.c_int32), ("refilled", C.c_int32), ("entries", C.c_int64)]
+
+
 STEREO_ABI_SYMBOLS = (
     "flame_stereo_default_params", "flame_stereo_create", "flame_stereo_destroy", "flame_stereo_set_stream",
     "flame_stereo_set_camera", "flame_stereo_add_frame", "flame_stereo_drop_frame", "flame_stereo_frame_count",
@@ -116,10 +125,11 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_projected_device", "flame_stereo_detect_features", "flame_stereo_prune_pose_frames",
     "flame_stereo_prune_features", "flame_stereo_clear_features", "flame_stereo_default_graph_params",
     "flame_stereo_select_graph_features", "flame_stereo_select_graph_features_arrays",
-    "flame_stereo_draw_features", "flame_stereo_frame_image_device",
+    "flame_stereo_draw_features", "flame_stereo_frame_image_device", "flame_stereo_draw_matches",
 )
 OPT_LANES_PER_FEATURE = 1
 OPT_GRAPH_COPY = 2
+OPT_RECORD_MATCHES = 3
 
 _READY = False
 _FP = C.POINTER(C.c_float)
@@ -176,6 +186,7 @@ def _lib():
             "flame_stereo_draw_features": (C.c_int, [ctx, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_void_p,
                                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
             "flame_stereo_frame_image_device": (C.c_int, [ctx, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+            "flame_stereo_draw_matches": (C.c_int, [ctx, C.c_int, C.c_void_p, C.POINTER(_MatchesStats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -347,6 +358,30 @@ class FeatureTracker:
                                                      C.c_float(scene_color_scale), int(bool(flip)), img.ctypes.data, C.byref(nc),
                                                      C.byref(nu)), "draw_features")
         return img, int(nc.value), int(nu.value)
+
+    def set_record_matches(self, on):
+        """FLAME_STEREO_OPT_RECORD_MATCHES: while on, every update also records what draw_matches paints (same feature
+        records, statistics and return codes)."""
+        self._chk(self._L.flame_stereo_set_option(self._ctx, OPT_RECORD_MATCHES, int(on)), "set_option")
+
+    def draw_matches(self, flip: bool = False, raise_on_error: bool = True):
+        """getDebugImageMatches (flame.cc:1293-1295 and the draws of updateFeatureIDepths / trackFeature) of the last update
+        that ran with set_record_matches(True), over the image of the frame it named as new.  Returns a dict: img
+        (height, width, 3) u8, num_features, kind_count (9 ints, MATCH_KINDS), lines_drawn, lines_skipped, rings_skipped,
+        entries, refilled; (status, dict or None) when raise_on_error is False."""
+        img = np.empty((self.height, self.width, 3), np.uint8)
+        st = _MatchesStats()
+        rc = self._L.flame_stereo_draw_matches(self._ctx, int(bool(flip)), img.ctypes.data, C.byref(st))
+        res = None
+        if rc == 0:
+            res = {n: int(getattr(st, n)) for n in ("num_features", "lines_drawn", "lines_skipped", "rings_skipped", "entries",
+                                                    "refilled")}
+            res["kind_count"] = [int(v) for v in st.kind_count]
+            res["img"] = img
+        if not raise_on_error:
+            return rc, res
+        self._chk(rc, "draw_matches")
+        return res
 
     def frame_image_device(self, frame_id: int):
         """(device address, step_bytes) of the unpadded image of a resident frame: Regularizer.debug_images(None, ...,

@@ -23,6 +23,11 @@
 //   here       flame_stereo_graph_inputs g = tracker.selectGraphFeatures(params, pfs_, graph_scale_);            // resident
 //              ... = tracker.selectGraphFeatures(params, pfs_, graph_scale_, feats_, feats_in_curr_);           // vectors
 //              g.feat_id / g.pos / g.data_term / g.data_weight go into DeviceGraph::syncPrepare as they are
+//   reference  getDebugImageMatches() (flame.h:294-306): the picture updateFeatureIDepths draws into its debug_img argument when
+//              params.debug_draw_matches is set (flame.cc:265-267, 1293-1295)
+//   here       tracker.recordMatches(params.debug_draw_matches);                 // once, e.g. beside the constructor
+//              tracker.updateFeatureIDepths(...);                                // any form
+//              tracker.getDebugImageMatches(params, debug_img_matches_.data);    // height * width * 3 bytes
 //   reference  Flame::getRawIDepths(&vertices, &idepths_mu, &idepths_var)  (flame.h:255-273)
 //   here       tracker.getRawIDepths(&vertices, &idepths_mu, &idepths_var);
 //
@@ -46,6 +51,8 @@
 #include "flame_stereo.h"
 
 namespace flame_hip {
+
+typedef flame_stereo_matches_stats MatchesStats;  // what getDebugImageMatches drew, by kind (flame_stereo.h)
 
 struct StereoError : std::runtime_error {
   int status;
@@ -279,6 +286,26 @@ class FeatureTracker {
                     int* num_unconverged = nullptr) {
     drawFeatures(fcur_id, params.idepth_var_max_graph, params.scene_color_scale, params.debug_flip_images, debug_img,
                  num_converged, num_unconverged);
+  }
+  // ---- getDebugImageMatches ----
+  // While on, every updateFeatureIDepths (and the resident forms of the C-ABI) also records what the reference draws into its
+  // debug_img argument with params.debug_draw_matches (flame.cc:1293-1295 and the draws of trackFeature); what the update
+  // computes and returns is the same.
+  void recordMatches(bool on) {
+    check(flame_stereo_set_option(ctx_, FLAME_STEREO_OPT_RECORD_MATCHES, on ? 1 : 0), -1, "flame_stereo_set_option");
+  }
+  // The picture of the last update, over the resident frame it named as new; debug_img: height * width * 3 bytes (cv::Vec3b,
+  // c[0], c[1], c[2]).  The text overlay (debug_draw_text_overlay) is not drawn.  Throws (FLAME_NLTGV2_ERR_INVALID_ARG) when no
+  // update ran since recordMatches(true), when it failed, or when that frame was dropped.
+  void getDebugImageMatches(uint8_t* debug_img, bool debug_flip_images, MatchesStats* stats = nullptr) {
+    check(flame_stereo_draw_matches(ctx_, debug_flip_images ? 1 : 0, debug_img, stats), -1, "flame_stereo_draw_matches");
+  }
+  // With the reference's parameters: nothing is drawn, and false returned, unless params.debug_draw_matches is set.
+  template <class FlameParams>
+  bool getDebugImageMatches(const FlameParams& params, uint8_t* debug_img, MatchesStats* stats = nullptr) {
+    if (!params.debug_draw_matches) return false;
+    getDebugImageMatches(debug_img, params.debug_flip_images ? true : false, stats);
+    return true;
   }
   // fnew_->img[0] of a resident frame in device memory (address, pitch): what DeviceGraph::debugImagesBegin takes as
   // img_device.  Valid until the frame is dropped or replaced.

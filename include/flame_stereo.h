@@ -16,7 +16,8 @@
  * pose algebra (Sophus::SE3f products, flame.cc:1315-1316, 1614) and passes one (quaternion, translation) pair
  * per pose-frame; everything from EpipolarGeometry::loadGeometry down runs on the GPU, a 16-lane row per feature.
  * Results are bit-identical to the reference's scalar float code (same expression order, no FMA contraction).
- * Debug drawing (params.debug_draw_matches) and the stderr diagnostics are not part of the path.
+ * Debug drawing (params.debug_draw_matches) is optional: flame_stereo_draw_matches, below.  The stderr diagnostics are not part
+ * of the path.
  *
  * Status codes are flame_nltgv2_status (flame_nltgv2.h).  Where the reference would FLAME_ASSERT -> exit(1)
  * (negative inverse depth into project(), a sample outside the padded image, ...), the call returns
@@ -390,16 +391,84 @@ int flame_stereo_draw_features(flame_stereo_ctx* ctx, uint32_t cur_frame_id, flo
  * dropped or replaced (add_frame with the same id, set_camera). */
 int flame_stereo_frame_image_device(flame_stereo_ctx* ctx, uint32_t frame_id, const void** img, int* step_bytes);
 
+/* ---- getDebugImageMatches (flame.h:294-306) -------------------------------------------------------------------------
+ * The picture updateFeatureIDepths / trackFeature draw with params.debug_draw_matches (flame.cc:265-267, 1293-1295): why each
+ * feature failed this frame.  With FLAME_STEREO_OPT_RECORD_MATCHES on, all three update entry points (update_resident,
+ * update_feature_idepths, update_feature_idepths_device) run the recording instance of the update kernel, which also writes one
+ * 32-byte draw record per feature at the branches where the reference draws, and the context keeps the records of the LAST
+ * update with its new_frame_id and feature count.  Feature records, flame_stereo_stats and return codes are bit-identical to
+ * the option off (the default), which launches the kernels it always launched.  flame_stereo_draw_matches paints the records
+ * over the image of the frame that update named as new.  The rule, restated by tests/matches_ref.py (the checker; like the rest
+ * of the front-end not pinned to the reference binary):
+ *   1. Order.  The reference's `omp parallel for` (flame.cc:1307) is inert (-fopenmp is never set): the loop is sequential in
+ *      feature index.  Feature i issues at most four draws, draw id = 4 i + k.  Rectangles and rings overwrite, the segment
+ *      blends; a pixel's final value is the fold, in increasing draw id, over the draws that touch it.
+ *   2. Base image: cvtColor(fnew.img[0], GRAY2RGB), three equal bytes.  Colours are the bytes c[0], c[1], c[2] in memory.
+ *   3. k = 0, a filled rectangle (cv::rectangle, thickness -1, both corners inclusive, clipped to the image) of half-width
+ *      r1 = width / 320 (integer division; 0 below 320 columns: a single pixel) around ((int)(u_cmp.x + 0.5f),
+ *      (int)(u_cmp.y + 0.5f)), C truncation, u_cmp = the point the FIRST predict returned (search writes it on success only,
+ *      line_stereo.h:381-382).  kind_count index, outcome, where, colour:
+ *        0  move to the newest pose-frame failed   flame.cc:1624-1632   (0, 51, 102)
+ *        1  moved                                  :1651-1656           (255, 0, 255)
+ *        2  getSearchRegion false                  :1667-1674           (0, 0, 0)
+ *        3  search: FAIL_REF_PATCH_GRADIENT        :1703-1707           (255, 255, 0)
+ *        4  the same with num_updates == 0         :1705-1707           (255, 255, 255)
+ *        5  search: FAIL_AMBIGUOUS_MATCH           :1708                (0, 0, 255)
+ *        6  search: FAIL_MAX_COST                  :1710                (0, 255, 255)
+ *      Nothing is drawn for the baseline skip (:1321), a failed first predict (:1561), !valid_region.contains(feat->xy)
+ *      (:1680) and a success.
+ *   4. k = 1, only after a failed search (:1723-1724): applyColorMapLine(u_start, u_end, 1, 1, the rectangle's colour, 0.5)
+ *      (utils/visualization.h:236-260).  Endpoints are rounded as cv::LineIterator takes them (cvRound: to nearest, ties to
+ *      even) and walked as flame_nltgv2_debug_wireframe walks (flame_nltgv2.h); per visited pixel and channel
+ *      colour * 0.5f + pixel * 0.5f truncated to a byte, which is exact in float and equals (colour + pixel) >> 1.
+ *      getSearchRegion clips to [1, width - 1] x [1, height - 1], so a rounded endpoint is never outside the image; if one
+ *      is (or is not finite) the segment is left out and counted in lines_skipped, as the wireframe does.
+ *   5. k = 2, a green ring (0, 255, 0) when this frame's failure pushed idepth_var over idepth_var_max (:1350, 1405, 1454;
+ *      kind_count[7]); k = 3, a blue ring (255, 0, 0) when num_dropouts > max_dropouts (:1365, 1420, 1469; kind_count[8]).
+ *      cv::circle(centre, r2 = 4 * width / 320, colour): thickness 1, LINE_8.  centre = ((int)(p.x + 0.5f), (int)(p.y + 0.5f)),
+ *      p = epigeo.project(fii.xy, fii.idepth_mu) with the geometry loaded at :1316 and the record AS IT STANDS at that moment:
+ *      after a successful move xy and idepth_mu are those in the newest pose-frame while the geometry is the old anchor's.
+ *      Kept as written.
+ *   6. After all draws flip != 0 reverses the linear pixel order (cv::flip(img, img, -1)); debug_draw_text_overlay
+ *      (cv::putText) is treated as false.
+ * UNPINNED (OpenCV is not part of this tree; restated here and in the checker): cv::rectangle's fill rule, the line walk, and
+ * the ring's pixel set: err = 0, dx = r, dy = 0, plus = 1, minus = 2 r - 1; while dx >= dy: plot the eight points
+ * (cx +- dx, cy +- dy), (cx +- dy, cy +- dx), each clipped to the image on its own (coinciding points once); dy += 1,
+ * err += plus, plus += 2; if err > 0: err -= minus, dx -= 1, minus -= 2.  (r = 4: 20 pixels, r = 8: 44, r = 24: 132.)
+ * UNPINNED too: a coordinate that does not fit an int, or is NaN, is undefined in the reference; here the cast saturates and a
+ * NaN gives 0, as in flame_stereo_draw_features.
+ * ONE DELIBERATE DEVIATION: the ring's centre goes through project(), which can FLAME_ASSERT (a negative or NaN idepth_mu, a
+ * zero third coordinate).  Recording never changes what the update computes or returns: a ring whose projection would assert
+ * is not drawn and is counted in rings_skipped. */
+typedef struct flame_stereo_matches_stats {
+  int32_t num_features;   /* records of the update the picture shows */
+  int32_t kind_count[9];  /* draws by kind: the seven rectangles in the order of rule 3, then the green and the blue rings */
+  int32_t lines_drawn;    /* searched segments blended in */
+  int32_t lines_skipped;  /* ... left out (rule 4) */
+  int32_t rings_skipped;  /* rings left out because their projection would assert */
+  int32_t refilled;       /* 1: the entry buffer was too small, fill and fold ran twice */
+  int64_t entries;        /* pixels touched, summed over the draws (clipped to the image) */
+} flame_stereo_matches_stats;
+/* Paints the records of the last update over the image of the frame that update named as new.  FLAME_NLTGV2_ERR_INVALID_ARG
+ * when no records stand (the option is off, no update ran with it on, the last update returned an error, or set_camera came
+ * since) or when that frame is no longer resident.  img_out: height * width * 3 bytes of host memory; `stats` may be NULL.
+ * The fold's entry buffer holds max(2 * height * width, 1.25 x the previous call's entries); a call that needs more grows
+ * it, repeats fill and fold and reports refilled = 1 (the wireframe's contract).  Enqueues on the context's stream and waits
+ * once (twice when it refills), so it is ordered behind an enqueue-only update; flame_stereo_last_kernel_ms covers its
+ * kernels. */
+int flame_stereo_draw_matches(flame_stereo_ctx* ctx, int flip, uint8_t* img_out, flame_stereo_matches_stats* stats);
+
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
  * bit for bit.  GRAPH_COPY: how select_graph_features brings its arrays down: 0 (default) the whole output block in one
  * copy and one wait, its sections spaced by the record count; 1 the counters first, then 24 bytes per selected vertex
- * (two waits); same results (profiles/graph_inputs.txt has both timings). */
-enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1, FLAME_STEREO_OPT_GRAPH_COPY = 2 };
+ * (two waits); same results (profiles/graph_inputs.txt has both timings).  RECORD_MATCHES: 0 (default) or 1: the updates also
+ * record what flame_stereo_draw_matches paints; same feature records, statistics and return codes. */
+enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1, FLAME_STEREO_OPT_GRAPH_COPY = 2, FLAME_STEREO_OPT_RECORD_MATCHES = 3 };
 int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value);
 
 /* Device time of the last update kernel (or of the kernels of the last project_features / detect_features /
- * prune_pose_frames / prune_features / select_graph_features[_arrays]) in
+ * prune_pose_frames / prune_features / select_graph_features[_arrays] / draw_matches) in
  * milliseconds (HIP events on the context's stream); < 0 if none. */
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx);
 int flame_stereo_last_hip_error(const flame_stereo_ctx* ctx);
