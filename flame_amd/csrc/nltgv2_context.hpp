@@ -31,6 +31,7 @@
 #include "flame_nltgv2_test_options.h"
 #include "nltgv2_kernels.h"
 #include "nltgv2_pack.hpp"
+#include "nltgv2_plan.hpp"
 #include "roctx_ranges.hpp"
 
 namespace flame_hip {
@@ -42,26 +43,12 @@ constexpr int kTvLdsWavesPerCu = 16;   // ... with the slot constants in LDS (<=
 constexpr size_t kXbufBytesPerVertex = 8 * 16 + 4;  // exchange buffers: up to four step buffers x (remote + same-XCD copy) of
                                                     // 16-byte records (the patch-per-wave form; the others use two) + the XCC table
 constexpr int kPv2FromPerCu = 14;       // from this many one-half-edge patches per CU on, the two-half-edges-per-lane form (k_persistent_pv2) runs the graph
-constexpr int kPv2PaceAbovePerCu = 10, kPv2DensePreSleep = 2, kPv2DenseGap = 2;  // its polls are paced from this many of its waves per CU (x64 cycles before the first poll / between rounds)
 constexpr int kPv2MaxGroups = 2;        // ... in at most this many launch groups of whole frames (11-20 frames of 640x480: 9-18 % faster than the vertex-per-lane form)
 constexpr int kPv2WavesPerCu = 19;     // ... up to this many of ITS waves per CU (20 really resident: 91 VGPRs)
 constexpr int kCrowdedWavesPerCu = 16, kCrowdedTopologies = 64;  // (see flame_nltgv2_ctx::crowded_until_topo)
 constexpr int kPvDensePerCu = 27;      // k_persistent_pv is used up to this many patches per CU (28 are resident: 7 waves per SIMD at <= 96 SGPRs)
-constexpr int kPvPaceAbovePerCu = 13;  // ... and above this many its polls are paced (kPvDensePreSleep, kPvDenseGap)
-constexpr int kPvDensePreSleep = 3, kPvDenseGap = 2;  // x64 cycles before the first poll of a step / between poll rounds (re-swept
-                                                      // with the issue priorities in: 8 / 4 before them; profiles/r03_priority.txt)
-constexpr int kPvPaceMoreAbovePerCu = 23;  // ... and above this many more slowly (a 1080p frame: 25 per CU)
-constexpr int kPvDenserPreSleep = 5, kPvDenserGap = 4;
-constexpr int kPvPreSleep = 0;         // k_persistent_pv: x64 cycles between a step's start and its first poll
-constexpr int kPvPollGap = 2;          // k_persistent_pv polls: re-loading only the fetch entries still waiting, no pause between
-                                       // rounds (with the round-2 first form of the kernel an s_sleep between rounds won by 1-3 %;
-                                       // with the shorter hand-off path of its final form no pause wins by 3-4 % at 640x480)
-constexpr int kDualMinWavesPerCu = 0;  // auto: exchange through the XCD's L2 when more waves than this share a CU
-// x64-cycle sleep between publishing and the first neighbour poll of k_persistent_tv (insensitive, shortest wins)
-constexpr int kPreSleepTv = 2;
 constexpr int32_t kFeatDirectMax = 1 << 22;  // sync_graph: feature ids below this are looked up in a plain table (16 MB at most), others hashed
 constexpr size_t kErrBytes = 16 * sizeof(int);  // the flag word + what the first expired wait reports (report_expired)
-constexpr unsigned kMaxSpins = 1u << 20;  // bound of every neighbour wait in the persistent run (~1 s of polling bursts)
 
 struct DevBuf {
   void* p = nullptr;
@@ -393,11 +380,10 @@ struct flame_nltgv2_ctx {
   // flame_nltgv2_stream_wait_run / _runs_in_flight: the last plain persistent launch of a run carries one of these two events (in turn) as
   // its own completion signal (hipExtLaunchKernel's stop event: no operation of its own on the solver's in-order queue)
   hipEvent_t ev_run[2] = {nullptr, nullptr};
-  int run_ev_pick = -1, run_ev_last = 0;          // the event the run being enqueued may bind / the one of the last enqueued run
+  int run_ev_last = 0;                           // the event of the last enqueued run
   bool run_ev_valid[2] = {false, false};         // the event stands for a run (bound to its launch, or recorded behind it)
   bool track_runs = false;                       // somebody asks runs_in_flight: a run whose launch cannot carry the event gets it recorded
-  bool run_event_bound = false;  // ev_run[run_ev_last] was carried by the last enqueued run's own launch ...
-  uint64_t call_seq = 0, run_event_seq = 0;  // ... as long as no other call into the context followed it (enter() counts the calls)
+  uint64_t call_seq = 0, run_event_seq = 0;      // calls into the context (enter() counts them) / the call that enqueued the last run
   std::vector<float> h_terms;
   DevBuf hq_alt, vstate_alt;  // the other copies of hq / vstate: a persistent run writes there, success swaps the roles
   DevBuf xbuf, abort_flag, tv_slot, tv_vid, tv_meta, tv_wave, wg2_slot, wg2_vid, wg2_meta, wg2_nbr, wg2_fetch, wg2_info, wg2_vfirst, wg2_rmax;
@@ -416,7 +402,6 @@ struct flame_nltgv2_ctx {
   bool open_inflight = false; // an open run is enqueued and unchecked (the last op of ctx->pending)
   bool open_stop_sent = false; // ... and has been asked to stop (request_open_stop)
   uint32_t open_tag0 = 0;      // ... its first tag: what a request to stop it says
-  int want_open = 0;          // enqueue_run: the run being enqueued is to be an open one (flame_nltgv2_run_open sets it for its call)
   int last_open_iters = 0;    // how far the last open run went
   int64_t iters_total = 0;    // iterations applied to the state by every run since create (open runs: counted when they are settled)
   DevBuf pos_undo;            // project_graph: the positions as they stood (when layout_pos already holds older ones), to take a projection back
@@ -535,7 +520,9 @@ struct PhotoStale {
   ~PhotoStale() { ctx->photo_fresh = false; }
 };
 int enqueue_photo_sweep(flame_nltgv2_ctx* ctx, bool packed_current);
-int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n);
+// n steps enqueued on the context's stream.  ask_open: as an open run, or not at all (*opened: it was).  bind_event: which of ev_run the
+// run's last launch may carry as its completion signal, -1 none (*event_bound: it does).
+int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n, bool ask_open, int bind_event, bool* opened, bool* event_bound);
 // reads the error word; rolls a failed persistent run back and redoes it.  unpack_behind: the unpack of the state is enqueued before the
 // host waits (*unpacked: it was, and the runs went through -- the canonical arrays are current)
 int finish(flame_nltgv2_ctx* ctx, bool unpack_behind = false, bool* unpacked = nullptr, const std::function<int()>* behind = nullptr,

@@ -15,19 +15,6 @@ void pick_config(const flame_nltgv2_ctx* ctx, int* unroll, int* wpb) {
   *wpb = ctx->opt_block_waves ? ctx->opt_block_waves : (small ? 1 : 4);
 }
 
-// A persistent launch covers a contiguous range of waves of one form.
-struct WaveGroup {
-  int begin, count;
-};
-
-// Which persistent form (if any) runs n steps -- 0 none (one launch per step), 1 lane-per-half-edge
-// (lowest latency), 2 vertex-per-lane (fewest instructions) -- and over which wave groups.  A graph that
-// is resident as a whole is one group.  A disjoint union too large for that (a big batch of frames) is run
-// group of connected components by group, each group resident on its own: the components are independent,
-// so running them one after the other for all n steps is exactly the same computation.
-int ensure_form_rows(flame_nltgv2_ctx* ctx, int form);
-int plan_groups(flame_nltgv2_ctx* ctx, int form, int total, int cap, const std::vector<int32_t>& cw, std::vector<WaveGroup>* groups);
-
 // Cooperative launches and rocprofiler-sdk do not end well together (ROCm 7.2): a process that runs under rocprofv3 and has made ONE
 // cooperative launch -- of any kernel: tools/coop_exit_repro.hip is 30 lines without this library -- dies with SIGSEGV inside
 // libhsa-runtime64 when the HIP runtime's static destructor (amd::Runtime::tearDown) takes the device's cooperative queue down after the
@@ -50,23 +37,11 @@ bool cooperative_allowed() {
   return ok;
 }
 
-// Where the lean patch kernel (k_persistent_pv_lean, nltgv2_persistent_lean.hip) runs instead of k_persistent_pv: a run of the patch-per-wave form
-// as ONE launch of what would be the plain instance -- no probe, no verification, not an open run, not a replay, no fault injection -- with
-// the default poll gap and pre-sleep, the same-XCD exchange on, below the paced regime, every patch resident under ITS register counts,
-// and no vertex of more than 16 edges.  Everything else runs the general kernel exactly as before.  (FLAME_NLTGV2_OPT_PV_LEAN: 1 = never,
-// 2 = or the run fails.)
-static bool pv_lean_applies(const flame_nltgv2_ctx* ctx, int form, const std::vector<WaveGroup>& groups, bool open_run) {
-  if (form != 3 || groups.size() != 1 || ctx->opt_pv_lean == 1) return false;
-  if (ctx->opt_probe != 0 || ctx->opt_verify != 0 || open_run || ctx->replaying != 0 || ctx->opt_fault != 0) return false;
-  if (ctx->opt_poll_gap != 0 || ctx->opt_presleep != 0) return false;
-  const int cus = ctx->prop.multiProcessorCount, count = groups[0].count;
-  const bool dual_on = ctx->opt_dual == 2 || (ctx->opt_dual == 1 && count > kDualMinWavesPerCu * cus);
-  if (!dual_on || count > kPvPaceAbovePerCu * cus) return false;
-  if (ctx->L.max_degree > 16 || !ctx->L.wg_rowpack) return false;
-  if (ctx->pv_lean_occ_topo != ctx->topo) ctx->pv_lean_occ = pv_lean_patches_per_cu(ctx->f), ctx->pv_lean_occ_topo = ctx->topo;
-  return count <= ctx->pv_lean_occ * cus;
-}
-
+// Which persistent form (if any) runs n steps -- 0 none (one launch per step), 1 lane-per-half-edge
+// (lowest latency), 2 vertex-per-lane (fewest instructions) -- and over which wave groups.  A graph that
+// is resident as a whole is one group.  A disjoint union too large for that (a big batch of frames) is run
+// group of connected components by group, each group resident on its own: the components are independent,
+// so running them one after the other for all n steps is exactly the same computation.
 // `consume`: the call plans a run that is about to be enqueued (enqueue_run) -- only then does a planned-around run count against
 // the back-off after an expired wait; a query (persistent_eligible, prepare_run) leaves the bookkeeping alone.
 int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups, bool consume = false) {
@@ -151,57 +126,13 @@ int plan_persistent(flame_nltgv2_ctx* ctx, int n, std::vector<WaveGroup>* groups
     if (!ok2) {
       if (ensure_form_rows(ctx, 2) != 0 || !L.tv_ok) return 0;
       groups->clear();
-      return plan_groups(ctx, 2, L.tv_waves, kTvLdsWavesPerCu * cus, L.comp_tv_wave, groups);
+      return plan_groups(2, L.tv_waves, kTvLdsWavesPerCu * cus, L.comp_tv_wave, groups);
     }
   }
   const std::vector<int32_t>& cw = form == 4 ? L.comp_wg2 : form == 3 ? L.comp_wg : L.comp_tv_wave;
-  return plan_groups(ctx, form, total, cap, cw, groups);
+  return plan_groups(form, total, cap, cw, groups);
 }
 
-// `total` waves of `form` over groups of whole components (cw: first wave of every component), each at most `cap` waves.
-int plan_groups(flame_nltgv2_ctx* ctx, int form, int total, int cap, const std::vector<int32_t>& cw, std::vector<WaveGroup>* groups) {
-  (void)ctx;
-  if (total <= cap) {
-    groups->push_back(WaveGroup{0, total});
-    return form;
-  }
-  if (cw.size() < 3) return 0;  // one component that does not fit: stream it
-  // Groups of about equal size (the per-step time of a group grows with its waves, and a small last group would run
-  // at low occupancy): cut at the component boundaries nearest to k * total / n_groups, never beyond what the chip
-  // holds; if the components are too uneven for that, fall back to filling each group greedily.
-  for (size_t c = 0; c + 1 < cw.size(); ++c)
-    if (cw[c + 1] - cw[c] > cap) return 0;  // a single component larger than the chip
-  const int n_groups = (total + cap - 1) / cap;
-  bool ok = true;
-  {
-    size_t c = 0;
-    int begin = cw[0];
-    for (int gi = 1; gi <= n_groups && ok; ++gi) {
-      const long ideal = cw[0] + (long)gi * total / n_groups;
-      size_t e = c + 1;  // at least one component per group
-      while (e + 1 < cw.size() && cw[e] < ideal) ++e;
-      if (gi == n_groups) e = cw.size() - 1;
-      while (e > c + 1 && cw[e] - begin > cap) --e;
-      if (cw[e] - begin > cap) ok = false;
-      groups->push_back(WaveGroup{begin, cw[e] - begin});
-      begin = cw[e], c = e;
-      if (c + 1 >= cw.size() && gi < n_groups) break;
-    }
-    if (ok && begin != cw.back()) ok = false;  // balanced cuts did not cover everything within n_groups groups
-  }
-  if (!ok) {
-    groups->clear();
-    int begin = cw[0];
-    for (size_t c = 0; c + 1 < cw.size(); ++c) {
-      if (cw[c + 1] - begin > cap) {
-        groups->push_back(WaveGroup{begin, cw[c] - begin});
-        begin = cw[c];
-      }
-    }
-    groups->push_back(WaveGroup{begin, cw.back() - begin});
-  }
-  return form;
-}
 bool persistent_eligible(flame_nltgv2_ctx* ctx, int n) {
   std::vector<WaveGroup> g;
   return plan_persistent(ctx, n, &g) != 0;
@@ -477,270 +408,248 @@ int place_records(flame_nltgv2_ctx* ctx, int per_xcd) {
   return 0;
 }
 
-// An open run: ONE launch of the patch-per-wave form or of the two-half-edges form.  Their OPEN instances keep fewer patches resident than
-// the plain ones (24 instead of 28 per CU; 16 instead of 20: tests/test_abi.py): graphs of at most 20 / 14 patches per CU.
-static bool open_run_applies(const flame_nltgv2_ctx* ctx, int form, const std::vector<WaveGroup>& groups) {
-  if (groups.size() != 1) return false;
-  const int cus = ctx->prop.multiProcessorCount;
-  return (form == 3 && groups[0].count <= 20 * cus) || (form == 4 && groups[0].count <= 14 * cus);
+// A run is decided ONCE, before anything is enqueued for it: the persistent form and its wave groups (plan_persistent), whether it is an
+// open run, whether the lean patch kernel runs it, the key of its kernel instance and what the launch of every group is given
+// (nltgv2_plan.hpp).  The steps of enqueue_run below only carry the plan out.
+struct RunPlan {
+  int form = 0;  // 0: one launch per step
+  std::vector<WaveGroup> groups;
+  std::vector<GroupLaunch> launch;  // per group
+  bool open = false, lean = false;
+  uint64_t coop_key = 0;  // (topology, form, kernel instance): a new instance -- other registers, other LDS -- gets a cooperative first launch
+};
+
+// The request: n steps, as an open run if `ask_open` (pl.open says whether it can be one); `consume` as for plan_persistent.
+static RunPlan plan_run(flame_nltgv2_ctx* ctx, int n, bool ask_open, bool consume) {
+  RunPlan pl;
+  if (ctx->opt_solver == 1) return pl;  // the canonical sweeps: no persistent form, no open run
+  pl.form = plan_persistent(ctx, n, &pl.groups, consume);
+  if (pl.form == 0) return pl;
+  PlanOptions o;
+  o.dual = ctx->opt_dual, o.xcds = ctx->opt_xcds, o.poll_gap = ctx->opt_poll_gap, o.presleep = ctx->opt_presleep, o.verify = ctx->opt_verify;
+  o.probe = ctx->opt_probe, o.fault = ctx->opt_fault, o.pv_lean = ctx->opt_pv_lean, o.replaying = ctx->replaying;
+  const int cus = ctx->prop.multiProcessorCount, count0 = pl.groups[0].count;
+  // (an open run also needs the channel its request to stop travels on)
+  pl.open = ask_open && open_run_applies(pl.form, pl.groups.size(), count0, cus, n, o) && ctx->h_stop != nullptr && ctx->ctl_stream != nullptr;
+  // the lean kernel: every patch resident under ITS register counts, and no vertex of more than 16 edges
+  if (pv_lean_may_apply(pl.form, pl.groups.size(), count0, cus, pl.open, o) && ctx->L.max_degree <= 16 && ctx->L.wg_rowpack) {
+    if (ctx->pv_lean_occ_topo != ctx->topo) ctx->pv_lean_occ = pv_lean_patches_per_cu(ctx->f), ctx->pv_lean_occ_topo = ctx->topo;
+    pl.lean = count0 <= ctx->pv_lean_occ * cus;
+  }
+  pl.coop_key = ctx->topo * 1024 + (uint64_t)pl.form * 64 + (o.verify != 0 ? 16 : 0) + (o.probe != 0 ? 8 : 0) +
+                (o.dual == 2 ? 4 : o.dual == 1 ? 2 : 0) + (o.xcds > 0 ? 1 : 0) + (pl.lean ? 32 : 0);
+  for (const WaveGroup& gr : pl.groups) {
+    GroupLaunch g = group_launch(pl.form, gr.count, cus, o);
+    g.place = pl.form == 3 && ctx->opt_place && pl.groups.size() == 1 && gr.begin == 0 && g.xcds == 8 && (g.dual & 1);
+    pl.launch.push_back(g);
+  }
+  return pl;
 }
 
-int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
-  if (n <= 0) return 0;
-  if (ctx->open_inflight) {  // nothing is chained behind an open run: it would wait for the run's upper bound
-    const int rc0 = finish(ctx);
-    if (rc0) return rc0;
+// a run (kind 0) joins the list of what finish() redoes if a wait of the chain expires
+static void push_pending_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n, bool open, uint32_t tag0) {
+  flame_nltgv2_ctx::PendingOp op;
+  op.kind = 0, op.params = *p, op.n = n;
+  op.open = open, op.tag0 = tag0;
+  op.dst = ctx->export_ptr, op.scale = ctx->export_scale;  // the standing export target THIS run was enqueued with
+  ctx->pending.ops.push_back(op);
+}
+
+// Step 1: FLAME_NLTGV2_OPT_SOLVER = 1, the canonical 4-sweep path
+static int run_canonical(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
+  int rc = ensure_canon(ctx);  // (settles a pending persistent run first)
+  if (rc) return rc;
+  const SolverParams sp = to_sp(p);
+  for (int it = 0; it < n; ++it) {
+    LAUNCHCHK(ctx, launch_save_prev(ctx->c, ctx->stream));
+    LAUNCHCHK(ctx, launch_dual(ctx->c, sp, ctx->stream));
+    LAUNCHCHK(ctx, launch_primal(ctx->c, sp, ctx->stream));
+    LAUNCHCHK(ctx, launch_extragradient(ctx->c, sp, ctx->stream));
   }
-  if (ctx->opt_solver == 1) {  // canonical 4-sweep path
-    int rc = ensure_canon(ctx);  // (settles a pending persistent run first)
-    if (rc) return rc;
-    const SolverParams sp = to_sp(p);
-    for (int it = 0; it < n; ++it) {
-      LAUNCHCHK(ctx, launch_save_prev(ctx->c, ctx->stream));
-      LAUNCHCHK(ctx, launch_dual(ctx->c, sp, ctx->stream));
-      LAUNCHCHK(ctx, launch_primal(ctx->c, sp, ctx->stream));
-      LAUNCHCHK(ctx, launch_extragradient(ctx->c, sp, ctx->stream));
-    }
-    ctx->fused_valid = false;
-    ctx->last_run_path = 4;
-    if (ctx->replaying == 0) ctx->iters_total += n;
-    if (ctx->export_ptr) LAUNCHCHK(ctx, launch_export(ctx->c, ctx->f, false, ctx->export_scale, ctx->export_ptr, ctx->stream));
-    return enqueue_photo_sweep(ctx, false);
-  }
+  ctx->fused_valid = false;
+  ctx->last_run_path = 4;
+  if (ctx->replaying == 0) ctx->iters_total += n;
+  if (ctx->export_ptr) LAUNCHCHK(ctx, launch_export(ctx->c, ctx->f, false, ctx->export_scale, ctx->export_ptr, ctx->stream));
+  return enqueue_photo_sweep(ctx, false);
+}
+
+// Step 2: the state in its packed form; a run that follows an unchecked persistent run is chained onto it
+static int chain_onto_pending(flame_nltgv2_ctx* ctx) {
   if (ctx->opt_mesh_state == 1 && ctx->canon_valid) {
     // FLAME_NLTGV2_OPT_MESH_STATE = 1: the canonical arrays stand as they are until the next unpack (the runs work on the packed
     // copies); interpolate_mesh_begin may read them beside the runs once everything enqueued so far -- their writers -- is through
     HIPCHK(ctx, hipEventRecord(ctx->ev_snap, ctx->stream));
     ctx->snap_topo = ctx->topo;
   }
-  int rc = ensure_fused(ctx);
-  if (rc) return rc;
-  if (ctx->pending.active) {  // chaining onto an unchecked persistent run
-    if (ctx->pending.ops.size() >= kMaxChain) {
-      rc = finish(ctx);
-    } else {
-      rc = snapshot_chain_start(ctx);
+  const int rc = ensure_fused(ctx);
+  if (rc || !ctx->pending.active) return rc;
+  return ctx->pending.ops.size() >= kMaxChain ? finish(ctx) : snapshot_chain_start(ctx);
+}
+
+// Step 3: the run's first tag; the record buffers are cleared where its tags could meet older ones
+static int next_run_tags(flame_nltgv2_ctx* ctx, int form, int n, uint32_t* tag0) {
+  // tags must stay unique: clear the record buffers long before the 28-bit tag of the XCC table wraps -- and when the
+  // form changes (the forms lay the buffers out differently: one's XCC table is another's record area)
+  if ((uint64_t)ctx->tag_next + (uint64_t)n >= 0x07ff0000ull || (ctx->xbuf_form != 0 && ctx->xbuf_form != form)) {
+    const size_t bytes = kXbufBytesPerVertex * records_capacity(ctx->L);
+    HIPCHK(ctx, hipMemsetAsync(ctx->xbuf.p, 0, bytes, ctx->stream));
+    if (ctx->place_base) {
+      HIPCHK(ctx, hipMemsetAsync(ctx->place_base, 0, (size_t)2 * kPlacePages * 4096, ctx->stream));
+      HIPCHK(ctx, hipMemsetAsync((int*)ctx->place_fill.p + 2 * kPlacePages, 0, 64, ctx->stream));
     }
-    if (rc) return rc;
+    HIPCHK(ctx, hipMemsetAsync((int*)ctx->err.p + 12, 0, 2 * sizeof(int), ctx->stream));  // (an open run's words count from its tag0)
+    ctx->tag_next = 1;
   }
+  ctx->xbuf_form = form;
+  // a fresh first tag per run: records left by earlier runs (whose state may since have been changed
+  // by per-step launches or host uploads) can never satisfy a wait of this one
+  *tag0 = ctx->tag_next + 2;
+  return 0;
+}
+
+// Step 4: standing outputs -- the small block the kernels read in their epilogue, (re)sent when no slot holds it
+static int run_tail_slot(flame_nltgv2_ctx* ctx, const RunPlan& pl, uint32_t tag0, const RunTail** tail_dev) {
+  RunTail want;
+  std::memset(static_cast<void*>(&want), 0, sizeof want);
+  want.export_out = ctx->export_ptr, want.export_scale = ctx->export_scale;
+  int rc = 0;
+  if (pl.open) {  // the request word: device memory; a request names the run it is for (its tag0), so the word is never cleared
+    const bool fresh = ctx->stop_dev.p == nullptr;
+    rc = ensure(ctx, ctx->stop_dev, 64);
+    if (rc) return rc;
+    if (fresh) HIPCHK(ctx, hipMemsetAsync(ctx->stop_dev.p, 0, 64, ctx->stream));
+    ctx->open_tag0 = tag0;
+    want.stop_req = (const unsigned*)ctx->stop_dev.p;
+  }
+  const PhotoFuse pf = photo_target(ctx);
+  std::memcpy(static_cast<void*>(&want.photo), &pf, sizeof pf);
+  if (pl.form == 3 && std::getenv("FLAME_NLTGV2_TRACE")) {
+    rc = ensure(ctx, ctx->progress, 2 * sizeof(unsigned) * (size_t)ctx->L.wg_count);  // [how far | started when]
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->progress.p, 0, 2 * sizeof(unsigned) * (size_t)ctx->L.wg_count, ctx->stream));
+    want.progress = (unsigned*)ctx->progress.p;
+  }
+  constexpr size_t kTailStride = (sizeof(RunTail) + 255) / 256 * 256;
+  rc = ensure(ctx, ctx->run_tail, kTailStride * flame_nltgv2_ctx::kTailSlots);
+  if (rc) return rc;
+  int slot = -1;
+  for (int i = 0; i < flame_nltgv2_ctx::kTailSlots && slot < 0; ++i)
+    if (ctx->tail_valid[i] && std::memcmp(&want, &ctx->tail_sent[i], sizeof(RunTail)) == 0) slot = i;
+  if (slot < 0) {  // (ordered on the solver's stream behind every launch that still reads the slot)
+    slot = ctx->tail_next, ctx->tail_next = (ctx->tail_next + 1) % flame_nltgv2_ctx::kTailSlots;
+    // pageable source: the runtime stages it during the call, so `want` may go out of scope
+    HIPCHK(ctx, hipMemcpyAsync((char*)ctx->run_tail.p + kTailStride * (size_t)slot, &want, sizeof(RunTail), hipMemcpyHostToDevice, ctx->stream));
+    ctx->tail_sent[slot] = want;
+    ctx->tail_valid[slot] = true;
+  }
+  *tail_dev = (const RunTail*)((const char*)ctx->run_tail.p + kTailStride * (size_t)slot);
+  return 0;
+}
+
+// Step 5: what a group of the patch-per-wave form needs on the device before its launch -- its records' places, the probe buffer
+static int prepare_group(flame_nltgv2_ctx* ctx, const WaveGroup& gr, const GroupLaunch& g, int form, int n) {
+  if (form != 3) return 0;
+  int rc = 0;
+  ctx->f.wg_poll_gap = g.poll_gap;
+  ctx->f.rec_off = nullptr, ctx->f.place_pool = nullptr;
+  if (g.place) {
+    const int per_xcd = (gr.count + g.xcds - 1) / g.xcds;
+    if (ctx->place_state == 0) rc = place_calibrate(ctx);
+    if (!rc && ctx->place_state == 1 && (ctx->place_topo != ctx->topo || ctx->place_per_xcd != per_xcd)) rc = place_records(ctx, per_xcd);
+    if (rc) return rc;
+    if (ctx->place_state == 1) {
+      ctx->f.place_pool = ctx->place_base, ctx->f.rec_off = (const int32_t*)ctx->place_rec_off.p;
+      ctx->f.rec_off_stride = (int)records_capacity(ctx->L);
+      ctx->f.rot_word = (unsigned*)ctx->place_fill.p + 2 * kPlacePages;
+    }
+  }
+  ctx->f.probe = nullptr;
+  if (ctx->opt_probe) {  // [patch][step][8 words]
+    const size_t words = (size_t)ctx->L.wg_count * (size_t)n * 8;
+    rc = ensure(ctx, ctx->probe, words * sizeof(unsigned));
+    if (rc) return rc;
+    ctx->f.probe = (unsigned*)ctx->probe.p;
+    ctx->probe_words = words;
+    HIPCHK(ctx, hipMemsetAsync(ctx->probe.p, 0, words * sizeof(unsigned), ctx->stream));  // (idle instances write nothing)
+  }
+  return 0;
+}
+
+// Step 6: the launch of one group: the two-half-edges kernel, the lean patch kernel (the same launch as the general one's but for the
+// kernel: placement, XCDs and the cooperative first launch alike) or the general kernels.  Returns the runtime's error (0: launched).
+static int launch_group(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n, const RunPlan& pl, size_t gi, uint32_t tag0,
+                        const RunTail* tail, hipEvent_t stop_event) {
+  const WaveGroup& gr = pl.groups[gi];
+  const GroupLaunch& g = pl.launch[gi];
+  const bool coop = cooperative_allowed() && ctx->coop_checked_key != pl.coop_key;
+  ctx->f.stop_event = stop_event, ctx->f.open_run = pl.open ? 1 : 0;
+  int e;
+  if (pl.form == 4) e = launch_persistent_pv2(ctx->f, ctx->pv2_args, to_sp(p), gr.begin, gr.count, ctx->parity, tag0, n, g.spins_arg, g.poll_gap, g.dual, tail, coop, ctx->stream);
+  else if (pl.lean) e = launch_persistent_pv_lean(ctx->f, to_sp(p), gr.begin, gr.count, ctx->parity, tag0, n, g.spins_arg, g.xcds, tail, coop, ctx->stream);
+  else e = launch_persistent_run(ctx->f, to_sp(p), pl.form, gr.begin, gr.count, ctx->parity, tag0, n, g.pw, g.spins_arg, g.presleep, g.dual, g.xcds, tail, coop, ctx->stream);
+  ctx->f.stop_event = nullptr, ctx->f.open_run = 0;
+  return e;
+}
+
+// Step 7: every group is enqueued.  The kernels wrote (will write) hq / vstate / bar into the other copies: make those current.
+// finish() takes this back if the run reports a timeout.
+static void commit_persistent_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n, const RunPlan& pl, uint32_t tag0) {
+  if (!ctx->pending.active) {
+    ctx->pending.active = true, ctx->pending.snapshotted = false;
+    ctx->pending.ops.clear();
+    ctx->pending.parity_before = ctx->parity, ctx->pending.have_prev_before = ctx->have_prev;
+  }
+  push_pending_run(ctx, p, n, pl.open, tag0);
+  ctx->photo_fresh = photo_target(ctx).err != nullptr;  // (the epilogue of this run writes it)
+  ctx->open_inflight = pl.open, ctx->open_stop_sent = false;
+  if (!pl.open && ctx->replaying == 0) ctx->iters_total += n;  // (an open run: counted by finish(), which learns how far it went)
+  std::swap(ctx->hq, ctx->hq_alt);
+  std::swap(ctx->vstate, ctx->vstate_alt);
+  ctx->buf_gen ^= 1;
+  refresh_args(ctx);
+  ctx->coop_checked_key = pl.coop_key;
+  ctx->last_run_path = pl.form == 4 ? 7 : pl.form == 3 ? 6 : 5;
+  ctx->last_run_groups = (int)pl.groups.size();
+  const int cus = ctx->prop.multiProcessorCount;
+  ctx->last_run_waves_per_cu = 0;
+  for (const WaveGroup& gr : pl.groups) ctx->last_run_waves_per_cu = std::max(ctx->last_run_waves_per_cu, (gr.count + cus - 1) / cus);
+  ctx->parity ^= 1;
+  ctx->have_prev = true;
+  ctx->canon_valid = false;
+}
+
+// Step 8: the runtime refused a launch (e.g. a cooperative launch too large).  Groups already enqueued write into the other copies
+// only: the current state is intact.  Let those groups drain first and forget what they reported (their waits expire without the
+// missing groups): that is not a failure of a run.
+static int drain_refused(flame_nltgv2_ctx* ctx, const RunPlan& pl, int e) {
+  if (std::getenv("FLAME_NLTGV2_TRACE")) std::fprintf(stderr, "[flame_nltgv2] persistent launch refused: hip error %d (%s), form %d, pv_occ %d\n", e, hipGetErrorString((hipError_t)e), pl.form, ctx->pv_occ);
+  (void)hipGetLastError();
+  if (!pl.open) ctx->persist_refused_topo = ctx->topo;  // do not try again for this topology (the OPEN instance alone: the plain ones may still fit)
+  if (pl.groups.size() > 1 && !ctx->pending.active) {
+    HIPCHK(ctx, hipMemsetAsync(ctx->abort_flag.p, 0xff, sizeof(int), ctx->stream));  // tells them to leave at once
+    HIPCHK(ctx, wait_solver_stream(ctx));
+    HIPCHK(ctx, hipMemsetAsync(ctx->err.p, 0, kErrBytes, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->abort_flag.p, 0, sizeof(int), ctx->stream));
+  }
+  return 0;
+}
+
+// Step 9: one launch per step, as captured graphs of kGraphChunk steps where they pay
+static int run_per_step(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
+  if (ctx->pending.active) push_pending_run(ctx, p, n, false, 0);
   int unroll, wpb;
   pick_config(ctx, &unroll, &wpb);
-  std::vector<WaveGroup> groups;
-  const int form = plan_persistent(ctx, n, &groups, /*consume=*/true);
-  // an open run: the patch-per-wave form as ONE launch of its plain instance, the first run of a chain -- anything else is run as asked
-  // for (n iterations), the caller sees that from flame_nltgv2_run_open's `opened`
-  const bool open_run = ctx->want_open != 0 && open_run_applies(ctx, form, groups) && !ctx->pending.active && ctx->opt_probe == 0 &&
-                        ctx->opt_verify == 0 && ctx->replaying == 0 && (n & 1) == 0 && ctx->h_stop != nullptr && ctx->ctl_stream != nullptr;
-  if (ctx->want_open != 0 && !open_run) {  // flame_nltgv2_run_open on a graph / a configuration it does not apply to: nothing is run
-    ctx->want_open = 0;
-    return 0;
-  }
-  const bool lean = pv_lean_applies(ctx, form, groups, open_run);
-  if (ctx->opt_pv_lean == 2 && !lean) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (test option: the lean kernel or nothing)
-  if (form != 0) {
-    // tags must stay unique: clear the record buffers long before the 28-bit tag of the XCC table wraps -- and when the
-    // form changes (the forms lay the buffers out differently: one's XCC table is another's record area)
-    if ((uint64_t)ctx->tag_next + (uint64_t)n >= 0x07ff0000ull || (ctx->xbuf_form != 0 && ctx->xbuf_form != form)) {
-      const size_t bytes = kXbufBytesPerVertex * records_capacity(ctx->L);
-      HIPCHK(ctx, hipMemsetAsync(ctx->xbuf.p, 0, bytes, ctx->stream));
-      if (ctx->place_base) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->place_base, 0, (size_t)2 * kPlacePages * 4096, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync((int*)ctx->place_fill.p + 2 * kPlacePages, 0, 64, ctx->stream));
-      }
-      HIPCHK(ctx, hipMemsetAsync((int*)ctx->err.p + 12, 0, 2 * sizeof(int), ctx->stream));  // (an open run's words count from its tag0)
-      ctx->tag_next = 1;
-    }
-    ctx->xbuf_form = form;
-    // a fresh first tag per run: records left by earlier runs (whose state may since have been changed
-    // by per-step launches or host uploads) can never satisfy a wait of this one
-    const uint32_t tag0 = ctx->tag_next + 2;
-    // (topology, form, kernel instance): a new instance -- other registers, other LDS -- gets a cooperative first launch
-    const uint64_t key = ctx->topo * 1024 + (uint64_t)form * 64 + (ctx->opt_verify != 0 ? 16 : 0) + (ctx->opt_probe != 0 ? 8 : 0) +
-                         (ctx->opt_dual == 2 ? 4 : ctx->opt_dual == 1 ? 2 : 0) + (ctx->opt_xcds > 0 ? 1 : 0) + (lean ? 32 : 0);
-    const RunTail* tail_dev = nullptr;
-    {  // standing outputs: the small block the kernels read in their epilogue, (re)sent when no slot holds it
-      RunTail want;
-      std::memset(static_cast<void*>(&want), 0, sizeof want);
-      want.export_out = ctx->export_ptr, want.export_scale = ctx->export_scale;
-      if (open_run) {  // the request word: device memory; a request names the run it is for (its tag0), so the word is never cleared
-        const bool fresh = ctx->stop_dev.p == nullptr;
-        rc = ensure(ctx, ctx->stop_dev, 64);
-        if (rc) return rc;
-        if (fresh) HIPCHK(ctx, hipMemsetAsync(ctx->stop_dev.p, 0, 64, ctx->stream));
-        ctx->open_tag0 = tag0;
-      }
-      want.stop_req = open_run ? (const unsigned*)ctx->stop_dev.p : nullptr;
-      const PhotoFuse pf = photo_target(ctx);
-      std::memcpy(static_cast<void*>(&want.photo), &pf, sizeof pf);
-      if (form == 3 && std::getenv("FLAME_NLTGV2_TRACE")) {
-        rc = ensure(ctx, ctx->progress, 2 * sizeof(unsigned) * (size_t)ctx->L.wg_count);  // [how far | started when]
-        if (rc) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->progress.p, 0, 2 * sizeof(unsigned) * (size_t)ctx->L.wg_count, ctx->stream));
-        want.progress = (unsigned*)ctx->progress.p;
-      }
-      constexpr size_t kTailStride = (sizeof(RunTail) + 255) / 256 * 256;
-      rc = ensure(ctx, ctx->run_tail, kTailStride * flame_nltgv2_ctx::kTailSlots);
-      if (rc) return rc;
-      int slot = -1;
-      for (int i = 0; i < flame_nltgv2_ctx::kTailSlots && slot < 0; ++i)
-        if (ctx->tail_valid[i] && std::memcmp(&want, &ctx->tail_sent[i], sizeof(RunTail)) == 0) slot = i;
-      if (slot < 0) {  // (ordered on the solver's stream behind every launch that still reads the slot)
-        slot = ctx->tail_next, ctx->tail_next = (ctx->tail_next + 1) % flame_nltgv2_ctx::kTailSlots;
-        // pageable source: the runtime stages it during the call, so `want` may go out of scope
-        HIPCHK(ctx, hipMemcpyAsync((char*)ctx->run_tail.p + kTailStride * (size_t)slot, &want, sizeof(RunTail), hipMemcpyHostToDevice, ctx->stream));
-        ctx->tail_sent[slot] = want;
-        ctx->tail_valid[slot] = true;
-      }
-      tail_dev = (const RunTail*)((const char*)ctx->run_tail.p + kTailStride * (size_t)slot);
-    }
-    int e = 0;
-    for (const WaveGroup& gr : groups) {
-      // the run's last launch carries an event as its own completion signal (flame_nltgv2_stream_wait_run, _runs_in_flight); a cooperative launch
-      // (the first of a topology) cannot: the wait then records the event behind it
-      // (only a run enqueued by flame_nltgv2_run_async binds one: run_ev_pick < 0 for the blocking run(), finish()'s replays, the warm-up --
-      //  their launches must not re-arm an event that still stands for an earlier run in flight)
-      const bool carries = &gr == &groups.back() && ctx->coop_checked_key == key && ctx->run_ev_pick >= 0 && ctx->ev_run[ctx->run_ev_pick] != nullptr;
-      ctx->f.stop_event = carries ? ctx->ev_run[ctx->run_ev_pick] : nullptr;
-      const int pw = gr.count <= 4 * ctx->prop.multiProcessorCount ? 1 : 4;  // waves per workgroup
-      // same-XCD exchange through L2: with the waves laid out along the Morton curve it wins at every size
-      // (measured per step: 640x480 -16 %, 1280x720 -23 %, 1080p -18 %, 7-frame batch -20 %, 15 frames -19 %)
-      const int dual = (ctx->opt_dual == 2 || (ctx->opt_dual == 1 && gr.count > kDualMinWavesPerCu * ctx->prop.multiProcessorCount) ? 1 : 0) |
-                       (ctx->opt_verify == 2 ? 6 : ctx->opt_verify == 1 ? 2 : 0);  // bits 1, 2: record verification, its test hook
-      // A graph small enough runs on ONE XCD (32 CUs) entirely: every exchange stays in that XCD's L2 -- while its CUs get at
-      // most two patches each (measured: 48 patches 0.98 against 1.21 us per step on all eight, 208 patches 1.53 against 1.33)
-      const int cus_per_xcd = ctx->prop.multiProcessorCount / 8;
-      const bool one_xcd = form == 3 && gr.count <= 2 * cus_per_xcd;
-      const int xcds = ctx->opt_xcds > 0 ? ctx->opt_xcds : one_xcd ? 1 : 8;
-      const int presleep = ctx->opt_presleep > 0 ? ctx->opt_presleep - 1 : kPreSleepTv;  // (the patch form has its own, below)
-      // (test hook: a fault of 2^22 + n also hits the persistent replay of the chain, so that the per-step rung below it is exercised)
-      const unsigned spins_arg = (ctx->opt_fault > 0 && (ctx->replaying == 0 || ctx->opt_fault >= (1 << 22)))
-                                     ? (0x80000000u | (unsigned)(ctx->opt_fault & ((1 << 22) - 1))) : kMaxSpins;
-      if (form == 3) {
-        // pacing: none where a CU holds few patches (a poll costs nothing there and a pause only delays the hand-off); at
-        // high residency the polls of ~20 waves per CU saturate the L2s' request ports and the fabric and it is the hand-off
-        // itself that slows down (probe: 0.72 us at 4 patches per CU, 1.03 at 15; 26 per CU unpaced: 50 us per step) -- a
-        // pause before the first poll and between rounds then wins (tools/pv_big.py sweeps, profiles/r03_pv_dense.txt)
-        const bool dense = gr.count > kPvPaceAbovePerCu * ctx->prop.multiProcessorCount;
-        const bool denser = gr.count > kPvPaceMoreAbovePerCu * ctx->prop.multiProcessorCount;
-        const int dense_gap = denser ? kPvDenserGap : kPvDenseGap, dense_pre = denser ? kPvDenserPreSleep : kPvDensePreSleep;
-        const int gap = ctx->opt_poll_gap > 0 ? ctx->opt_poll_gap - 1 : dense ? (3 | ((dense_gap - 1) << 4)) : kPvPollGap;
-        ctx->f.wg_poll_gap = gap | ((ctx->opt_presleep > 0 ? ctx->opt_presleep - 1 : dense ? dense_pre : kPvPreSleep) << 8);
-        ctx->f.rec_off = nullptr, ctx->f.place_pool = nullptr;
-        if (ctx->opt_place && groups.size() == 1 && gr.begin == 0 && xcds == 8 && (dual & 1)) {
-          if (ctx->place_state == 0) {
-            rc = place_calibrate(ctx);
-            if (rc) return rc;
-          }
-          const int per_xcd = (gr.count + xcds - 1) / xcds;
-          if (ctx->place_state == 1 && (ctx->place_topo != ctx->topo || ctx->place_per_xcd != per_xcd)) {
-            rc = place_records(ctx, per_xcd);
-            if (rc) return rc;
-          }
-          if (ctx->place_state == 1) {
-            ctx->f.place_pool = ctx->place_base, ctx->f.rec_off = (const int32_t*)ctx->place_rec_off.p;
-            ctx->f.rec_off_stride = (int)records_capacity(ctx->L);
-            ctx->f.rot_word = (unsigned*)ctx->place_fill.p + 2 * kPlacePages;
-          }
-        }
-        ctx->f.probe = nullptr;
-        if (ctx->opt_probe) {  // [patch][step][8 words]
-          const size_t words = (size_t)ctx->L.wg_count * (size_t)n * 8;
-          rc = ensure(ctx, ctx->probe, words * sizeof(unsigned));
-          if (rc) return rc;
-          ctx->f.probe = (unsigned*)ctx->probe.p;
-          ctx->probe_words = words;
-          HIPCHK(ctx, hipMemsetAsync(ctx->probe.p, 0, words * sizeof(unsigned), ctx->stream));  // (idle instances write nothing)
-        }
-      }
-      if (form == 4) {  // two half-edges per lane: its own pacing (swept: profiles/r03_pv2.txt)
-        const bool dense = gr.count > kPv2PaceAbovePerCu * ctx->prop.multiProcessorCount;
-        const int gap = ctx->opt_poll_gap > 0 ? ctx->opt_poll_gap - 1 : dense ? (3 | ((kPv2DenseGap - 1) << 4)) : kPvPollGap;
-        const int poll_gap = gap | ((ctx->opt_presleep > 0 ? ctx->opt_presleep - 1 : dense ? kPv2DensePreSleep : kPvPreSleep) << 8);
-        ctx->f.open_run = open_run ? 1 : 0;
-        e = launch_persistent_pv2(ctx->f, ctx->pv2_args, to_sp(p), gr.begin, gr.count, ctx->parity, tag0, n, spins_arg, poll_gap, dual,
-                                  tail_dev, cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
-        ctx->f.open_run = 0;
-        if (e != 0) break;
-        continue;
-      }
-      if (lean) {  // (the same launch but for the kernel: placement, XCDs and the cooperative first launch as for the general one)
-        e = launch_persistent_pv_lean(ctx->f, to_sp(p), gr.begin, gr.count, ctx->parity, tag0, n, spins_arg, xcds, tail_dev,
-                                      cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
-        if (e != 0) break;
-        continue;
-      }
-      ctx->f.open_run = open_run ? 1 : 0;
-      e = launch_persistent_run(ctx->f, to_sp(p), form, gr.begin, gr.count, ctx->parity, tag0, n, pw, spins_arg, presleep, dual,
-                                xcds, tail_dev, cooperative_allowed() && ctx->coop_checked_key != key, ctx->stream);
-      ctx->f.open_run = 0;
-      if (e != 0) break;
-    }
-    ctx->run_event_bound = e == 0 && ctx->f.stop_event != nullptr;
-    ctx->f.stop_event = nullptr;
-    ctx->tag_next = tag0 + (uint32_t)n;
-    if (e == 0) {
-      // The kernels wrote (will write) hq / vstate / bar into the other copies: make those current.  finish() takes
-      // this back if the run reports a timeout.
-      if (!ctx->pending.active) {
-        ctx->pending.active = true, ctx->pending.snapshotted = false;
-        ctx->pending.ops.clear();
-        ctx->pending.parity_before = ctx->parity, ctx->pending.have_prev_before = ctx->have_prev;
-      }
-      {
-        flame_nltgv2_ctx::PendingOp op;
-        op.kind = 0, op.params = *p, op.n = n;
-        op.open = open_run, op.tag0 = tag0;
-        op.dst = ctx->export_ptr, op.scale = ctx->export_scale;  // the standing export target THIS run was enqueued with
-        ctx->pending.ops.push_back(op);
-      }
-      ctx->photo_fresh = photo_target(ctx).err != nullptr;  // (the epilogue of this run writes it)
-      ctx->open_inflight = open_run, ctx->open_stop_sent = false;
-      if (open_run) ctx->want_open = 2;
-      if (!open_run && ctx->replaying == 0) ctx->iters_total += n;  // (an open run: counted by finish(), which learns how far it went)
-      std::swap(ctx->hq, ctx->hq_alt);
-      std::swap(ctx->vstate, ctx->vstate_alt);
-      ctx->buf_gen ^= 1;
-      refresh_args(ctx);
-      ctx->coop_checked_key = key;
-      ctx->last_run_path = form == 4 ? 7 : form == 3 ? 6 : 5;
-      ctx->last_run_groups = (int)groups.size();
-      ctx->last_run_waves_per_cu = 0;
-      for (const WaveGroup& gr : groups) ctx->last_run_waves_per_cu = std::max(ctx->last_run_waves_per_cu, (gr.count + ctx->prop.multiProcessorCount - 1) / ctx->prop.multiProcessorCount);
-      ctx->parity ^= 1;
-      ctx->have_prev = true;
-      ctx->canon_valid = false;
-      return 0;
-    }
-    if (std::getenv("FLAME_NLTGV2_TRACE")) std::fprintf(stderr, "[flame_nltgv2] persistent launch refused: hip error %d (%s), form %d, pv_occ %d\n", e, hipGetErrorString((hipError_t)e), form, ctx->pv_occ);
-    // e.g. cooperative launch too large.  Groups already enqueued write into the other copies only: the current
-    // state is intact, the steps are done on the one-launch-per-step path below.  Let those groups drain first and
-    // forget what they reported (their waits expire without the missing groups): that is not a failure of a run.
-    (void)hipGetLastError();
-    ctx->persist_refused_topo = ctx->topo;  // do not try again for this topology
-    if (groups.size() > 1 && !ctx->pending.active) {
-      HIPCHK(ctx, hipMemsetAsync(ctx->abort_flag.p, 0xff, sizeof(int), ctx->stream));  // tells them to leave at once
-      HIPCHK(ctx, wait_solver_stream(ctx));
-      HIPCHK(ctx, hipMemsetAsync(ctx->err.p, 0, kErrBytes, ctx->stream));
-      HIPCHK(ctx, hipMemsetAsync(ctx->abort_flag.p, 0, sizeof(int), ctx->stream));
-    }
-  }
-  if (ctx->pending.active) {
-    flame_nltgv2_ctx::PendingOp op;
-    op.kind = 0, op.params = *p, op.n = n;
-    op.dst = ctx->export_ptr, op.scale = ctx->export_scale;
-    ctx->pending.ops.push_back(op);
-  }
   int left = n;
   while (left > 0) {
     const int chunk = left >= kGraphChunk ? kGraphChunk : left;
     if (ctx->opt_use_graph && chunk >= 4) {
       hipGraphExec_t exec = nullptr;
-      rc = get_graph(ctx, p, chunk, ctx->parity, unroll, wpb, &exec);
+      const int rc = get_graph(ctx, p, chunk, ctx->parity, unroll, wpb, &exec);
       if (rc) return rc;
       HIPCHK(ctx, hipGraphLaunch(exec, ctx->stream));
       ctx->last_run_path = 2;
     } else {
-      rc = enqueue_fused_eager(ctx, p, chunk, ctx->parity, unroll, wpb, true);
+      const int rc = enqueue_fused_eager(ctx, p, chunk, ctx->parity, unroll, wpb, true);
       if (rc) return rc;
       ctx->last_run_path = 3;
     }
@@ -752,6 +661,51 @@ int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n) {
   if (ctx->replaying == 0) ctx->iters_total += n;
   if (ctx->export_ptr) LAUNCHCHK(ctx, launch_export(ctx->c, ctx->f, true, ctx->export_scale, ctx->export_ptr, ctx->stream));
   return enqueue_photo_sweep(ctx, true);
+}
+
+int enqueue_run(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n, bool ask_open, int bind_event, bool* opened, bool* event_bound) {
+  if (opened) *opened = false;
+  if (event_bound) *event_bound = false;
+  if (n <= 0) return 0;
+  // nothing is chained behind an open run (it would wait for the run's upper bound), and an open run is the first of its chain
+  if (ctx->open_inflight || (ask_open && ctx->pending.active)) {
+    const int rc0 = finish(ctx);
+    if (rc0) return rc0;
+  }
+  if (ctx->opt_solver == 1) return ask_open ? 0 : run_canonical(ctx, p, n);
+  int rc = chain_onto_pending(ctx);
+  if (rc) return rc;
+  const RunPlan pl = plan_run(ctx, n, ask_open, /*consume=*/true);
+  if (ask_open && !pl.open) return 0;  // flame_nltgv2_run_open on a graph / a configuration it does not apply to: nothing is run
+  if (ctx->opt_pv_lean == 2 && !pl.lean) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (test option: the lean kernel or nothing)
+  if (pl.form != 0) {
+    uint32_t tag0 = 0;
+    const RunTail* tail = nullptr;
+    rc = next_run_tags(ctx, pl.form, n, &tag0);
+    if (!rc) rc = run_tail_slot(ctx, pl, tag0, &tail);
+    if (rc) return rc;
+    int e = 0;
+    bool carries = false;
+    for (size_t gi = 0; gi < pl.groups.size() && e == 0; ++gi) {
+      rc = prepare_group(ctx, pl.groups[gi], pl.launch[gi], pl.form, n);
+      if (rc) return rc;
+      // the run's last launch carries an event as its own completion signal (flame_nltgv2_stream_wait_run, _runs_in_flight); a cooperative
+      // launch (the first of a topology) cannot: the wait then records the event behind it.  Only a run enqueued by flame_nltgv2_run_async /
+      // _run_open binds one: the launches of finish()'s replays must not re-arm an event that still stands for an earlier run in flight.
+      carries = gi + 1 == pl.groups.size() && ctx->coop_checked_key == pl.coop_key && bind_event >= 0 && ctx->ev_run[bind_event] != nullptr;
+      e = launch_group(ctx, p, n, pl, gi, tag0, tail, carries ? ctx->ev_run[bind_event] : nullptr);
+    }
+    ctx->tag_next = tag0 + (uint32_t)n;
+    if (e == 0) {
+      commit_persistent_run(ctx, p, n, pl, tag0);
+      if (opened) *opened = pl.open;
+      if (event_bound) *event_bound = carries;
+      return 0;
+    }
+    rc = drain_refused(ctx, pl, e);
+    if (rc || pl.open) return rc;  // an open run that cannot be launched runs nothing; anything else goes step by step
+  }
+  return run_per_step(ctx, p, n);
 }
 
 // FLAME_NLTGV2_TRACE: which wait of the persistent run expired first, and how far every patch had got
@@ -890,7 +844,7 @@ int finish(flame_nltgv2_ctx* ctx, bool unpack_behind, bool* unpacked, const std:
     for (const flame_nltgv2_ctx::PendingOp& op : run.ops) {
       if (op.kind == 0) {
         ctx->export_ptr = op.dst, ctx->export_scale = op.scale;
-        replay_rc = enqueue_run(ctx, &op.params, op.n);
+        replay_rc = enqueue_run(ctx, &op.params, op.n, /*ask_open=*/false, /*bind_event=*/-1, nullptr, nullptr);
         ctx->export_ptr = export_now, ctx->export_scale = export_scale_now;
       } else {
         const int e = launch_export(ctx->c, ctx->f, true, op.scale, op.dst, ctx->stream);
@@ -945,6 +899,19 @@ int snapshot_chain_start(flame_nltgv2_ctx* ctx) {
 
 extern "C" {
 
+// flame_nltgv2_run_async / _run_open have enqueued a run: ev_run[idx] stands for it -- carried by its last launch (`bound`), or recorded
+// behind it where that launch could not (a cooperative first launch, the per-step path) and somebody asks runs_in_flight
+static int run_event_stands(flame_nltgv2_ctx* ctx, int idx, bool bound) {
+  if (!bound && ctx->track_runs) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_run[idx], ctx->stream));
+    bound = true;
+  }
+  ctx->run_ev_valid[idx] = bound;
+  ctx->run_ev_last = idx;
+  ctx->run_event_seq = ctx->call_seq;
+  return 0;
+}
+
 int flame_nltgv2_run_async(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int n_iters) {
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_run_async");
   int rc = enter(ctx);
@@ -953,20 +920,10 @@ int flame_nltgv2_run_async(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, 
   if (!params_ok(p) || n_iters < 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (n_iters == 0) return 0;  // nothing is enqueued: the two events keep standing for the runs they stand for
   const int idx = ctx->run_ev_last ^ 1;  // the two events take turns: the last two runs can be told apart
-  ctx->run_ev_pick = idx;
-  ctx->run_event_bound = false;
-  rc = enqueue_run(ctx, p, n_iters);
-  ctx->run_ev_pick = -1;
+  bool bound = false;
+  rc = enqueue_run(ctx, p, n_iters, /*ask_open=*/false, idx, nullptr, &bound);
   if (rc) return rc;
-  bool stands = ctx->run_event_bound;
-  if (!stands && ctx->track_runs) {  // (a cooperative first launch, the per-step path: recorded behind it)
-    HIPCHK(ctx, hipEventRecord(ctx->ev_run[idx], ctx->stream));
-    stands = true;
-  }
-  ctx->run_ev_valid[idx] = stands;
-  ctx->run_ev_last = idx;
-  ctx->run_event_seq = ctx->call_seq;
-  return 0;
+  return run_event_stands(ctx, idx, bound);
 }
 
 int flame_nltgv2_run_open(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, int max_iters, int32_t* opened) {
@@ -977,34 +934,14 @@ int flame_nltgv2_run_open(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, i
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (!params_ok(p) || max_iters < 0 || (max_iters & 1)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (max_iters == 0) return 0;
-  if (ctx->pending.active) {  // applicable at all?  Asked BEFORE anything is settled: a loop that falls back to rounds must not have them waited for here
-    std::vector<WaveGroup> groups;
-    const int form = plan_persistent(ctx, max_iters, &groups, /*consume=*/false);
-    if (!open_run_applies(ctx, form, groups) || ctx->opt_probe != 0 || ctx->opt_verify != 0 || !ctx->h_stop || !ctx->ctl_stream) return 0;
-  }
-  if (ctx->pending.active) {  // an open run is the first of its chain
-    rc = finish(ctx);
-    if (rc) return rc;
-  }
+  // applicable at all?  Asked BEFORE anything is touched or settled: a loop that falls back to rounds must not have them waited for here
+  if (!plan_run(ctx, max_iters, /*ask_open=*/true, /*consume=*/false).open) return 0;
   const int idx = ctx->run_ev_last ^ 1;
-  ctx->run_ev_pick = idx;
-  ctx->run_event_bound = false;
-  ctx->want_open = 1;
-  rc = enqueue_run(ctx, p, max_iters);
-  const bool was_open = ctx->want_open == 2;
-  ctx->want_open = 0;
-  ctx->run_ev_pick = -1;
-  if (rc) return rc;
-  bool stands = ctx->run_event_bound;
-  if (!stands && ctx->track_runs) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_run[idx], ctx->stream));
-    stands = true;
-  }
-  ctx->run_ev_valid[idx] = stands;
-  ctx->run_ev_last = idx;
-  ctx->run_event_seq = ctx->call_seq;
-  if (opened) *opened = was_open ? 1 : 0;
-  return 0;
+  bool was_open = false, bound = false;
+  rc = enqueue_run(ctx, p, max_iters, /*ask_open=*/true, idx, &was_open, &bound);  // (settles what is pending: an open run is the first of its chain)
+  if (rc || !was_open) return rc;
+  if (opened) *opened = 1;
+  return run_event_stands(ctx, idx, bound);
 }
 
 int flame_nltgv2_iterations(flame_nltgv2_ctx* ctx, int64_t* total, int32_t* open_in_flight) {
@@ -1082,7 +1019,7 @@ int flame_nltgv2_run_timed(flame_nltgv2_ctx* ctx, const flame_nltgv2_params* p, 
   rc = prepare_run(ctx, p, n_iters);
   if (rc) return rc;
   HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  rc = enqueue_run(ctx, p, n_iters);
+  rc = enqueue_run(ctx, p, n_iters, /*ask_open=*/false, /*bind_event=*/-1, nullptr, nullptr);
   if (rc) return rc;
   HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   rc = finish(ctx);
@@ -1123,6 +1060,5 @@ int flame_nltgv2_save_prev(flame_nltgv2_ctx* ctx) {
   ctx->fused_valid = false;
   return finish(ctx);
 }
-
 
 }  // extern "C"

@@ -1151,3 +1151,60 @@ def test_open_run_stops_when_asked_and_says_how_far_it_went(built, size, path):
         reg.set_option(OPT_FAULT_INJECT, 0)
         assert reg.info()["timeouts_recovered"] == rec + 1
         print(f"open runs: {n} iterations in ~4 ms, {n0} when stopped at once")
+
+
+def test_a_refused_open_run_on_the_four_kernel_path_runs_nothing(built):
+    """flame_nltgv2_run_open with FLAME_NLTGV2_OPT_SOLVER = 1 (the canonical sweeps: no persistent form, so no open run): *opened = 0, and as
+    the header promises for it NOTHING was enqueued -- no iteration counted, no run in flight, the state still the oracle's after the 10
+    iterations run before."""
+    import torch  # noqa: F401
+
+    import flame_amd
+    from flame_amd.regularizer import OPT_SOLVER
+    from oracle import capi as oracle
+
+    g = synth.make_graph("320x240", seed=3)
+    ref = synth.copy_graph(g)
+    p = flame_amd.Params()
+    with flame_amd.Regularizer(0) as reg:
+        reg.set_option(OPT_SOLVER, 1)
+        reg.upload_graph(g)
+        reg.run(p, 10)
+        oracle.run(ref, 10)
+        assert reg.info()["last_run_path"] == 4
+        before, in_flight = reg.iterations(), reg.runs_in_flight()
+        assert before == (10, False)
+        assert not reg.run_open(p, 8)
+        assert reg.iterations() == before and reg.runs_in_flight() == in_flight
+        assert_state_equal(reg.download_state(), ref, keys=OUT_KEYS + ("x_prev", "w1_prev", "w2_prev"), what="after the refused open run")
+
+
+def test_a_refused_open_run_leaves_the_run_in_flight_alone(built):
+    """flame_nltgv2_run_open where it does not apply (record verification on) while a run is in flight: *opened = 0, the run is neither
+    waited for nor forgotten (runs_in_flight still counts it), nothing is counted, and once settled the state is the oracle's after the
+    iterations that WERE asked for."""
+    import torch  # noqa: F401
+
+    import flame_amd
+    from flame_amd.regularizer import OPT_SOLVER, OPT_VERIFY_RECORDS
+    from oracle import capi as oracle
+
+    g = synth.make_graph("320x240", seed=3)
+    ref = synth.copy_graph(g)
+    p = flame_amd.Params()
+    with flame_amd.Regularizer(0) as reg:
+        reg.set_option(OPT_SOLVER, 0)
+        reg.set_option(OPT_VERIFY_RECORDS, 1)
+        reg.upload_graph(g)
+        reg.run(p, 10)
+        assert reg.info()["last_run_path"] == 6  # (the patch-per-wave form)
+        assert reg.runs_in_flight() == 0
+        reg.run_async(p, 3000)
+        assert reg.runs_in_flight() == 1
+        before = reg.iterations()
+        assert not reg.run_open(p, 1000)
+        assert reg.runs_in_flight() == 1 and reg.iterations() == before
+        reg.sync()
+        assert reg.iterations() == (3010, False)
+        oracle.run(ref, 3010)
+        assert_state_equal(reg.download_state(), ref, keys=OUT_KEYS + ("x_prev", "w1_prev", "w2_prev"), what="after the run in flight")
