@@ -46,6 +46,22 @@ int ensure(flame_nltgv2_ctx* ctx, DevBuf& b, size_t bytes) {
   return 0;
 }
 
+int grow_pinned(flame_nltgv2_ctx* ctx, PinnedBuf& b, size_t bytes, bool* replaced) {
+  if (replaced) *replaced = false;
+  if (b.cap >= bytes) return 0;
+  request_open_stop(ctx);  // (the pinned allocator waits for the device)
+  const size_t want = bytes + bytes / 2;
+  void* h = nullptr;
+  if (hipHostMalloc(&h, want, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
+  }
+  if (b.p) (void)hipHostFree(b.p);
+  b.p = (char*)h, b.cap = want;
+  if (replaced) *replaced = true;
+  return 0;
+}
+
 void drop_graphs(flame_nltgv2_ctx* ctx) {
   for (auto& g : ctx->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -519,9 +535,8 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   ok = ok && hipEventCreateWithFlags(&ctx->ev_snap, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_raster_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_topo_ready, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreate(&ctx->ev_mesh0) == hipSuccess && hipEventCreate(&ctx->ev_mesh1) == hipSuccess;
-  ok = ok && hipEventCreate(&ctx->ev_dbg0) == hipSuccess && hipEventCreate(&ctx->ev_dbg1) == hipSuccess;
-  ok = ok && hipEventCreate(&ctx->ev_wire0) == hipSuccess && hipEventCreate(&ctx->ev_wire1) == hipSuccess;
+  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire})
+    ok = ok && hipEventCreate(&st->ev0) == hipSuccess && hipEventCreate(&st->ev1) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_expanded, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[0], hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[1], hipEventDisableTiming) == hipSuccess;
@@ -592,7 +607,7 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
     if (b->p) (void)hipFree(b->p);
   if (ctx->h_err) (void)hipHostFree(ctx->h_err);
   if (ctx->h_cost) (void)hipHostFree(ctx->h_cost);
-  if (ctx->h_keep) (void)hipHostFree(ctx->h_keep);
+  if (ctx->h_keep.p) (void)hipHostFree(ctx->h_keep.p);
   if (ctx->h_stop) (void)hipHostFree(ctx->h_stop);
   if (ctx->ctl_stream) (void)hipStreamSynchronize(ctx->ctl_stream), (void)hipStreamDestroy(ctx->ctl_stream);
   for (auto& st : ctx->stage)
@@ -606,16 +621,12 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
   if (ctx->ev_raster_done) (void)hipEventDestroy(ctx->ev_raster_done);
   for (hipEvent_t e : ctx->ev_run)
     if (e) (void)hipEventDestroy(e);
-  if (ctx->h_img) (void)hipHostFree(ctx->h_img);
-  if (ctx->h_mesh) (void)hipHostFree(ctx->h_mesh);
-  if (ctx->ev_mesh0) (void)hipEventDestroy(ctx->ev_mesh0);
-  if (ctx->ev_mesh1) (void)hipEventDestroy(ctx->ev_mesh1);
-  if (ctx->h_dbg) (void)hipHostFree(ctx->h_dbg);
-  if (ctx->ev_dbg0) (void)hipEventDestroy(ctx->ev_dbg0);
-  if (ctx->ev_dbg1) (void)hipEventDestroy(ctx->ev_dbg1);
-  if (ctx->h_wire) (void)hipHostFree(ctx->h_wire);
-  if (ctx->ev_wire0) (void)hipEventDestroy(ctx->ev_wire0);
-  if (ctx->ev_wire1) (void)hipEventDestroy(ctx->ev_wire1);
+  if (ctx->h_img.p) (void)hipHostFree(ctx->h_img.p);
+  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire}) {
+    if (st->h.p) (void)hipHostFree(st->h.p);
+    if (st->ev0) (void)hipEventDestroy(st->ev0);
+    if (st->ev1) (void)hipEventDestroy(st->ev1);
+  }
   if (ctx->h_dims) (void)hipHostFree(ctx->h_dims);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -9,7 +9,8 @@
 //   nltgv2_context.hip     buffers, uploads of a topology, context life cycle, options, info, self-tests
 //   nltgv2_run.hip         which kernels run n steps (planner), enqueue / settle / roll back, the run entry points
 //   nltgv2_graph_capi.hip  graph in / out: upload, per-frame sync, projection, rescale, state download, costs, export
-//   nltgv2_frame_capi.hip  the rows around the solver that work on its device state: mesh rasteriser, photometric residual
+//   nltgv2_frame_capi.hip  the rows around the solver that work on its device state: the dense map, the mesh outputs, the debug images and
+//                          the wireframe (begin / end stages on the side stream; their pure part: side_stage.hpp), photometric residual
 #ifndef FLAME_AMD_NLTGV2_CONTEXT_HPP_
 #define FLAME_AMD_NLTGV2_CONTEXT_HPP_
 
@@ -33,6 +34,7 @@
 #include "nltgv2_pack.hpp"
 #include "nltgv2_plan.hpp"
 #include "roctx_ranges.hpp"
+#include "side_stage.hpp"
 
 namespace flame_hip {
 namespace host {
@@ -53,6 +55,20 @@ constexpr size_t kErrBytes = 16 * sizeof(int);  // the flag word + what the firs
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+};
+
+// Pinned host memory that only grows (grow_pinned).
+struct PinnedBuf {
+  char* p = nullptr;
+  size_t cap = 0;
+};
+
+// A begin / end stage on the side stream: its pinned outputs, the timing events around its device work, and whether a begin has left
+// outputs there that an _end may hand out.
+struct SideStage {
+  PinnedBuf h;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool active = false;
 };
 
 struct CachedGraph {
@@ -293,59 +309,44 @@ struct flame_nltgv2_ctx {
   hipStream_t raster_stream = nullptr;  // the side stream of interpolate_mesh_begin / _end
   hipEvent_t ev_canon = nullptr, ev_raster_done = nullptr;
   bool raster_inflight = false;       // the side stream still reads the canonical pos / x: the next unpack waits for ev_raster_done
-  float* h_img = nullptr;             // pinned: the map of the last interpolate_mesh_begin (+ the coverage count behind it)
-  size_t h_img_cap = 0;
+  PinnedBuf h_img;                    // the map of the last interpolate_mesh_begin (+ the coverage count behind it)
   int map_rows = 0, map_cols = 0;     // the dense map resident in r_img (0: none)
   int img_pending_rows = 0, img_pending_cols = 0;  // the map an interpolate_mesh_begin left in h_img for its _end (0: none pending)
-  // flame_nltgv2_mesh_outputs_begin / _end (mesh_kernels.hip): the triangles interpolate_mesh[_begin] left in r_tris (-1: none, or
-  // they index other arrays than the graph's) and the topology their indices were checked against; scratch, outputs and the
-  // filtered map with buffers of their own (r_img / h_img stay the unfiltered map's)
-  int32_t tris_T = -1;
-  uint64_t tris_topo = ~0ull;
+  // The triangles interpolate_mesh[_begin] or mesh_outputs_begin left in r_tris, and what r_keys (the key image of the resident map)
+  // and m_tvalid (the filters' validity, debug_wireframe_begin's validity == 2) say about them: side_stage.hpp
+  ResidentTris tris;
+  // flame_nltgv2_mesh_outputs_begin / _end (mesh_kernels.hip): scratch, outputs and the filtered map with buffers of their own (r_img /
+  // h_img stay the unfiltered map's).  Pinned: normals, vtx_idepth, {n_valid, coverage}, filtered map, tri_valid (mesh_layout)
   DevBuf m_P, m_idepth, m_normals, m_tvalid, m_nvalid, m_tnormal, m_offset, m_cursor, m_incident, m_keys, m_img, m_cov;
-  char* h_mesh = nullptr;             // pinned: normals, vtx_idepth, {n_valid, coverage}, filtered map, tri_valid
-  size_t h_mesh_cap = 0;
+  SideStage mesh;
   struct MeshPending {
-    bool active = false;
     int32_t V = 0, T = 0;
     int rows = 0, cols = 0;           // of the filtered map (0: not asked for)
-    size_t off_idepth = 0, off_counts = 0, off_map = 0, off_valid = 0;  // byte offsets in h_mesh (normals at 0)
+    MeshLayout at{};
   } mesh_pending;
-  hipEvent_t ev_mesh0 = nullptr, ev_mesh1 = nullptr;  // timing events around the stage on the side stream
-  // flame_nltgv2_debug_images_begin / _end (debug_kernels.hip): r_keys is the key image of the resident map; it names the winning
-  // triangles of an all-valid rasterisation of r_tris exactly when keys_gen == tris_gen (tris_gen counts the uploads into r_tris,
-  // keys_gen is the count the last rasterisation of the graph's map saw, 0 where it had a validity mask or was another image's).
-  // Buffers, pinned outputs and timing events of its own: the resident map, h_img, h_mesh and r_keys are only read.
-  uint64_t tris_gen = 0, keys_gen = 0;
+  // flame_nltgv2_debug_images_begin / _end (debug_kernels.hip): buffers, pinned outputs and timing events of its own: the resident map,
+  // h_img, the mesh stage's outputs and r_keys are only read.  Pinned: idepth image | normals image | w1 map | w2 map | staging of a
+  // host grey image (debug_layout)
   DevBuf d_gray, d_idimg, d_nimg, d_w1map, d_w2map, d_keys, d_cov;
-  char* h_dbg = nullptr;              // pinned: idepth image | normals image | w1 map | w2 map | staging of a host grey image
-  size_t h_dbg_cap = 0;
+  SideStage dbg;
   struct DebugPending {
-    bool active = false;
     int rows = 0, cols = 0;
     bool want_idepth = false, want_normals = false;
-    size_t off_nimg = 0, off_w1 = 0, off_w2 = 0, off_gray = 0;  // byte offsets in h_dbg (idepth image at 0)
+    DebugLayout at{};
   } debug_pending;
-  hipEvent_t ev_dbg0 = nullptr, ev_dbg1 = nullptr;
   // flame_nltgv2_debug_wireframe_begin / _end (wireframe_kernels.hip): buffers, pinned outputs, pending record and timing events of
-  // its own.  tvalid_*: for which upload into r_tris (tris_gen), how many triangles and which topology the last mesh_outputs_begin
-  // wrote m_tvalid (validity == 2).  w_cap: entries w_entries holds; w_last_total: the entries of the last finished call.
-  bool tvalid_have = false;
-  uint64_t tvalid_gen = 0, tvalid_topo = 0;
-  int32_t tvalid_T = -1;
+  // its own.  w_cap: entries w_entries holds; w_last_total: the entries of the last finished call.  Pinned: the picture | the
+  // counters | staging of a host grey image (wire_layout)
   DevBuf w_draws, w_cnt, w_off, w_fill, w_entries, w_counts, w_img, w_gray, w_tvalid;
   size_t w_cap = 0, w_last_total = 0;
-  char* h_wire = nullptr;             // pinned: the picture | the counters | staging of a host grey image
-  size_t h_wire_cap = 0;
+  SideStage wire;
   struct WirePending {
-    bool active = false;
     int rows = 0, cols = 0, flip = 0, gray_step = 0;
     int32_t T = 0;
     float scene_color_scale = 1.0f;
     const uint8_t* gray = nullptr;    // device memory: what fill + fold read if _end has to repeat them
-    size_t off_counts = 0, off_gray = 0;  // byte offsets in h_wire (the picture at 0)
+    WireLayout at{};
   } wire_pending;
-  hipEvent_t ev_wire0 = nullptr, ev_wire1 = nullptr;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {
@@ -394,7 +395,7 @@ struct flame_nltgv2_ctx {
   int* h_err = nullptr;    // pinned, kErrBytes
   int last_expired[16] = {0};  // what the most recent expired wait reported (report_expired)
   float* h_cost = nullptr; // pinned
-  uint8_t* h_keep = nullptr;  // pinned: project_graph's keep mask, written by its kernel
+  PinnedBuf h_keep;        // project_graph's keep mask, written by its kernel
   unsigned* h_stop = nullptr; // pinned: the open run's tag0, which request_open_stop copies into stop_dev when the host wants the state
   DevBuf stop_dev;            // the word an open run's deciding patch looks at (device memory: a word in host memory cost that patch -- and with it
                               // the whole lock-step network -- a PCIe round trip per two steps: 1.38 against 0.95 us per iteration)
@@ -405,7 +406,6 @@ struct flame_nltgv2_ctx {
   int last_open_iters = 0;    // how far the last open run went
   int64_t iters_total = 0;    // iterations applied to the state by every run since create (open runs: counted when they are settled)
   DevBuf pos_undo;            // project_graph: the positions as they stood (when layout_pos already holds older ones), to take a projection back
-  size_t h_keep_cap = 0;
   std::vector<CachedGraph> graphs;
   size_t device_bytes = 0;
 };
@@ -436,6 +436,9 @@ namespace host {
 // ---- nltgv2_context.hip ------------------------------------------------------------------------------------------------
 int fail(flame_nltgv2_ctx* ctx, int status);
 int ensure(flame_nltgv2_ctx* ctx, DevBuf& b, size_t bytes);   // grows a device buffer geometrically, reused across frames
+// At least `bytes` of pinned memory in b, with half as much again when it has to grow.  Stops an open run first (the pinned allocator
+// waits for the device).  Out of memory: the old buffer and what it holds stay.  *replaced: b is a new buffer, the old contents are gone.
+int grow_pinned(flame_nltgv2_ctx* ctx, PinnedBuf& b, size_t bytes, bool* replaced = nullptr);
 void drop_graphs(flame_nltgv2_ctx* ctx);
 SolverParams to_sp(const flame_nltgv2_params* p);
 int enter(flame_nltgv2_ctx* ctx);

@@ -1,5 +1,14 @@
-// nltgv2_frame_capi.hip -- the rows around the solver that work on its device state: mesh -> dense inverse-depth map, photometric
-// residual (see nltgv2_context.hpp).
+// nltgv2_frame_capi.hip -- the rows around the solver that work on its device state (see nltgv2_context.hpp):
+//   the mesh rasteriser       interpolate_mesh, interpolate_mesh_arrays on the solver's stream; interpolate_mesh_begin / _end beside it
+//   the mesh outputs          mesh_outputs_begin / _end: triangle filters, vertex normals and idepths, the filtered map
+//   the debug images          debug_images_begin / _end: idepth colours, normals, the w1 / w2 maps
+//   the wireframe             debug_wireframe_begin / _end
+//   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
+// The four begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
+// they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
+// the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
+// record of the resident triangles) is in side_stage.hpp.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,15 +33,71 @@ static int mesh_state_on(flame_nltgv2_ctx* ctx, hipStream_t rs) {
   return FLAME_NLTGV2_OK;
 }
 
+// A begin without its end may still be writing the pinned outputs and the device buffers that are about to be reused: the side stream
+// is waited for, then the pinned buffer holds `bytes` (grow_pinned; *replaced: what a pending _end would have returned is gone).
+static int open_stage(flame_nltgv2_ctx* ctx, PinnedBuf& h, size_t bytes, bool* replaced) {
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  return grow_pinned(ctx, h, bytes, replaced);
+}
+static int open_stage(flame_nltgv2_ctx* ctx, SideStage& st, size_t bytes) {
+  bool replaced = false;
+  const int rc = open_stage(ctx, st.h, bytes, &replaced);
+  if (replaced) st.active = false;
+  return rc;
+}
+
+// The side stream's kernels enqueued so far are the last readers of the canonical arrays (and the writers of the stage's device
+// outputs): whoever rewrites those waits for THEM, not for the outputs' way to the host (the map: 0.05 ms at 640x480, 0.3 ms at
+// 1920x1080 -- time a commit would stand still for).
+static int side_kernels_read_last(flame_nltgv2_ctx* ctx) {
+  HIPCHK(ctx, hipEventRecord(ctx->ev_raster_done, ctx->raster_stream));
+  ctx->raster_inflight = true;
+  return FLAME_NLTGV2_OK;
+}
+
+// Everything of the stage is enqueued: its _end may hand the pinned outputs out.
+static int close_stage(flame_nltgv2_ctx* ctx, SideStage& st) {
+  HIPCHK(ctx, hipEventRecord(st.ev1, ctx->raster_stream));
+  st.active = true;
+  return FLAME_NLTGV2_OK;
+}
+
+// Device time between the stage's two events, which must have completed; 0 where the runtime cannot tell.
+static float stage_ms(const SideStage& st) {
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, st.ev0, st.ev1) != hipSuccess) (void)hipGetLastError(), ms = 0.0f;
+  return ms;
+}
+
+// The grey image a stage draws over.  A host image goes through pinned memory (`staging`, rows packed) into `d`, so the caller's buffer
+// is free again when this returns; a device image is read where it lies.
+static int stage_gray(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes, int rows, int cols,
+                      char* staging, DevBuf& d, const uint8_t** gray, int* gray_step) {
+  *gray = (const uint8_t*)img_device, *gray_step = step_bytes;
+  if (!img_host) return FLAME_NLTGV2_OK;
+  for (int r = 0; r < rows; ++r) std::memcpy(staging + (size_t)r * cols, img_host + (size_t)r * step_bytes, (size_t)cols);
+  HIPCHK(ctx, hipMemcpyAsync(d.p, staging, (size_t)rows * (size_t)cols, hipMemcpyHostToDevice, ctx->raster_stream));
+  *gray = (const uint8_t*)d.p, *gray_step = cols;
+  return FLAME_NLTGV2_OK;
+}
+
+static flame_hip::WireBuffers wire_buffers(const flame_nltgv2_ctx* ctx) {
+  flame_hip::WireBuffers wb;
+  wb.draws = (flame_hip::WireDraw*)ctx->w_draws.p, wb.cnt = (uint32_t*)ctx->w_cnt.p, wb.offset = (uint32_t*)ctx->w_off.p;
+  wb.fill = (uint32_t*)ctx->w_fill.p, wb.entries = (uint64_t*)ctx->w_entries.p, wb.capacity = (uint32_t)ctx->w_cap;
+  wb.counts = (int*)ctx->w_counts.p;
+  return wb;
+}
+static_assert(flame_hip::kWireCounts * sizeof(int) <= kWireCountBytes, "wire_layout reserves too little for the counters");
+
 extern "C" {
 
 // Shared tail of the two interpolate_mesh entry points: triangles/validity -> device, rasterise, copy back.
-static int interpolate_common(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, int32_t V,
+static int interpolate_common(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, int32_t V, bool foreign,
                               const uint8_t* vtx_valid, const uint8_t* tri_valid, const float2* d_vtx,
                               const float* d_val, float value_scale, int rows, int cols, float* out, int32_t* coverage) {
   if (T < 0 || rows <= 0 || cols <= 0 || !out || (T > 0 && !triangles)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  for (int32_t t = 0; t < 3 * T; ++t)
-    if (triangles[t] < 0 || triangles[t] >= V) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!triangles_in_range(triangles, T, V)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const size_t n = (size_t)rows * (size_t)cols;
   int rc = ensure(ctx, ctx->r_tris, sizeof(int32_t) * 3 * (size_t)T);
   if (!rc) rc = ensure(ctx, ctx->r_valid, (size_t)T + (size_t)V + 16);
@@ -41,7 +106,8 @@ static int interpolate_common(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
   if (!rc) rc = ensure(ctx, ctx->r_cov, sizeof(int));
   if (rc) return rc;
   if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, ctx->stream));
-  ctx->tris_gen++, ctx->keys_gen = (tri_valid || vtx_valid) ? 0 : ctx->tris_gen;  // (r_keys: see flame_nltgv2_debug_images_begin)
+  if (foreign) ctx->tris.uploaded_foreign(tri_valid || vtx_valid);
+  else ctx->tris.uploaded(T, ctx->topo, tri_valid || vtx_valid);
   uint8_t* d_tv = nullptr;
   uint8_t* d_vv = nullptr;
   if (tri_valid && T > 0) {
@@ -73,25 +139,17 @@ int flame_nltgv2_interpolate_mesh_begin(flame_nltgv2_ctx* ctx, const int32_t* tr
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   const int32_t V = ctx->L.V;
   if (T < 0 || rows <= 0 || cols <= 0 || (T > 0 && !triangles)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  for (int32_t t = 0; t < 3 * T; ++t)
-    if (triangles[t] < 0 || triangles[t] >= V) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!triangles_in_range(triangles, T, V)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const size_t n = (size_t)rows * (size_t)cols;
   hipStream_t rs = ctx->raster_stream;
   const bool trace = std::getenv("FLAME_NLTGV2_TRACE") != nullptr;
   const auto tr0 = std::chrono::steady_clock::now();
   auto tr_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr0).count(); };
   double tr_a = 0, tr_b = 0, tr_c = 0, tr_d = 0;
-  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned map and the device buffers are about to be reused)
-  if (ctx->h_img_cap < n + 16) {
-    request_open_stop(ctx);  // (the pinned allocator waits for the device)
-    if (ctx->h_img) (void)hipHostFree(ctx->h_img);
-    ctx->h_img = nullptr, ctx->h_img_cap = 0;
-    if (hipHostMalloc((void**)&ctx->h_img, sizeof(float) * (n + 16), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, FLAME_NLTGV2_ERR_OOM);
-    }
-    ctx->h_img_cap = n + 16;
-  }
+  bool replaced = false;
+  rc = open_stage(ctx, ctx->h_img, sizeof(float) * (n + 16), &replaced);  // pinned: the map | the coverage count
+  if (replaced) ctx->img_pending_rows = ctx->img_pending_cols = 0;
+  if (rc) return rc;
   // the caller's triangles go up first (pageable memory: the copy holds the host), while the solver still runs ...
   rc = ensure(ctx, ctx->r_tris, sizeof(int32_t) * 3 * (size_t)T);
   if (!rc) rc = ensure(ctx, ctx->r_tvalid, (size_t)T + 16);  // (its own buffer: project_graph writes r_valid on the context's stream)
@@ -100,26 +158,23 @@ int flame_nltgv2_interpolate_mesh_begin(flame_nltgv2_ctx* ctx, const int32_t* tr
   if (!rc) rc = ensure(ctx, ctx->r_cov, sizeof(int));
   if (rc) return rc;
   if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
-  ctx->tris_gen++, ctx->keys_gen = tri_valid ? 0 : ctx->tris_gen;  // (r_keys: see flame_nltgv2_debug_images_begin)
+  ctx->tris.uploaded(T, ctx->topo, tri_valid != nullptr);  // (what mesh_outputs_begin(triangles = NULL) and the debug stages refer to)
   uint8_t* d_tv = nullptr;
   if (tri_valid && T > 0) {
     d_tv = (uint8_t*)ctx->r_tvalid.p;
     HIPCHK(ctx, hipMemcpyAsync(d_tv, tri_valid, (size_t)T, hipMemcpyHostToDevice, rs));
   }
   tr_a = tr_us();
-  ctx->tris_T = T, ctx->tris_topo = ctx->topo;  // (what flame_nltgv2_mesh_outputs_begin(triangles = NULL) refers to)
   rc = mesh_state_on(ctx, rs);  // ... it stops here, and may go on as soon as the caller enqueues the next run
   if (rc) return rc;
   tr_b = tr_us();
   LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.x, graph_scale, nullptr, d_tv,
                                          (unsigned long long*)ctx->r_keys.p, (float*)ctx->r_img.p, (int*)ctx->r_cov.p, rows, cols, rs));
-  // the rasteriser's kernels are the last readers of the canonical arrays (and the writers of the resident map): whoever rewrites those
-  // waits for THEM, not for the map's way out to the host (0.05 ms at 640x480, 0.3 ms at 1920x1080 -- time a commit would stand still for)
   tr_c = tr_us();
-  HIPCHK(ctx, hipEventRecord(ctx->ev_raster_done, rs));
-  ctx->raster_inflight = true;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->h_img, ctx->r_img.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->h_img + n, ctx->r_cov.p, sizeof(int), hipMemcpyDeviceToHost, rs));
+  rc = side_kernels_read_last(ctx);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_img.p, ctx->r_img.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_img.p + sizeof(float) * n, ctx->r_cov.p, sizeof(int), hipMemcpyDeviceToHost, rs));
   ctx->map_rows = rows, ctx->map_cols = cols;
   ctx->img_pending_rows = rows, ctx->img_pending_cols = cols;  // (what _end describes: a synchronous interpolate_mesh in between changes map_rows)
   tr_d = tr_us();
@@ -133,11 +188,11 @@ int flame_nltgv2_interpolate_mesh_end(flame_nltgv2_ctx* ctx, const float** map_o
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_interpolate_mesh_end");
   int rc = enter(ctx);
   if (rc) return rc;
-  if (!ctx->h_img || ctx->img_pending_rows == 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!ctx->h_img.p || ctx->img_pending_rows == 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
   const size_t n = (size_t)ctx->img_pending_rows * (size_t)ctx->img_pending_cols;
-  if (map_out) *map_out = ctx->h_img;
-  if (coverage_out) std::memcpy(coverage_out, ctx->h_img + n, sizeof(int32_t));
+  if (map_out) *map_out = (const float*)ctx->h_img.p;
+  if (coverage_out) std::memcpy(coverage_out, ctx->h_img.p + sizeof(float) * n, sizeof(int32_t));
   return FLAME_NLTGV2_OK;
 }
 
@@ -150,10 +205,10 @@ int flame_nltgv2_interpolate_mesh(flame_nltgv2_ctx* ctx, const int32_t* triangle
   rc = ensure_canon(ctx);
   if (rc) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));  // (r_img may still be on its way out for an interpolate_mesh_begin)
-  rc = interpolate_common(ctx, triangles, T, ctx->L.V, nullptr, tri_valid, ctx->c.pos, ctx->c.x, graph_scale, rows,
+  rc = interpolate_common(ctx, triangles, T, ctx->L.V, false, nullptr, tri_valid, ctx->c.pos, ctx->c.x, graph_scale, rows,
                           cols, idepthmap_out, coverage_out);
   if (!rc) ctx->map_rows = rows, ctx->map_cols = cols;  // (the map stays on the device: flame_nltgv2_sync_input.init_from_map)
-  ctx->tris_T = rc ? -1 : T, ctx->tris_topo = ctx->topo;
+  else ctx->tris.none_resident();
   return rc;
 }
 
@@ -174,8 +229,8 @@ int flame_nltgv2_interpolate_mesh_arrays(flame_nltgv2_ctx* ctx, const int32_t* t
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
   ctx->map_rows = ctx->map_cols = 0;  // (r_img will hold an image of the caller's arrays, not the graph's map)
-  ctx->tris_T = -1;                   // (... and r_tris triangles of those arrays)
-  return interpolate_common(ctx, triangles, T, V, vtx_valid, tri_valid, (const float2*)ctx->r_vtx.p,
+  ctx->tris.none_resident();          // (... and r_tris triangles of those arrays)
+  return interpolate_common(ctx, triangles, T, V, true, vtx_valid, tri_valid, (const float2*)ctx->r_vtx.p,
                             (const float*)ctx->r_val.p, 1.0f, rows, cols, img_out, coverage_out);
 }
 
@@ -219,8 +274,7 @@ float flame_nltgv2_oblique_cos_bound(float thresh) {
   return ord_float(hi);
 }
 
-// The mesh outputs on the side stream (see flame_nltgv2.h).  Everything is checked before the stream or a buffer is touched: an error
-// leaves what an earlier begin put into the pinned outputs, and its pending _end, as they are.
+// The mesh outputs on the side stream (see flame_nltgv2.h).
 int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, const float* Kinv,
                                     const flame_nltgv2_mesh_filter_params* filter, int rows, int cols, float graph_scale,
                                     int want_filtered_map) {
@@ -230,32 +284,15 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   const int32_t V = ctx->L.V;
   if (T < 0 || rows <= 0 || cols <= 0 || !Kinv || !filter) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  if (!triangles && (ctx->tris_T != T || ctx->tris_topo != ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  if (triangles)
-    for (int32_t t = 0; t < 3 * T; ++t)
-      if (triangles[t] < 0 || triangles[t] >= V) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!triangles && !ctx->tris.matches(T, ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (triangles && !triangles_in_range(triangles, T, V)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const size_t n = want_filtered_map ? (size_t)rows * (size_t)cols : 0;
   hipStream_t rs = ctx->raster_stream;
-  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned outputs and the device buffers are about to be reused)
-  // pinned outputs: normals | vtx_idepth | n_valid, coverage | filtered map | tri_valid
   flame_nltgv2_ctx::MeshPending mp;
   mp.V = V, mp.T = T, mp.rows = want_filtered_map ? rows : 0, mp.cols = want_filtered_map ? cols : 0;
-  mp.off_idepth = sizeof(float) * 3 * (size_t)V;
-  mp.off_counts = mp.off_idepth + sizeof(float) * (size_t)V;
-  mp.off_map = mp.off_counts + 4 * sizeof(int32_t);
-  mp.off_valid = mp.off_map + sizeof(float) * n;
-  const size_t h_bytes = mp.off_valid + (size_t)T + 16;
-  if (ctx->h_mesh_cap < h_bytes) {
-    request_open_stop(ctx);  // (the pinned allocator waits for the device)
-    void* h = nullptr;
-    if (hipHostMalloc(&h, h_bytes + h_bytes / 2, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
-    }
-    if (ctx->h_mesh) (void)hipHostFree(ctx->h_mesh);
-    ctx->h_mesh = (char*)h, ctx->h_mesh_cap = h_bytes + h_bytes / 2;
-    ctx->mesh_pending.active = false;
-  }
+  mp.at = mesh_layout(V, T, rows, cols, want_filtered_map != 0);
+  rc = open_stage(ctx, ctx->mesh, mp.at.total);
+  if (rc) return rc;
   const size_t fV = sizeof(float) * (size_t)V;
   rc = ensure(ctx, ctx->m_P, 4 * fV);
   if (!rc) rc = ensure(ctx, ctx->m_idepth, fV);
@@ -273,11 +310,10 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
     if (!rc) rc = ensure(ctx, ctx->m_cov, sizeof(int));
   }
   if (rc) return rc;
-  ctx->mesh_pending.active = false;  // (from here on the pinned outputs are being rewritten)
+  ctx->mesh.active = false;  // (from here on the pinned outputs are being rewritten)
   if (triangles) {
     if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->r_tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
-    ctx->tris_T = T, ctx->tris_topo = ctx->topo;
-    ctx->tris_gen++;  // (r_keys no longer speaks of r_tris)
+    ctx->tris.uploaded_unrasterised(T, ctx->topo);  // (r_keys no longer speaks of r_tris)
   }
   flame_hip::MeshFilter mf;
   std::memcpy(mf.Kinv, Kinv, sizeof(mf.Kinv));
@@ -294,30 +330,28 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
   mb.P = (float4*)ctx->m_P.p, mb.vtx_idepth = (float*)ctx->m_idepth.p, mb.normals = (float*)ctx->m_normals.p;
   mb.tri_valid = (uint8_t*)ctx->m_tvalid.p, mb.n_valid = (int*)ctx->m_nvalid.p, mb.tri_normal = (float4*)ctx->m_tnormal.p;
   mb.offset = (int*)ctx->m_offset.p, mb.cursor = (int*)ctx->m_cursor.p, mb.incident = (int32_t*)ctx->m_incident.p;
-  ctx->tvalid_have = true, ctx->tvalid_gen = ctx->tris_gen, ctx->tvalid_T = T, ctx->tvalid_topo = ctx->topo;  // (flame_nltgv2_debug_wireframe_begin, validity == 2)
+  ctx->tris.validity_written();  // (flame_nltgv2_debug_wireframe_begin, validity == 2)
   rc = mesh_state_on(ctx, rs);
   if (rc) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_mesh0, rs));
+  HIPCHK(ctx, hipEventRecord(ctx->mesh.ev0, rs));
   LAUNCHCHK(ctx, flame_hip::launch_mesh_outputs(V, T, ctx->c.pos, ctx->c.x, graph_scale, (const int32_t*)ctx->r_tris.p, mf, mb, rs));
   // the filtered map: the rasteriser of interpolate_mesh over the idepths and the validity this stage has just left on the device
   if (want_filtered_map)
     LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, mb.vtx_idepth, 1.0f, nullptr, mb.tri_valid,
                                            (unsigned long long*)ctx->m_keys.p, (float*)ctx->m_img.p, (int*)ctx->m_cov.p, rows, cols, rs));
-  HIPCHK(ctx, hipEventRecord(ctx->ev_raster_done, rs));  // (the last readers of the canonical pos / x: see interpolate_mesh_begin)
-  ctx->raster_inflight = true;
-  char* h = ctx->h_mesh;
-  HIPCHK(ctx, hipMemcpyAsync(h, mb.normals, 3 * fV, hipMemcpyDeviceToHost, rs));
-  HIPCHK(ctx, hipMemcpyAsync(h + mp.off_idepth, mb.vtx_idepth, fV, hipMemcpyDeviceToHost, rs));
-  HIPCHK(ctx, hipMemcpyAsync(h + mp.off_counts, mb.n_valid, sizeof(int), hipMemcpyDeviceToHost, rs));
-  if (T > 0) HIPCHK(ctx, hipMemcpyAsync(h + mp.off_valid, mb.tri_valid, (size_t)T, hipMemcpyDeviceToHost, rs));
+  rc = side_kernels_read_last(ctx);  // (of the canonical pos / x)
+  if (rc) return rc;
+  char* h = ctx->mesh.h.p;
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.at.normals, mb.normals, 3 * fV, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.at.idepth, mb.vtx_idepth, fV, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.at.counts, mb.n_valid, sizeof(int), hipMemcpyDeviceToHost, rs));
+  if (T > 0) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.valid, mb.tri_valid, (size_t)T, hipMemcpyDeviceToHost, rs));
   if (want_filtered_map) {
-    HIPCHK(ctx, hipMemcpyAsync(h + mp.off_map, ctx->m_img.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
-    HIPCHK(ctx, hipMemcpyAsync(h + mp.off_counts + sizeof(int32_t), ctx->m_cov.p, sizeof(int), hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + mp.at.map, ctx->m_img.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + mp.at.counts + sizeof(int32_t), ctx->m_cov.p, sizeof(int), hipMemcpyDeviceToHost, rs));
   }
-  HIPCHK(ctx, hipEventRecord(ctx->ev_mesh1, rs));
-  mp.active = true;
   ctx->mesh_pending = mp;
-  return FLAME_NLTGV2_OK;
+  return close_stage(ctx, ctx->mesh);
 }
 
 int flame_nltgv2_mesh_outputs_end(flame_nltgv2_ctx* ctx, flame_nltgv2_mesh_outputs_view* out) {
@@ -325,21 +359,20 @@ int flame_nltgv2_mesh_outputs_end(flame_nltgv2_ctx* ctx, flame_nltgv2_mesh_outpu
   int rc = enter(ctx);
   if (rc) return rc;
   const flame_nltgv2_ctx::MeshPending& mp = ctx->mesh_pending;
-  if (!out || !ctx->h_mesh || !mp.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!out || !ctx->mesh.h.p || !ctx->mesh.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
-  const char* h = ctx->h_mesh;
+  const char* h = ctx->mesh.h.p;
   int32_t counts[2];
-  std::memcpy(counts, h + mp.off_counts, sizeof(counts));
+  std::memcpy(counts, h + mp.at.counts, sizeof(counts));
   out->V = mp.V, out->T = mp.T;
-  out->tri_valid = (const uint8_t*)(h + mp.off_valid);
-  out->normals = (const float*)h;
-  out->vtx_idepth = (const float*)(h + mp.off_idepth);
+  out->tri_valid = (const uint8_t*)(h + mp.at.valid);
+  out->normals = (const float*)(h + mp.at.normals);
+  out->vtx_idepth = (const float*)(h + mp.at.idepth);
   out->n_valid = counts[0];
   out->rows = mp.rows, out->cols = mp.cols;
-  out->filtered_map = mp.rows > 0 ? (const float*)(h + mp.off_map) : nullptr;
+  out->filtered_map = mp.rows > 0 ? (const float*)(h + mp.at.map) : nullptr;
   out->filtered_coverage = mp.rows > 0 ? counts[1] : 0;
-  out->device_ms = 0.0f;
-  if (hipEventElapsedTime(&out->device_ms, ctx->ev_mesh0, ctx->ev_mesh1) != hipSuccess) (void)hipGetLastError(), out->device_ms = 0.0f;
+  out->device_ms = stage_ms(ctx->mesh);
   return FLAME_NLTGV2_OK;
 }
 
@@ -370,8 +403,7 @@ void flame_nltgv2_default_debug_image_params(flame_nltgv2_debug_image_params* p)
   p->want_normals = 1;
 }
 
-// The debug images on the side stream (see flame_nltgv2.h).  Like mesh_outputs_begin: everything is checked before the stream or a
-// buffer is touched, so an error leaves what an earlier begin put into the pinned outputs, and its pending _end, as they are.
+// The debug images on the side stream (see flame_nltgv2.h).
 int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
                                     const float* K, const flame_nltgv2_debug_image_params* params, int rows, int cols) {
   flame_hip::RoctxRange roctx_range_("flame_nltgv2_debug_images_begin");
@@ -379,34 +411,20 @@ int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_ho
   if (rc) return rc;
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (rows <= 0 || cols <= 0 || ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  if (ctx->tris_T < 0 || ctx->tris_topo != ctx->topo) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if ((img_host != nullptr) == (img_device != nullptr) || step_bytes < cols || !K || !params) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  const int32_t T = ctx->tris_T;
+  const int32_t T = ctx->tris.T();
   const size_t n = (size_t)rows * (size_t)cols;
   const bool want_id = params->want_idepthmap != 0, want_n = params->want_normals != 0;
   hipStream_t rs = ctx->raster_stream;
-  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned outputs and the device buffers are about to be reused)
-  // pinned: idepth image | normals image | w1 map | w2 map | the grey image on its way up
   flame_nltgv2_ctx::DebugPending dp;
-  auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
   dp.rows = rows, dp.cols = cols, dp.want_idepth = want_id, dp.want_normals = want_n;
-  dp.off_nimg = up16(want_id ? 3 * n : 0);
-  dp.off_w1 = dp.off_nimg + up16(want_n ? 3 * n : 0);
-  dp.off_w2 = dp.off_w1 + up16(want_n ? sizeof(float) * n : 0);
-  dp.off_gray = dp.off_w2 + up16(want_n ? sizeof(float) * n : 0);
-  const size_t h_bytes = dp.off_gray + up16(img_host ? n : 0) + 16;
-  if (ctx->h_dbg_cap < h_bytes) {
-    request_open_stop(ctx);  // (the pinned allocator waits for the device)
-    void* h = nullptr;
-    if (hipHostMalloc(&h, h_bytes + h_bytes / 2, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
-    }
-    if (ctx->h_dbg) (void)hipHostFree(ctx->h_dbg);
-    ctx->h_dbg = (char*)h, ctx->h_dbg_cap = h_bytes + h_bytes / 2;
-    ctx->debug_pending.active = false;
-  }
-  const bool from_keys = ctx->keys_gen != 0 && ctx->keys_gen == ctx->tris_gen;
+  dp.at = debug_layout(rows, cols, want_id, want_n, img_host != nullptr);
+  rc = open_stage(ctx, ctx->dbg, dp.at.total);
+  if (rc) return rc;
+  // r_keys names the winners of an all-valid rasterisation of r_tris: w1 / w2 are looked up there.  Otherwise (a map rasterised with
+  // tri_valid, triangles re-uploaded by mesh_outputs_begin) the stage rasterises them itself
+  const bool from_keys = ctx->tris.keys_name_winners();
   if (img_host) rc = ensure(ctx, ctx->d_gray, n + 16);
   if (!rc && want_id) rc = ensure(ctx, ctx->d_idimg, 3 * n + 16);
   if (!rc && want_n) {
@@ -417,23 +435,19 @@ int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_ho
     if (!rc && !from_keys) rc = ensure(ctx, ctx->d_cov, sizeof(int));
   }
   if (rc) return rc;
-  ctx->debug_pending.active = false;  // (from here on the pinned outputs are being rewritten)
-  char* h = ctx->h_dbg;
+  ctx->dbg.active = false;  // (from here on the pinned outputs are being rewritten)
+  char* h = ctx->dbg.h.p;
   flame_hip::DebugImageArgs a;
   a.rows = rows, a.cols = cols;
-  a.gray = (const uint8_t*)img_device, a.gray_step = step_bytes;
   a.scene_color_scale = params->scene_color_scale, a.flip = params->flip != 0;
   a.k00 = K[0], a.k11 = K[4];
-  if (img_host) {  // through pinned memory, rows packed: the caller's buffer is free again when this returns
-    for (int r = 0; r < rows; ++r) std::memcpy(h + dp.off_gray + (size_t)r * cols, img_host + (size_t)r * step_bytes, (size_t)cols);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_gray.p, h + dp.off_gray, n, hipMemcpyHostToDevice, rs));
-    a.gray = (const uint8_t*)ctx->d_gray.p, a.gray_step = cols;
-  }
+  rc = stage_gray(ctx, img_host, img_device, step_bytes, rows, cols, h + dp.at.gray, ctx->d_gray, &a.gray, &a.gray_step);
+  if (rc) return rc;
   if (want_n) {  // (w1 / w2 of the state mesh_state_on selects; the idepth image needs the resident map alone)
     rc = mesh_state_on(ctx, rs);
     if (rc) return rc;
   }
-  HIPCHK(ctx, hipEventRecord(ctx->ev_dbg0, rs));
+  HIPCHK(ctx, hipEventRecord(ctx->dbg.ev0, rs));
   if (want_n) {
     if (from_keys) {
       LAUNCHCHK(ctx, flame_hip::launch_debug_wmaps((const unsigned long long*)ctx->r_keys.p, (const int32_t*)ctx->r_tris.p, ctx->c.pos,
@@ -444,21 +458,19 @@ int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_ho
       LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.w2, 1.0f, nullptr, nullptr,
                                              (unsigned long long*)ctx->d_keys.p, (float*)ctx->d_w2map.p, (int*)ctx->d_cov.p, rows, cols, rs));
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_raster_done, rs));  // (the last readers of the canonical pos / w1 / w2: see interpolate_mesh_begin)
-    ctx->raster_inflight = true;
+    rc = side_kernels_read_last(ctx);  // (of the canonical pos / w1 / w2)
+    if (rc) return rc;
   }
   LAUNCHCHK(ctx, flame_hip::launch_debug_images(a, (const float*)ctx->r_img.p, (const float*)ctx->d_w1map.p, (const float*)ctx->d_w2map.p,
                                                 want_id ? (uint8_t*)ctx->d_idimg.p : nullptr, want_n ? (uint8_t*)ctx->d_nimg.p : nullptr, rs));
-  if (want_id) HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_idimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
+  if (want_id) HIPCHK(ctx, hipMemcpyAsync(h + dp.at.idimg, ctx->d_idimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
   if (want_n) {
-    HIPCHK(ctx, hipMemcpyAsync(h + dp.off_nimg, ctx->d_nimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
-    HIPCHK(ctx, hipMemcpyAsync(h + dp.off_w1, ctx->d_w1map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
-    HIPCHK(ctx, hipMemcpyAsync(h + dp.off_w2, ctx->d_w2map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + dp.at.nimg, ctx->d_nimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + dp.at.w1, ctx->d_w1map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    HIPCHK(ctx, hipMemcpyAsync(h + dp.at.w2, ctx->d_w2map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
   }
-  HIPCHK(ctx, hipEventRecord(ctx->ev_dbg1, rs));
-  dp.active = true;
   ctx->debug_pending = dp;
-  return FLAME_NLTGV2_OK;
+  return close_stage(ctx, ctx->dbg);
 }
 
 int flame_nltgv2_debug_images_end(flame_nltgv2_ctx* ctx, flame_nltgv2_debug_images_view* out) {
@@ -466,16 +478,15 @@ int flame_nltgv2_debug_images_end(flame_nltgv2_ctx* ctx, flame_nltgv2_debug_imag
   int rc = enter(ctx);
   if (rc) return rc;
   const flame_nltgv2_ctx::DebugPending& dp = ctx->debug_pending;
-  if (!out || !ctx->h_dbg || !dp.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!out || !ctx->dbg.h.p || !ctx->dbg.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
-  const char* h = ctx->h_dbg;
+  const char* h = ctx->dbg.h.p;
   out->rows = dp.rows, out->cols = dp.cols;
-  out->idepthmap_img = dp.want_idepth ? (const uint8_t*)h : nullptr;
-  out->normals_img = dp.want_normals ? (const uint8_t*)(h + dp.off_nimg) : nullptr;
-  out->w1_map = dp.want_normals ? (const float*)(h + dp.off_w1) : nullptr;
-  out->w2_map = dp.want_normals ? (const float*)(h + dp.off_w2) : nullptr;
-  out->device_ms = 0.0f;
-  if (hipEventElapsedTime(&out->device_ms, ctx->ev_dbg0, ctx->ev_dbg1) != hipSuccess) (void)hipGetLastError(), out->device_ms = 0.0f;
+  out->idepthmap_img = dp.want_idepth ? (const uint8_t*)(h + dp.at.idimg) : nullptr;
+  out->normals_img = dp.want_normals ? (const uint8_t*)(h + dp.at.nimg) : nullptr;
+  out->w1_map = dp.want_normals ? (const float*)(h + dp.at.w1) : nullptr;
+  out->w2_map = dp.want_normals ? (const float*)(h + dp.at.w2) : nullptr;
+  out->device_ms = stage_ms(ctx->dbg);
   return FLAME_NLTGV2_OK;
 }
 
@@ -505,21 +516,16 @@ void flame_nltgv2_default_wireframe_params(flame_nltgv2_wireframe_params* p) {
 // fill + fold + the picture's way out, on the side stream: the second half of a wireframe call, which _end repeats with a larger
 // entry buffer where the entries did not fit
 static int wireframe_second_half(flame_nltgv2_ctx* ctx, const flame_nltgv2_ctx::WirePending& wp) {
-  flame_hip::WireBuffers wb;
-  wb.draws = (flame_hip::WireDraw*)ctx->w_draws.p, wb.cnt = (uint32_t*)ctx->w_cnt.p, wb.offset = (uint32_t*)ctx->w_off.p;
-  wb.fill = (uint32_t*)ctx->w_fill.p, wb.entries = (uint64_t*)ctx->w_entries.p, wb.capacity = (uint32_t)ctx->w_cap;
-  wb.counts = (int*)ctx->w_counts.p;
   flame_hip::WireImageArgs a;
   a.rows = wp.rows, a.cols = wp.cols, a.gray = wp.gray, a.gray_step = wp.gray_step;
   a.scene_color_scale = wp.scene_color_scale, a.flip = wp.flip;
   hipStream_t rs = ctx->raster_stream;
-  LAUNCHCHK(ctx, flame_hip::launch_wireframe_paint(wp.T, wb, a, (uint8_t*)ctx->w_img.p, rs));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->h_wire, ctx->w_img.p, 3 * (size_t)wp.rows * (size_t)wp.cols, hipMemcpyDeviceToHost, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_wireframe_paint(wp.T, wire_buffers(ctx), a, (uint8_t*)ctx->w_img.p, rs));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->wire.h.p + wp.at.img, ctx->w_img.p, 3 * (size_t)wp.rows * (size_t)wp.cols, hipMemcpyDeviceToHost, rs));
   return FLAME_NLTGV2_OK;
 }
 
-// The wireframe image on the side stream (see flame_nltgv2.h).  Like debug_images_begin: everything is checked before the stream or a
-// buffer is touched, so an error leaves what an earlier begin put into the pinned outputs, and its pending _end, as they are.
+// The wireframe image on the side stream (see flame_nltgv2.h).
 int flame_nltgv2_debug_wireframe_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes,
                                        const uint8_t* tri_valid, const flame_nltgv2_wireframe_params* params, int rows, int cols,
                                        float graph_scale) {
@@ -528,35 +534,20 @@ int flame_nltgv2_debug_wireframe_begin(flame_nltgv2_ctx* ctx, const uint8_t* img
   if (rc) return rc;
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
   if (rows <= 0 || cols <= 0 || rows > 32767 || cols > 32767) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (int16 endpoints)
-  if (ctx->tris_T < 0 || ctx->tris_topo != ctx->topo) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if ((img_host != nullptr) == (img_device != nullptr) || step_bytes < cols || !params) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (params->validity < 0 || params->validity > 2 || (tri_valid != nullptr) != (params->validity == 1)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  const int32_t T = ctx->tris_T;
-  if (params->validity == 2 && !(ctx->tvalid_have && ctx->tvalid_gen == ctx->tris_gen && ctx->tvalid_T == T && ctx->tvalid_topo == ctx->topo))
-    return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t T = ctx->tris.T();
+  if (params->validity == 2 && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   // every draw visits at most max(rows, cols) pixels: the entries, their offsets and the draw ids are 32-bit
   if ((uint64_t)3 * (uint64_t)T * (uint64_t)(rows > cols ? rows : cols) >= (1ull << 31)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const size_t n = (size_t)rows * (size_t)cols;
   hipStream_t rs = ctx->raster_stream;
-  HIPCHK(ctx, hipStreamSynchronize(rs));  // (a begin without its end: the pinned outputs and the device buffers are about to be reused)
-  // pinned: the picture | the counters | the grey image on its way up
   flame_nltgv2_ctx::WirePending wp;
-  auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
   wp.rows = rows, wp.cols = cols, wp.flip = params->flip != 0, wp.T = T, wp.scene_color_scale = params->scene_color_scale;
-  wp.off_counts = up16(3 * n);
-  wp.off_gray = wp.off_counts + 16;
-  const size_t h_bytes = wp.off_gray + up16(img_host ? n : 0) + 16;
-  if (ctx->h_wire_cap < h_bytes) {
-    request_open_stop(ctx);  // (the pinned allocator waits for the device)
-    void* h = nullptr;
-    if (hipHostMalloc(&h, h_bytes + h_bytes / 2, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, FLAME_NLTGV2_ERR_OOM);  // (the old buffer and what it holds stay)
-    }
-    if (ctx->h_wire) (void)hipHostFree(ctx->h_wire);
-    ctx->h_wire = (char*)h, ctx->h_wire_cap = h_bytes + h_bytes / 2;
-    ctx->wire_pending.active = false;
-  }
+  wp.at = wire_layout(rows, cols, img_host != nullptr);
+  rc = open_stage(ctx, ctx->wire, wp.at.total);
+  if (rc) return rc;
   size_t want = 2 * n, grown = ctx->w_last_total + ctx->w_last_total / 4 + 1;
   if (grown > want) want = grown;
   if (want < ctx->w_cap) want = ctx->w_cap;  // (never shrinks)
@@ -572,14 +563,10 @@ int flame_nltgv2_debug_wireframe_begin(flame_nltgv2_ctx* ctx, const uint8_t* img
   if (!rc && tri_valid) rc = ensure(ctx, ctx->w_tvalid, (size_t)T + 16);
   if (rc) return rc;
   ctx->w_cap = want;
-  ctx->wire_pending.active = false;  // (from here on the pinned outputs are being rewritten)
-  char* h = ctx->h_wire;
-  wp.gray = (const uint8_t*)img_device, wp.gray_step = step_bytes;
-  if (img_host) {  // through pinned memory, rows packed: the caller's buffer is free again when this returns
-    for (int r = 0; r < rows; ++r) std::memcpy(h + wp.off_gray + (size_t)r * cols, img_host + (size_t)r * step_bytes, (size_t)cols);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->w_gray.p, h + wp.off_gray, n, hipMemcpyHostToDevice, rs));
-    wp.gray = (const uint8_t*)ctx->w_gray.p, wp.gray_step = cols;
-  }
+  ctx->wire.active = false;  // (from here on the pinned outputs are being rewritten)
+  char* h = ctx->wire.h.p;
+  rc = stage_gray(ctx, img_host, img_device, step_bytes, rows, cols, h + wp.at.gray, ctx->w_gray, &wp.gray, &wp.gray_step);
+  if (rc) return rc;
   const uint8_t* d_tv = nullptr;
   if (params->validity == 1 && T > 0) {  // (pageable memory: the copy holds the host until the bytes have left the caller's array)
     HIPCHK(ctx, hipMemcpyAsync(ctx->w_tvalid.p, tri_valid, (size_t)T, hipMemcpyHostToDevice, rs));
@@ -589,22 +576,16 @@ int flame_nltgv2_debug_wireframe_begin(flame_nltgv2_ctx* ctx, const uint8_t* img
   }
   rc = mesh_state_on(ctx, rs);
   if (rc) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_wire0, rs));
-  flame_hip::WireBuffers wb;
-  wb.draws = (flame_hip::WireDraw*)ctx->w_draws.p, wb.cnt = (uint32_t*)ctx->w_cnt.p, wb.offset = (uint32_t*)ctx->w_off.p;
-  wb.fill = (uint32_t*)ctx->w_fill.p, wb.entries = (uint64_t*)ctx->w_entries.p, wb.capacity = (uint32_t)ctx->w_cap;
-  wb.counts = (int*)ctx->w_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->wire.ev0, rs));
   // the setup kernel is the last reader of the canonical pos / x (see interpolate_mesh_begin): ev_raster_done goes right behind it
-  LAUNCHCHK(ctx, flame_hip::launch_wireframe_lists(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.x, graph_scale, d_tv, wb, rows, cols,
-                                                   ctx->ev_raster_done, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_wireframe_lists(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, ctx->c.x, graph_scale, d_tv, wire_buffers(ctx), rows,
+                                                   cols, ctx->ev_raster_done, rs));
   ctx->raster_inflight = true;
-  HIPCHK(ctx, hipMemcpyAsync(h + wp.off_counts, ctx->w_counts.p, flame_hip::kWireCounts * sizeof(int), hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(h + wp.at.counts, ctx->w_counts.p, flame_hip::kWireCounts * sizeof(int), hipMemcpyDeviceToHost, rs));
   rc = wireframe_second_half(ctx, wp);
   if (rc) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_wire1, rs));
-  wp.active = true;
   ctx->wire_pending = wp;
-  return FLAME_NLTGV2_OK;
+  return close_stage(ctx, ctx->wire);
 }
 
 int flame_nltgv2_debug_wireframe_end(flame_nltgv2_ctx* ctx, flame_nltgv2_wireframe_view* out) {
@@ -612,32 +593,29 @@ int flame_nltgv2_debug_wireframe_end(flame_nltgv2_ctx* ctx, flame_nltgv2_wirefra
   int rc = enter(ctx);
   if (rc) return rc;
   const flame_nltgv2_ctx::WirePending wp = ctx->wire_pending;
-  if (!out || !ctx->h_wire || !wp.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!out || !ctx->wire.h.p || !ctx->wire.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
   int32_t counts[flame_hip::kWireCounts];
-  std::memcpy(counts, ctx->h_wire + wp.off_counts, sizeof(counts));
+  std::memcpy(counts, ctx->wire.h.p + wp.at.counts, sizeof(counts));
   const size_t total = (size_t)(uint32_t)counts[flame_hip::kWireTotal];
-  out->device_ms = 0.0f;
-  if (hipEventElapsedTime(&out->device_ms, ctx->ev_wire0, ctx->ev_wire1) != hipSuccess) (void)hipGetLastError(), out->device_ms = 0.0f;
+  out->device_ms = stage_ms(ctx->wire);
   out->refilled = 0;
   if (total > ctx->w_cap) {  // the entries did not fit: a larger buffer, then fill and fold once more (the records, cnt and offsets stand)
     const size_t want = total + total / 4 + 1;
     rc = ensure(ctx, ctx->w_entries, sizeof(uint64_t) * want);
     if (rc) return rc;
     ctx->w_cap = want;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_wire0, ctx->raster_stream));
+    HIPCHK(ctx, hipEventRecord(ctx->wire.ev0, ctx->raster_stream));
     rc = wireframe_second_half(ctx, wp);
     if (rc) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_wire1, ctx->raster_stream));
+    HIPCHK(ctx, hipEventRecord(ctx->wire.ev1, ctx->raster_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
-    float again = 0.0f;
-    if (hipEventElapsedTime(&again, ctx->ev_wire0, ctx->ev_wire1) != hipSuccess) (void)hipGetLastError(), again = 0.0f;
-    out->device_ms += again;
+    out->device_ms += stage_ms(ctx->wire);
     out->refilled = 1;
   }
   ctx->w_last_total = total;
   out->rows = wp.rows, out->cols = wp.cols;
-  out->wireframe_img = (const uint8_t*)ctx->h_wire;
+  out->wireframe_img = (const uint8_t*)(ctx->wire.h.p + wp.at.img);
   out->lines_drawn = counts[flame_hip::kWireDrawn], out->lines_skipped = counts[flame_hip::kWireSkipped];
   out->entries = (int64_t)total;
   return FLAME_NLTGV2_OK;

@@ -474,17 +474,8 @@ int flame_nltgv2_project_graph(flame_nltgv2_ctx* ctx, const flame_nltgv2_project
   // the keep mask is written by the kernel straight into pinned host memory, the positions as they stood are kept by the same kernel
   // (round 6: as a device-to-device copy, the kernel and a copy out to the caller's pageable array this call was three more trips
   // through the runtime, 10-16 us each, with the solver standing still: profiles/r06_holds.txt)
-  if (ctx->h_keep_cap < V + 16) {
-    request_open_stop(ctx);  // (the pinned allocator waits for the device)
-    if (ctx->h_keep) (void)hipHostFree(ctx->h_keep);
-    ctx->h_keep = nullptr, ctx->h_keep_cap = 0;
-    const size_t want = (V + 16) + (V + 16) / 2;
-    if (hipHostMalloc((void**)&ctx->h_keep, want, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, FLAME_NLTGV2_ERR_OOM);
-    }
-    ctx->h_keep_cap = want;
-  }
+  rc = grow_pinned(ctx, ctx->h_keep, V + 16);
+  if (rc) return rc;
   ProjectGeometry geo;
   std::memcpy(geo.K, pr->K, sizeof(geo.K));
   std::memcpy(geo.Kinv, pr->Kinv, sizeof(geo.Kinv));
@@ -499,7 +490,7 @@ int flame_nltgv2_project_graph(flame_nltgv2_ctx* ctx, const flame_nltgv2_project
   rc = ensure(ctx, save, sizeof(float) * 2 * V);
   if (rc) return rc;
   const std::function<int()> project = [&]() -> int {
-    LAUNCHCHK(ctx, launch_project_graph(ctx->c, graph_scale, geo, ctx->h_keep, (float2*)save.p, ctx->stream));
+    LAUNCHCHK(ctx, launch_project_graph(ctx->c, graph_scale, geo, (uint8_t*)ctx->h_keep.p, (float2*)save.p, ctx->stream));
     return 0;
   };
   // The kernel goes out BEHIND the rounds in flight and the unpack of their state, before the host has seen how they ended: one wait of
@@ -516,7 +507,7 @@ int flame_nltgv2_project_graph(flame_nltgv2_ctx* ctx, const flame_nltgv2_project
   if (first_since_layout && V) ctx->layout_pos_saved = true;
   if (V && pos_out) HIPCHK(ctx, hipMemcpyAsync(pos_out, ctx->pos.p, sizeof(float) * 2 * V, hipMemcpyDeviceToHost, ctx->stream));
   if (behind != kBehindDone || (V && pos_out)) HIPCHK(ctx, wait_solver_stream(ctx));
-  if (V) std::memcpy(keep_out, ctx->h_keep, V);
+  if (V) std::memcpy(keep_out, ctx->h_keep.p, V);
   ctx->fused_valid = false;  // x changed; pos changed: alpha/dx/dy of the packed records are stale until the next
                              // sync_graph / upload_graph re-derives them (the reference re-triangulates right after)
   ctx->static_stale = true;

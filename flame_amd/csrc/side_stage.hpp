@@ -1,0 +1,114 @@
+// side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
+// images, the wireframe), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
+// outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it.
+#ifndef FLAME_AMD_SIDE_STAGE_HPP_
+#define FLAME_AMD_SIDE_STAGE_HPP_
+
+#include <cstddef>
+#include <cstdint>
+
+namespace flame_hip {
+namespace host {
+
+// Which triangles r_tris holds, whether the key image r_keys names their winners, and whether the filter validity m_tvalid speaks of
+// them.  Every upload into r_tris counts `uploads` up; the key image and the validity remember the upload they were made from, so
+// another upload makes both stale without anybody having to say so.
+//   An upload counts up in every transition that makes T >= 0, so a count remembered while the triangles were current cannot meet
+// `uploads` again under other triangles, another T or another topology: the validity needs no T and no topology of its own.
+class ResidentTris {
+ public:
+  // -- transitions ---------------------------------------------------------------------------------------------------------
+  // T triangles of the graph of topology `topo` were uploaded and the graph's map rasterised from them (interpolate_mesh,
+  // interpolate_mesh_begin); masked: with a validity mask, so the key image does not name the winners of the all-valid rasterisation.
+  // interpolate_mesh_begin says so when the upload is enqueued, before mesh_state_on can fail: the triangles are resident then, whatever
+  // becomes of the map.
+  void uploaded(int32_t T, uint64_t topo, bool masked) {
+    T_ = T, topo_ = topo, ++uploads_;
+    keys_of_ = masked ? 0 : uploads_;
+  }
+  // Triangles that index the caller's arrays were uploaded and rasterised (interpolate_mesh_arrays): r_tris and r_keys are another
+  // image's.  The counts may agree afterwards; nothing is current, because no triangles of the graph are resident.
+  void uploaded_foreign(bool masked) {
+    T_ = -1, ++uploads_;
+    keys_of_ = masked ? 0 : uploads_;
+  }
+  // T triangles of the graph were uploaded and nothing rasterised (mesh_outputs_begin with a list of its own): the key image still
+  // describes the list before.
+  void uploaded_unrasterised(int32_t T, uint64_t topo) { T_ = T, topo_ = topo, ++uploads_; }
+  // The filters wrote m_tvalid for the resident triangles (mesh_outputs_begin).
+  void validity_written() { validity_of_ = uploads_; }
+  // No triangles of the graph are resident: interpolate_mesh_arrays is about to replace them, or a synchronous interpolate_mesh
+  // failed -- wherever it failed, also in its argument checks with the old list still in r_tris.
+  void none_resident() { T_ = -1; }
+
+  // -- predicates ----------------------------------------------------------------------------------------------------------
+  int32_t T() const { return T_; }
+  bool current(uint64_t topo) const { return T_ >= 0 && topo_ == topo; }
+  bool matches(int32_t T, uint64_t topo) const { return T_ == T && topo_ == topo; }  // (the caller's T >= 0: mesh_outputs_begin(NULL))
+  bool keys_name_winners() const { return T_ >= 0 && keys_of_ != 0 && keys_of_ == uploads_; }
+  bool validity_current(uint64_t topo) const { return current(topo) && validity_of_ != 0 && validity_of_ == uploads_; }
+
+ private:
+  int32_t T_ = -1;         // triangles in r_tris (-1: none, or they index other arrays than the graph's)
+  uint64_t topo_ = ~0ull;  // the topology their indices were checked against
+  uint64_t uploads_ = 0;   // uploads into r_tris so far
+  uint64_t keys_of_ = 0, validity_of_ = 0;  // the upload r_keys / m_tvalid describe (0: none)
+};
+
+inline size_t up16(size_t bytes) { return (bytes + 15) & ~size_t(15); }
+
+// Byte offsets of a stage's outputs in its pinned buffer, and the bytes the buffer needs.
+struct MeshLayout {
+  size_t normals, idepth, counts, map, valid, total;  // 3V floats | V floats | {n_valid, coverage} | the filtered map | T bytes
+};
+inline MeshLayout mesh_layout(int32_t V, int32_t T, int rows, int cols, bool want_map) {
+  MeshLayout m;
+  m.normals = 0;
+  m.idepth = sizeof(float) * 3 * (size_t)V;
+  m.counts = m.idepth + sizeof(float) * (size_t)V;
+  m.map = m.counts + 4 * sizeof(int32_t);
+  m.valid = m.map + (want_map ? sizeof(float) * (size_t)rows * (size_t)cols : 0);
+  m.total = m.valid + (size_t)T + 16;
+  return m;
+}
+
+struct DebugLayout {
+  size_t idimg, nimg, w1, w2, gray, total;  // idepth image | normals image | w1 map | w2 map | a host grey image on its way up
+};
+inline DebugLayout debug_layout(int rows, int cols, bool want_idepth, bool want_normals, bool host_gray) {
+  const size_t n = (size_t)rows * (size_t)cols;
+  DebugLayout d;
+  d.idimg = 0;
+  d.nimg = up16(want_idepth ? 3 * n : 0);
+  d.w1 = d.nimg + up16(want_normals ? 3 * n : 0);
+  d.w2 = d.w1 + up16(want_normals ? sizeof(float) * n : 0);
+  d.gray = d.w2 + up16(want_normals ? sizeof(float) * n : 0);
+  d.total = d.gray + up16(host_gray ? n : 0) + 16;
+  return d;
+}
+
+constexpr size_t kWireCountBytes = 16;  // the wireframe's counters (wireframe_kernels.h: kWireCounts ints)
+struct WireLayout {
+  size_t img, counts, gray, total;  // the picture | the counters | a host grey image on its way up
+};
+inline WireLayout wire_layout(int rows, int cols, bool host_gray) {
+  const size_t n = (size_t)rows * (size_t)cols;
+  WireLayout w;
+  w.img = 0;
+  w.counts = up16(3 * n);
+  w.gray = w.counts + kWireCountBytes;
+  w.total = w.gray + up16(host_gray ? n : 0) + 16;
+  return w;
+}
+
+// Every index of T triangles names one of V vertices.
+inline bool triangles_in_range(const int32_t* triangles, int32_t T, int32_t V) {
+  for (int64_t t = 0; t < 3 * (int64_t)T; ++t)
+    if (triangles[t] < 0 || triangles[t] >= V) return false;
+  return true;
+}
+
+}  // namespace host
+}  // namespace flame_hip
+
+#endif  // FLAME_AMD_SIDE_STAGE_HPP_

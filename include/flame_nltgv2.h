@@ -265,7 +265,8 @@ int flame_nltgv2_interpolate_mesh(flame_nltgv2_ctx* ctx, const int32_t* triangle
 /* interpolate_mesh in two halves, so that the solver iterates while the map is rasterised and copied out: begin settles the runs,
  * brings the state to its canonical arrays and enqueues rasteriser + device-to-host copy on a side stream, returning at once (the
  * caller goes on with run_async); end waits for that stream.  *map_out points at the context's pinned rows*cols floats (valid
- * until the next begin); the map also stays on the device for flame_nltgv2_sync_input.init_from_map. */
+ * until the next begin); the map also stays on the device for flame_nltgv2_sync_input.init_from_map.  A begin that runs out of
+ * pinned memory (FLAME_NLTGV2_ERR_OOM) leaves the map of an earlier begin, and its pending end, as they are. */
 int flame_nltgv2_interpolate_mesh_begin(flame_nltgv2_ctx* ctx, const int32_t* triangles, int32_t T, const uint8_t* tri_valid,
                                         int rows, int cols, float graph_scale);
 int flame_nltgv2_interpolate_mesh_end(flame_nltgv2_ctx* ctx, const float** map_out, int32_t* coverage_out);

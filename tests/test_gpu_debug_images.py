@@ -235,3 +235,25 @@ def test_gpu_every_error_is_reported_before_anything_is_enqueued(gpu, scene):
             assert np.array_equal(kept[k], first[k], equal_nan=True), k
     with gpu.Regularizer(0) as fresh:
         assert lib.flame_nltgv2_debug_images_end(fresh._ctx, C.byref(gpu.regularizer._DebugImagesView())) == -1  # nothing begun
+
+
+@pytest.mark.gpu
+def test_gpu_key_image_is_not_read_after_mesh_outputs_hands_in_a_new_triangle_list(gpu, scene):
+    """interpolate_mesh_begin(tris) leaves a key image that names winners of `tris`; mesh_outputs(tris reversed) replaces the resident
+    triangles and rasterises nothing.  The key image's indices now name other triangles, so the stage has to rasterise w1 / w2 itself,
+    over the reversed list."""
+    s = scene
+    rev = np.ascontiguousarray(s["tris"][::-1])
+    Kinv = np.linalg.inv(s["K"].astype(np.float64)).astype(F)
+    w1m = oracle.raster_interpolate_mesh(rev, s["pos"], s["g"]["w1"], ROWS, COLS)
+    w2m = oracle.raster_interpolate_mesh(rev, s["pos"], s["g"]["w2"], ROWS, COLS)
+    with gpu.Regularizer(0) as reg:
+        reg.upload_graph(s["g"])
+        reg.interpolate_mesh_begin(s["tris"], ROWS, COLS, graph_scale=GRAPH_SCALE)
+        reg.mesh_outputs(rev, Kinv, ROWS, COLS, graph_scale=GRAPH_SCALE)
+        got = reg.debug_images(s["img"], s["K"], ROWS, COLS, gpu.DebugImageParams(scene_color_scale=COLOR_SCALE))
+        assert np.array_equal(bits(got["w1_map"]), bits(w1m)), "w1_map"
+        assert np.array_equal(bits(got["w2_map"]), bits(w2m)), "w2_map"
+        dense, _ = reg.interpolate_mesh_end()
+        assert np.array_equal(bits(dense), bits(s["dense"]))  # (the map itself is the first list's)
+        assert_image(got["normals_img"], dr.draw_normals(s["img"], s["K"], s["dense"], w1m, w2m), "normals over the reversed list's maps")

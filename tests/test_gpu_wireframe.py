@@ -233,3 +233,69 @@ def test_gpu_every_error_is_reported_before_anything_is_enqueued(gpu, scene):
         assert np.array_equal(kept["wireframe_img"], first["wireframe_img"])
     with gpu.Regularizer(0) as fresh:
         assert lib.flame_nltgv2_debug_wireframe_end(fresh._ctx, C.byref(gpu.regularizer._WireframeView())) == -1  # nothing begun
+
+
+@pytest.mark.gpu
+def test_gpu_pending_outputs_survive_the_other_stages_regrowing_their_pinned_buffers(gpu, scene):
+    """Every stage's pinned buffer grows with half as much again; twice the rows and twice the columns is four times the bytes of every
+    region but the per-vertex and per-triangle ones (a few hundred bytes here), so a call at 100 x 140 after one at 50 x 70 replaces
+    the buffer of every stage it goes through.  A replaced buffer must be that stage's alone: what another stage's begin left
+    pending comes out of its _end as it went in.  (A begin of the SAME stage does supersede its own pending _end.)"""
+    from oracle import capi as oracle
+    from tests import debug_ref as dr
+
+    s = scene
+    R2, C2 = 2 * ROWS, 2 * COLS
+    img = np.ascontiguousarray(s["img"])
+    big = tw.grey(R2, C2, 45)
+    K = s["K"]
+    Kinv = np.linalg.inv(K.astype(np.float64)).astype(F)
+    wp, dp = gpu.WireframeParams(scene_color_scale=COLOR_SCALE), gpu.DebugImageParams(scene_color_scale=COLOR_SCALE)
+    idepth = mr.vertex_idepths(s["g"]["x"], GRAPH_SCALE)
+    small = dict(wireframe_img=tw.scene_wireframe(s)[0], idepthmap_img=dr.draw_inverse_depth_map(img, s["dense"], COLOR_SCALE),
+                 normals_img=dr.draw_normals(img, K, s["dense"], s["w1m"], s["w2m"]), w1_map=s["w1m"], w2_map=s["w2m"])
+    dense2, w1m2, w2m2 = (oracle.raster_interpolate_mesh(s["tris"], s["pos"], v, R2, C2) for v in (idepth, s["g"]["w1"], s["g"]["w2"]))
+    large = dict(wireframe_img=wr.draw_wireframe(big, s["tris"], s["pos"], idepth, None, COLOR_SCALE)[0],
+                 idepthmap_img=dr.draw_inverse_depth_map(big, dense2, COLOR_SCALE), normals_img=dr.draw_normals(big, K, dense2, w1m2, w2m2),
+                 w1_map=w1m2, w2_map=w2m2)
+
+    def same(got, ref, what):
+        assert got.keys() & ref.keys(), what
+        for k in got.keys() & ref.keys():
+            assert got[k].dtype == ref[k].dtype and np.array_equal(got[k], ref[k], equal_nan=True), (what, k)
+
+    # the larger calls right behind two pending small ones: every stage they use replaces its buffer, and their results are right
+    with gpu.Regularizer(0) as reg:
+        reg.upload_graph(s["g"])
+        reg.interpolate_mesh(s["tris"], ROWS, COLS, graph_scale=GRAPH_SCALE)
+        reg.debug_wireframe_begin(img, ROWS, COLS, GRAPH_SCALE, wp)
+        reg.debug_images_begin(img, K, ROWS, COLS, dp)
+        dense, _ = reg.interpolate_mesh(s["tris"], R2, C2, graph_scale=GRAPH_SCALE)
+        mesh = reg.mesh_outputs(None, Kinv, R2, C2, graph_scale=GRAPH_SCALE, want_filtered_map=True)
+        dbg = reg.debug_images(big, K, R2, C2, dp)
+        wire = reg.debug_wireframe(big, R2, C2, GRAPH_SCALE, wp)
+        assert np.array_equal(dense, dense2, equal_nan=True) and mesh["filtered_map"].shape == (R2, C2)
+        same(dbg, large, "debug images at 100 x 140")
+        same(wire, large, "wireframe at 100 x 140")
+    # two pending small begins, then the OTHER stages replace their buffers: the two small _ends return the first pictures
+    with gpu.Regularizer(0) as reg:
+        reg.upload_graph(s["g"])
+        reg.interpolate_mesh_begin(s["tris"], ROWS, COLS, graph_scale=GRAPH_SCALE)  # (small buffers for the map and the mesh outputs first)
+        reg.interpolate_mesh_end()
+        reg.mesh_outputs(None, Kinv, ROWS, COLS, graph_scale=GRAPH_SCALE, want_filtered_map=True)
+        reg.debug_wireframe_begin(img, ROWS, COLS, GRAPH_SCALE, wp)
+        reg.debug_images_begin(img, K, ROWS, COLS, dp)
+        reg.interpolate_mesh_begin(s["tris"], R2, C2, graph_scale=GRAPH_SCALE)
+        mesh = reg.mesh_outputs(None, Kinv, R2, C2, graph_scale=GRAPH_SCALE, want_filtered_map=True)
+        dense, _ = reg.interpolate_mesh_end()
+        assert np.array_equal(dense, dense2, equal_nan=True) and mesh["filtered_map"].shape == (R2, C2)
+        same(reg.debug_wireframe_end(), small, "pending wireframe, map and mesh outputs regrown")
+        same(reg.debug_images_end(), small, "pending debug images, map and mesh outputs regrown")
+        # ... and the two debug stages against each other (the resident map is the large one now)
+        reg.debug_wireframe_begin(img, ROWS, COLS, GRAPH_SCALE, wp)
+        same(reg.debug_images(big, K, R2, C2, dp), large, "debug images at 100 x 140 inside a pending wireframe")
+        same(reg.debug_wireframe_end(), small, "pending wireframe, debug images regrown")
+        reg.interpolate_mesh(s["tris"], ROWS, COLS, graph_scale=GRAPH_SCALE)
+        reg.debug_images_begin(img, K, ROWS, COLS, dp)
+        same(reg.debug_wireframe(big, R2, C2, GRAPH_SCALE, wp), large, "wireframe at 100 x 140 inside pending debug images")
+        same(reg.debug_images_end(), small, "pending debug images, wireframe regrown")

@@ -1,7 +1,8 @@
 """The library's HOST code under AddressSanitizer + UndefinedBehaviorSanitizer (`make -C flame_amd/csrc sanitize`): the
 Delaunay triangulator (flame_amd/csrc/delaunay.cpp), the layout builders and the CPU replay of the patch rows
-(flame_amd/csrc/nltgv2_pack.hpp via tests/cpp/wg_layout_test.cc and tests/cpp/host_sanitize_test.cc) and the facade's packing
-(include/flame_hip/*.hpp).  No device needed; any out-of-bounds access, use after free, signed overflow or invalid shift
+(flame_amd/csrc/nltgv2_pack.hpp via tests/cpp/wg_layout_test.cc and tests/cpp/host_sanitize_test.cc), the pure parts of the run
+planner and of the side-stream stages (nltgv2_plan.hpp, side_stage.hpp via tests/cpp/run_plan_test.cc, tests/cpp/side_stage_test.cc)
+and the facade's packing (include/flame_hip/*.hpp).  No device needed; any out-of-bounds access, use after free, signed overflow or invalid shift
 aborts the programs (-fno-sanitize-recover=all)."""
 import os
 import subprocess
