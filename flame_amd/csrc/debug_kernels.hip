@@ -8,9 +8,9 @@
 // float, double where a double literal or variable pulls the expression up), built with -ffp-contract=off like the rest of the
 // library; division and square root are the correctly rounded ones, in both precisions.  tests/debug_ref.py restates the same.
 //
-// drawWireframe is wireframe_kernels.hip; the colour map and the pixel stores the two files share are debug_pixel.hpp.
-// Not here (include/flame_nltgv2.h says why): cv::putText (debug_draw_text_overlay is taken as false),
-// drawDetections / debug_draw_matches / debug_draw_photo_error.
+// drawWireframe is wireframe_kernels.hip, the matches picture matches_kernels.hip, drawDetections detections_kernels.hip; the
+// colour map and the pixel stores these files share are debug_pixel.hpp.
+// Not here (include/flame_nltgv2.h says why): cv::putText (debug_draw_text_overlay is taken as false), debug_draw_photo_error.
 //
 // Streaming kernels: a thread owns four consecutive OUTPUT pixels, 12 bytes, and stores them as three dwords.
 #include <hip/hip_runtime.h>

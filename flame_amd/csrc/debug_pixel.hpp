@@ -15,12 +15,11 @@ inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block 
 __device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)(int)v; }
 __device__ __forceinline__ uint8_t to_u8(double v) { return (uint8_t)(int)v; }
 
-// utils::jet(v, 0, 2), visualization.h:142-167.  c starts white; the first branch is float arithmetic, the other three go
+// utils::jet(v, vmin, vmax), visualization.h:142-167.  c starts white; the first branch is float arithmetic, the other three go
 // through double (their 0.25 * dv, 0.5 * dv, 0.75 * dv literals); `4 * a / dv` is (4 * a) / dv.
 // A NaN v fails every comparison and ends in the last branch with a NaN cast to uint8_t, which C++ leaves undefined: the
 // library's colour for it is (0, 0, 255), what x86 produces (UNPINNED).
-__device__ __forceinline__ void jet02(float v, uint8_t c[3]) {
-  const float vmin = 0.0f, vmax = 2.0f;
+__device__ __forceinline__ void jet(float v, const float vmin, const float vmax, uint8_t c[3]) {
   c[0] = 255, c[1] = 255, c[2] = 255;
   if (v < vmin) v = vmin;
   if (v > vmax) v = vmax;
@@ -40,6 +39,9 @@ __device__ __forceinline__ void jet02(float v, uint8_t c[3]) {
     c[0] = 0;
   }
 }
+
+// jet(v, 0, 2): the map of the inverse-depth colours (drawInverseDepthMap, drawFeatures, drawWireframe, the matches)
+__device__ __forceinline__ void jet02(float v, uint8_t c[3]) { jet(v, 0.0f, 2.0f, c); }
 
 // four pixels, each packed as c[0] | c[1] << 8 | c[2] << 16 -> memory: three dwords where all four exist, bytes at the image's tail
 __device__ __forceinline__ uint32_t pack3(const uint8_t c[3]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16); }

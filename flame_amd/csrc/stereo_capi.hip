@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <unordered_map>
@@ -16,6 +17,7 @@
 #include "stereo_kernels.h"
 #include "feature_kernels.h"
 #include "debug_kernels.h"
+#include "detections_kernels.h"
 #include "matches_kernels.h"
 #include "roctx_ranges.hpp"
 
@@ -95,7 +97,8 @@ struct flame_stereo_ctx {
   int* h_sel = nullptr;  // pinned, the same
   size_t h_sel_cap = 0;
   int graph_copy = 0;  // FLAME_STEREO_OPT_GRAPH_COPY
-  // draw_features (debug_kernels.hip): per-pixel owner words + the two counters behind them, and the image
+  // draw_features (debug_kernels.hip): per-pixel owner words + the two counters behind them, and the image;
+  // draw_detections (detections_kernels.hip) keeps its kDetWords stats words in d_owner and paints into d_draw too
   uint32_t* d_owner = nullptr;
   size_t owner_cap = 0;
   uint8_t* d_draw = nullptr;
@@ -885,6 +888,59 @@ int flame_stereo_draw_matches(flame_stereo_ctx* ctx, int flip, uint8_t* img_out,
     stats->rings_skipped = counts[kMatchRingsSkippedCount];
     stats->entries = (int64_t)total;
     stats->refilled = refilled;
+  }
+  return 0;
+}
+
+int flame_stereo_draw_detections(flame_stereo_ctx* ctx, const flame_stereo_params* params,
+                                 const flame_stereo_detect_params* dparams, uint32_t ref_frame_id,
+                                 const float q_ref_to_prev[4], const float t_ref_to_prev[3], float max_score, int flip,
+                                 uint8_t* img_out, flame_stereo_detections_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_draw_detections");
+  if (int rc = enter(ctx)) return rc;
+  if (stats) stats->num_scored = 0, stats->num_examined = 0, stats->error_pixel = -1;
+  if (!params || !dparams || !q_ref_to_prev || !t_ref_to_prev || !img_out || !std::isfinite(max_score) || !(max_score > 0.0f))
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  auto fr = ctx->frames.find(ref_frame_id);
+  if (fr == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int width = ctx->cam.width, height = ctx->cam.height, pitch = width + 2 * ctx->cam.border;
+  const int border = front_border(*params);
+  if (border < 0) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const int row_offset = params->do_letterbox ? height / 3 : 0;
+  DetectGrid G;  // the scan rectangle and the threshold of flame_stereo_detect_features; the cell grid is not read
+  G.win = 1, G.hc = G.wc = 0;
+  G.r_lo = border + row_offset, G.r_hi = height - border - row_offset;
+  G.c_lo = border, G.c_hi = width - border;
+  G.g2 = dparams->min_grad_mag * dparams->min_grad_mag;
+  const size_t px = (size_t)width * height;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers may be reallocated)
+  if (int rc = grow(ctx, &ctx->d_owner, &ctx->owner_cap, (size_t)kDetWords)) return rc;  // (scratch of the pictures: the stats words)
+  if (int rc = grow(ctx, &ctx->d_draw, &ctx->draw_cap, 3 * px + 16)) return rc;
+  DebugImageArgs a;
+  a.rows = height, a.cols = width;
+  a.gray = fr->second.img_pad + (size_t)ctx->cam.border * pitch + ctx->cam.border, a.gray_step = pitch;
+  a.scene_color_scale = 1.0f, a.flip = flip != 0;
+  a.k00 = a.k11 = 0.0f;
+  Geo geo;
+  load_geometry(geo, ctx->cam, q_ref_to_prev, t_ref_to_prev);
+  int* d_stats = (int*)ctx->d_owner;
+  int s[kDetWords] = {0};
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, (hipError_t)launch_draw_detections(a, G, geo, ctx->cam, fr->second.gx_pad, fr->second.gy_pad, max_score, d_stats,
+                                               ctx->d_draw, ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(img_out, ctx->d_draw, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipMemcpyAsync(s, d_stats, sizeof s, hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) {
+    for (int k = 0; k < kDetSlots; ++k) stats->num_scored += s[kDetCount + k * kDetSlotStride];
+    stats->num_examined = std::max(G.r_hi - G.r_lo, 0) * std::max(G.c_hi - G.c_lo, 0);
+  }
+  if (s[kDetAssert] != 0) {
+    if (stats) stats->error_pixel = INT_MAX - s[kDetAssert];
+    return FLAME_NLTGV2_ERR_ASSERT;
   }
   return 0;
 }

@@ -67,6 +67,10 @@ class _FeatureStats(C.Structure):
     _fields_ = [("num_features", C.c_int32), ("num_examined", C.c_int32), ("error_feature", C.c_int32)]
 
 
+class _DetectionsStats(C.Structure):
+    _fields_ = [("num_scored", C.c_int32), ("num_examined", C.c_int32), ("error_pixel", C.c_int32)]
+
+
 class _PruneStats(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_examined", "num_moved", "num_invalidated", "num_removed", "num_features",
                                           "num_frames_dropped", "error_feature")]
@@ -126,6 +130,7 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_prune_features", "flame_stereo_clear_features", "flame_stereo_default_graph_params",
     "flame_stereo_select_graph_features", "flame_stereo_select_graph_features_arrays",
     "flame_stereo_draw_features", "flame_stereo_frame_image_device", "flame_stereo_draw_matches",
+    "flame_stereo_draw_detections",
 )
 OPT_LANES_PER_FEATURE = 1
 OPT_GRAPH_COPY = 2
@@ -187,6 +192,8 @@ def _lib():
                                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
             "flame_stereo_frame_image_device": (C.c_int, [ctx, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
             "flame_stereo_draw_matches": (C.c_int, [ctx, C.c_int, C.c_void_p, C.POINTER(_MatchesStats)]),
+            "flame_stereo_draw_detections": (C.c_int, [ctx, PP, C.POINTER(DetectParams), C.c_uint32, _FP, _FP, C.c_float,
+                                                       C.c_int, C.c_void_p, C.POINTER(_DetectionsStats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -382,6 +389,26 @@ class FeatureTracker:
             return rc, res
         self._chk(rc, "draw_matches")
         return res
+
+    def draw_detections(self, params: StereoParams, dparams: DetectParams, ref_frame_id: int, q_ref_to_prev, t_ref_to_prev,
+                        max_score: float = 0.005, flip: bool = False, raise_on_error: bool = True):
+        """getDebugImageDetections (flame.cc:1212-1251, 1272-1275, drawDetections :2363-2412): the epipolar-gradient score of
+        the detect_features call with the same arguments, coloured with jet(score, 0, max_score) and blended over the image of
+        resident frame `ref_frame_id` (0.005 is the reference's literal max_score).  Changes nothing but scratch.  Returns
+        (img (height, width, 3) u8, stats dict: num_scored, num_examined, error_pixel), or (status, img, stats dict) when
+        raise_on_error is False (img is unspecified unless status is 0)."""
+        q, t = _f32(q_ref_to_prev, 4), _f32(t_ref_to_prev, 3)
+        img = np.empty((self.height, self.width, 3), np.uint8)
+        st = _DetectionsStats()
+        rc = self._L.flame_stereo_draw_detections(self._ctx, C.byref(params), C.byref(dparams), ref_frame_id,
+                                                  q.ctypes.data_as(_FP), t.ctypes.data_as(_FP), C.c_float(max_score),
+                                                  int(bool(flip)), img.ctypes.data, C.byref(st))
+        stats = {n: int(getattr(st, n)) for n, _ in _DetectionsStats._fields_}
+        if not raise_on_error:
+            return rc, img, stats
+        if rc != 0:
+            raise NLTGV2Error(rc, "draw_detections: %s (pixel %d)" % (status_string(rc), stats["error_pixel"]))
+        return img, stats
 
     def frame_image_device(self, frame_id: int):
         """(device address, step_bytes) of the unpadded image of a resident frame: Regularizer.debug_images(None, ...,

@@ -28,6 +28,9 @@
 //   here       tracker.recordMatches(params.debug_draw_matches);                 // once, e.g. beside the constructor
 //              tracker.updateFeatureIDepths(...);                                // any form
 //              tracker.getDebugImageMatches(params, debug_img_matches_.data);    // height * width * 3 bytes
+//   reference  getDebugImageDetections() (flame.h:294-306): the picture detectFeatures draws into its debug_img argument when
+//              params.debug_draw_detections is set (flame.cc:1272-1275, drawDetections flame.cc:2363-2412)
+//   here       tracker.getDebugImageDetections(params, fref, fprev, debug_img_detections_.data);   // beside detectFeatures
 //   reference  Flame::getRawIDepths(&vertices, &idepths_mu, &idepths_var)  (flame.h:255-273)
 //   here       tracker.getRawIDepths(&vertices, &idepths_mu, &idepths_var);
 //
@@ -53,6 +56,7 @@
 namespace flame_hip {
 
 typedef flame_stereo_matches_stats MatchesStats;  // what getDebugImageMatches drew, by kind (flame_stereo.h)
+typedef flame_stereo_detections_stats DetectionsStats;  // what getDebugImageDetections scored (flame_stereo.h)
 
 struct StereoError : std::runtime_error {
   int status;
@@ -305,6 +309,33 @@ class FeatureTracker {
   bool getDebugImageMatches(const FlameParams& params, uint8_t* debug_img, MatchesStats* stats = nullptr) {
     if (!params.debug_draw_matches) return false;
     getDebugImageMatches(debug_img, params.debug_flip_images ? true : false, stats);
+    return true;
+  }
+  // ---- getDebugImageDetections ----
+  // == the picture Flame::detectFeatures draws into its debug_img argument with params.debug_draw_detections (flame.cc:1272-1275,
+  // drawDetections flame.cc:2363-2412): the epipolar-gradient score of the detectFeatures call with the same params, fref and
+  // fprev, over the resident frame fref.id.  A pure function of the frame's resident gradients: nothing is recorded at
+  // detection time, and nothing but scratch changes.  debug_img: height * width * 3 bytes (cv::Vec3b, c[0], c[1], c[2]).
+  // max_score: the reference passes the literal 0.005f (then every scored pixel has the colour of the maximum); a larger value
+  // shows the gradient strengths.  The text overlay and the (commented out) keypoints are not drawn.
+  template <class FlameParams, class Frame>
+  void drawDetections(const FlameParams& params, const Frame& fref, const Frame& fprev, bool debug_flip_images, uint8_t* debug_img,
+                      float max_score = 0.005f, DetectionsStats* stats = nullptr) {
+    float q[4], t[3];
+    toQuatTrans(fprev.pose.inverse() * fref.pose, q, t);  // T_ref_to_prev (flame.cc:1207)
+    const flame_stereo_params sp = toStereoParams(params);
+    const flame_stereo_detect_params dp = toDetectParams(params);
+    DetectionsStats local;
+    DetectionsStats* st = stats ? stats : &local;
+    const int rc = flame_stereo_draw_detections(ctx_, &sp, &dp, fref.id, q, t, max_score, debug_flip_images ? 1 : 0, debug_img, st);
+    check(rc, st->error_pixel, "flame_stereo_draw_detections");
+  }
+  // With the reference's parameters: nothing is drawn, and false returned, unless params.debug_draw_detections is set.
+  template <class FlameParams, class Frame>
+  bool getDebugImageDetections(const FlameParams& params, const Frame& fref, const Frame& fprev, uint8_t* debug_img,
+                               float max_score = 0.005f, DetectionsStats* stats = nullptr) {
+    if (!params.debug_draw_detections) return false;
+    drawDetections(params, fref, fprev, params.debug_flip_images ? true : false, debug_img, max_score, stats);
     return true;
   }
   // fnew_->img[0] of a resident frame in device memory (address, pitch): what DeviceGraph::debugImagesBegin takes as

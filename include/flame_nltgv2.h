@@ -360,8 +360,9 @@ int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
  * NOT covered, on purpose:
  *   cv::putText        debug_draw_text_overlay is treated as false.
  *   debug_draw_photo_error   feeds on commented-out code in the reference.
- *   drawDetections           is live code (its `score` is written at flame.cc:1249) and is OPEN: no counterpart yet.
- * (getDebugImageMatches, debug_draw_matches: live code too; flame_stereo_draw_matches, flame_stereo.h.)
+ * (getDebugImageMatches, debug_draw_matches: live code too; flame_stereo_draw_matches, flame_stereo.h.  getDebugImageDetections,
+ * drawDetections, whose `score` is written at flame.cc:1249: flame_stereo_draw_detections, flame_stereo.h.  With them every
+ * getDebugImage* getter of flame.h has a counterpart.)
  *
  * Pixel bytes are the reference's cv::Vec3b c[0], c[1], c[2] in that order; cvtColor(GRAY2RGB) is three equal bytes.
  *   idepth image   drawInverseDepthMap, flame.cc:2699-2719: a NaN of the map leaves the grey pixel, every other value v gives

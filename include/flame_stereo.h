@@ -458,6 +458,50 @@ typedef struct flame_stereo_matches_stats {
  * kernels. */
 int flame_stereo_draw_matches(flame_stereo_ctx* ctx, int flip, uint8_t* img_out, flame_stereo_matches_stats* stats);
 
+/* ---- getDebugImageDetections (flame.h:294-306) ----------------------------------------------------------------------
+ * The picture detectFeatures draws with params.debug_draw_detections (flame.cc:1272-1275): the epipolar-gradient score of
+ * every scanned pixel over the image of resident frame `ref_frame_id`.  It is a pure function of its pixel, recomputed from the
+ * frame's resident gradients: nothing is recorded at detection time, flame_stereo_detect_features launches what it always
+ * launched, and this call takes the arguments of the detect_features call it illustrates.  The rule, restated by
+ * tests/detections_ref.py (the checker; like the rest of the front-end not pinned to the reference binary):
+ *   1. Score (flame.cc:1212-1251).  `score` starts all NaN.  The scan covers rows ii in [border + row_offset,
+ *      height - border - row_offset) and columns jj in [border, width - border), border and row_offset as in
+ *      flame_stereo_detect_features: (int)(rescale_factor_max * win_size / 2 + 1) in float, and height / 3 with do_letterbox,
+ *      else 0.  Per pixel, with g2 = min_grad_mag * min_grad_mag in float: skipped if gx * gx + gy * gy < g2;
+ *      epi = referenceEpiline(cv::Point2f(ii, jj)) -- (row, col) passed as (x, y), kept as written --;
+ *      epigrad = gx * epi.x + gy * epi.y; skipped if epigrad * epigrad < g2; else score(ii, jj) = |epigrad|.
+ *      The score does not depend on detection_win_size, the cell mask or the inverse-depth map: of `dparams` only
+ *      min_grad_mag is read, of `params` rescale_factor_max, win_size and do_letterbox.
+ *   2. Colour (drawDetections, flame.cc:2363-2412).  The picture starts (0, 0, 0); a pixel with a non-NaN score v becomes
+ *      utils::jet(v, 0, max_score) (utils/visualization.h:142-167: the first branch in float, the other three through double,
+ *      truncated to a byte; bytes c[0], c[1], c[2] in memory); a NaN score (never scanned, skipped, or a NaN epigrad, which
+ *      fails `epigrad * epigrad < g2` and stays NaN through fast_abs) keeps (0, 0, 0).  The reference passes the literal
+ *      max_score = 0.005f: with the default min_grad_mag = 5 every scored pixel then clamps to vmax and the picture is
+ *      two-valued, so max_score is a parameter here (0.005f reproduces the reference).
+ *   3. Blend (flame.cc:2388) with cvtColor(img, GRAY2RGB), three equal bytes g: per channel
+ *      t = (float)c * (float)0.7 + (float)g * (float)0.3 in float -- two rounded products, one rounded sum, no FMA --, then
+ *      saturate_cast<uchar>(t): round to nearest, ties to even, clamped to [0, 255].  An unscored pixel is rne(g * 0.3f).
+ *      UNPINNED: this reads the MatExpr `0.7 * A + 0.3 * B` on 8-bit data as cv::addWeighted(A, 0.7, B, 0.3, 0); OpenCV is
+ *      not part of this tree, so the rounding is restated here and in the checker, not checked against it.
+ *   4. flip != 0 reverses the linear pixel order of the finished picture (cv::flip(img, img, -1)).  debug_draw_text_overlay
+ *      (cv::putText) is treated as false; cv::drawKeypoints is commented out in the reference.
+ * A pixel that passes the first gradient test where the reference's referenceEpiline asserts (zero translation) is treated as
+ * unscored on the device and reported: FLAME_NLTGV2_ERR_ASSERT, stats->error_pixel set, img_out unspecified. */
+typedef struct flame_stereo_detections_stats {
+  int32_t num_scored;    /* pixels with a non-NaN score */
+  int32_t num_examined;  /* pixels of the scan rectangle */
+  int32_t error_pixel;   /* -1, or the lowest row * width + col whose referenceEpiline asserted */
+} flame_stereo_detections_stats;
+/* FLAME_NLTGV2_ERR_INVALID_ARG, before anything is enqueued or written, for a NULL params, dparams, q, t or img_out, a
+ * max_score that is not finite or <= 0, a frame that is not resident, or a negative border; FLAME_NLTGV2_ERR_NO_GRAPH when no
+ * camera is set.  Changes nothing in the context but its scratch buffers: the resident set, the projected set, the frames and
+ * the match records stay as they are.  img_out: height * width * 3 bytes of host memory; `stats` may be NULL.  Enqueues on the
+ * context's stream and waits once; flame_stereo_last_kernel_ms covers its kernel. */
+int flame_stereo_draw_detections(flame_stereo_ctx* ctx, const flame_stereo_params* params,
+                                 const flame_stereo_detect_params* dparams, uint32_t ref_frame_id,
+                                 const float q_ref_to_prev[4], const float t_ref_to_prev[3], float max_score, int flip,
+                                 uint8_t* img_out, flame_stereo_detections_stats* stats);
+
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
  * bit for bit.  GRAPH_COPY: how select_graph_features brings its arrays down: 0 (default) the whole output block in one
@@ -468,7 +512,7 @@ enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1, FLAME_STEREO_OPT_GRAPH_COPY = 2, 
 int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value);
 
 /* Device time of the last update kernel (or of the kernels of the last project_features / detect_features /
- * prune_pose_frames / prune_features / select_graph_features[_arrays] / draw_matches) in
+ * prune_pose_frames / prune_features / select_graph_features[_arrays] / draw_matches / draw_detections) in
  * milliseconds (HIP events on the context's stream); < 0 if none. */
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx);
 int flame_stereo_last_hip_error(const flame_stereo_ctx* ctx);
