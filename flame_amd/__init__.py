@@ -10,6 +10,7 @@ There is no CPU fallback in this package: without the HIP library / a GPU every 
 from .regularizer import (  # noqa: F401
     DebugImageParams,
     MeshFilterParams,
+    MetricParams,
     NLTGV2Error,
     Params,
     Regularizer,

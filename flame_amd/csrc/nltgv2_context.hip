@@ -535,7 +535,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   ok = ok && hipEventCreateWithFlags(&ctx->ev_snap, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_raster_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_topo_ready, hipEventDisableTiming) == hipSuccess;
-  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire})
+  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire, &ctx->metric})
     ok = ok && hipEventCreate(&st->ev0) == hipSuccess && hipEventCreate(&st->ev1) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_expanded, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_run[0], hipEventDisableTiming) == hipSuccess;
@@ -587,6 +587,9 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   for (DevBuf* b : {&ctx->d_gray, &ctx->d_idimg, &ctx->d_nimg, &ctx->d_w1map, &ctx->d_w2map, &ctx->d_keys, &ctx->d_cov}) ctx->all.push_back(b);
   for (DevBuf* b : {&ctx->w_draws, &ctx->w_cnt, &ctx->w_off, &ctx->w_fill, &ctx->w_entries, &ctx->w_counts, &ctx->w_img, &ctx->w_gray, &ctx->w_tvalid})
     ctx->all.push_back(b);
+  for (DevBuf* b : {&ctx->x_depth, &ctx->x_mm, &ctx->x_org, &ctx->x_cloud, &ctx->x_pix, &ctx->x_blocks, &ctx->x_counts, &ctx->x_verts, &ctx->x_norms,
+                    &ctx->x_tris, &ctx->x_tblocks})
+    ctx->all.push_back(b);
   ctx->all.push_back(&ctx->stop_dev);
   ctx->all.push_back(&ctx->place_patch_nx), ctx->all.push_back(&ctx->place_fill_nx);
   for (auto& b : ctx->sp_v) ctx->all.push_back(&b);
@@ -622,7 +625,7 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
   for (hipEvent_t e : ctx->ev_run)
     if (e) (void)hipEventDestroy(e);
   if (ctx->h_img.p) (void)hipHostFree(ctx->h_img.p);
-  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire}) {
+  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire, &ctx->metric}) {
     if (st->h.p) (void)hipHostFree(st->h.p);
     if (st->ev0) (void)hipEventDestroy(st->ev0);
     if (st->ev1) (void)hipEventDestroy(st->ev1);

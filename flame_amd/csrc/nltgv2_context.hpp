@@ -347,6 +347,18 @@ struct flame_nltgv2_ctx {
     const uint8_t* gray = nullptr;    // device memory: what fill + fold read if _end has to repeat them
     WireLayout at{};
   } wire_pending;
+  // flame_nltgv2_metric_outputs_begin / _end (metric_kernels.hip): device outputs, pinned outputs and timing events of its own; the
+  // resident map, the filtered map and the mesh stage's P / normals / validity are only read.  Pinned: metric_layout
+  DevBuf x_depth, x_mm, x_org, x_cloud, x_pix, x_blocks, x_counts, x_verts, x_norms, x_tris, x_tblocks;
+  int fmap_rows = 0, fmap_cols = 0;   // the filtered map resident in m_img (0: none)
+  SideStage metric;
+  struct MetricPending {
+    int rows = 0, cols = 0;
+    int32_t V = 0, T = 0;
+    MetricWants want{};
+    bool cloud_fetched = false;       // _end has brought the n_points points to the host
+    MetricLayout at{};
+  } metric_pending;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

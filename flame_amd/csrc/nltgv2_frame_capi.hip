@@ -3,8 +3,9 @@
 //   the mesh outputs          mesh_outputs_begin / _end: triangle filters, vertex normals and idepths, the filtered map
 //   the debug images          debug_images_begin / _end: idepth colours, normals, the w1 / w2 maps
 //   the wireframe             debug_wireframe_begin / _end
+//   the metric outputs        metric_outputs_begin / _end: depth image, millimetre image, point clouds, 3-D mesh
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
-// The four begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// The five begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
 // they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
 // the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
@@ -14,6 +15,7 @@
 #include <cstdlib>
 #include "debug_kernels.h"
 #include "mesh_kernels.h"
+#include "metric_kernels.h"
 #include "nltgv2_context.hpp"
 #include "wireframe_kernels.h"
 
@@ -305,6 +307,7 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
   if (!rc) rc = ensure(ctx, ctx->m_incident, sizeof(int32_t) * 3 * (size_t)T);
   if (!rc && triangles) rc = ensure(ctx, ctx->r_tris, sizeof(int32_t) * 3 * (size_t)T);
   if (!rc && want_filtered_map) {
+    ctx->fmap_rows = ctx->fmap_cols = 0;  // (m_img is about to be rewritten: flame_nltgv2_metric_outputs_begin, use_filtered_map)
     rc = ensure(ctx, ctx->m_keys, sizeof(unsigned long long) * n);
     if (!rc) rc = ensure(ctx, ctx->m_img, sizeof(float) * n);
     if (!rc) rc = ensure(ctx, ctx->m_cov, sizeof(int));
@@ -336,9 +339,11 @@ int flame_nltgv2_mesh_outputs_begin(flame_nltgv2_ctx* ctx, const int32_t* triang
   HIPCHK(ctx, hipEventRecord(ctx->mesh.ev0, rs));
   LAUNCHCHK(ctx, flame_hip::launch_mesh_outputs(V, T, ctx->c.pos, ctx->c.x, graph_scale, (const int32_t*)ctx->r_tris.p, mf, mb, rs));
   // the filtered map: the rasteriser of interpolate_mesh over the idepths and the validity this stage has just left on the device
-  if (want_filtered_map)
+  if (want_filtered_map) {
     LAUNCHCHK(ctx, launch_interpolate_mesh(T, (const int32_t*)ctx->r_tris.p, ctx->c.pos, mb.vtx_idepth, 1.0f, nullptr, mb.tri_valid,
                                            (unsigned long long*)ctx->m_keys.p, (float*)ctx->m_img.p, (int*)ctx->m_cov.p, rows, cols, rs));
+    ctx->fmap_rows = rows, ctx->fmap_cols = cols;
+  }
   rc = side_kernels_read_last(ctx);  // (of the canonical pos / x)
   if (rc) return rc;
   char* h = ctx->mesh.h.p;
@@ -392,6 +397,180 @@ int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
   if (n_valid_out) *n_valid_out = v.n_valid;
   if (filtered_map_out) std::memcpy(filtered_map_out, v.filtered_map, sizeof(float) * (size_t)v.rows * (size_t)v.cols);
   if (filtered_coverage_out) *filtered_coverage_out = v.filtered_coverage;
+  return FLAME_NLTGV2_OK;
+}
+
+void flame_nltgv2_default_metric_params(flame_nltgv2_metric_params* p) {
+  if (!p) return;
+  p->min_depth = 0.0f, p->max_depth = HUGE_VALF;
+  p->use_filtered_map = 0;
+  p->want_depth = p->want_depth_mm = p->want_organized = p->want_cloud = 1;
+  p->want_mesh = 0;
+  p->copy_out = 1;
+  p->reserved = 0;
+  p->map_device = nullptr;
+}
+
+// The metric outputs on the side stream (see flame_nltgv2.h).  The stage reads what the other stages left on the device, in the
+// order of that stream, and nothing of the canonical arrays: no mesh_state_on, no side_kernels_read_last.
+int flame_nltgv2_metric_outputs_begin(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                      const flame_nltgv2_metric_params* params, int rows, int cols) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_metric_outputs_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  if (!Kinv || !params || rows <= 0 || cols <= 0 || (uint64_t)rows * (uint64_t)cols >= (1ull << 31)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  MetricWants w;
+  w.depth = params->want_depth != 0, w.depth_mm = params->want_depth_mm != 0, w.organized = params->want_organized != 0;
+  w.cloud = params->want_cloud != 0, w.mesh = params->want_mesh != 0, w.copy_out = params->copy_out != 0;
+  const bool want_pixels = w.depth || w.depth_mm || w.organized || w.cloud;
+  if (!want_pixels && !w.mesh) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const float* map = nullptr;
+  if (want_pixels) {
+    if (params->map_device) {
+      map = (const float*)params->map_device;
+    } else if (params->use_filtered_map) {
+      if (ctx->fmap_rows != rows || ctx->fmap_cols != cols || !ctx->m_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      map = (const float*)ctx->m_img.p;
+    } else {
+      if (ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      map = (const float*)ctx->r_img.p;
+    }
+  }
+  if (w.mesh && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t V = w.mesh ? ctx->L.V : 0, T = w.mesh ? ctx->tris.T() : 0;
+  const size_t n = (size_t)rows * (size_t)cols, f = sizeof(float);
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::MetricPending mp;
+  mp.rows = rows, mp.cols = cols, mp.V = V, mp.T = T, mp.want = w;
+  mp.at = metric_layout(rows, cols, V, T, w);
+  rc = open_stage(ctx, ctx->metric, mp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->x_counts, 2 * sizeof(int));
+  if (!rc && w.depth) rc = ensure(ctx, ctx->x_depth, f * n);
+  if (!rc && w.depth_mm) rc = ensure(ctx, ctx->x_mm, sizeof(uint16_t) * n + 16);
+  if (!rc && w.organized) rc = ensure(ctx, ctx->x_org, 3 * f * n);
+  if (!rc && w.cloud) {
+    rc = ensure(ctx, ctx->x_cloud, 3 * f * n);
+    if (!rc) rc = ensure(ctx, ctx->x_pix, sizeof(uint32_t) * n);
+    if (!rc) rc = ensure(ctx, ctx->x_blocks, sizeof(int) * (size_t)flame_hip::metric_blocks((long)n));
+  }
+  if (!rc && w.mesh) {
+    rc = ensure(ctx, ctx->x_verts, 3 * f * (size_t)V + 16);
+    if (!rc) rc = ensure(ctx, ctx->x_norms, 3 * f * (size_t)V + 16);
+    if (!rc) rc = ensure(ctx, ctx->x_tris, 3 * sizeof(int32_t) * (size_t)T + 16);
+    if (!rc) rc = ensure(ctx, ctx->x_tblocks, sizeof(int) * (size_t)flame_hip::metric_blocks(T) + 16);
+  }
+  if (rc) return rc;
+  ctx->metric.active = false;  // (from here on the pinned outputs are being rewritten)
+  flame_hip::MetricArgs a;
+  a.rows = rows, a.cols = cols;
+  std::memcpy(a.Kinv, Kinv, sizeof(a.Kinv));
+  a.has_pose = T_world_cam != nullptr;
+  if (T_world_cam) std::memcpy(a.pose, T_world_cam, sizeof(a.pose));
+  else std::memset(a.pose, 0, sizeof(a.pose));
+  a.min_depth = params->min_depth, a.max_depth = params->max_depth;
+  int* counts = (int*)ctx->x_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->metric.ev0, rs));
+  HIPCHK(ctx, hipMemsetAsync(counts, 0, 2 * sizeof(int), rs));
+  if (want_pixels) {
+    LAUNCHCHK(ctx, flame_hip::launch_metric_pixels(a, map, w.depth ? (float*)ctx->x_depth.p : nullptr, w.depth_mm ? (uint16_t*)ctx->x_mm.p : nullptr,
+                                                   w.organized ? (float*)ctx->x_org.p : nullptr, w.cloud ? (int*)ctx->x_blocks.p : nullptr, rs));
+    if (w.cloud)
+      LAUNCHCHK(ctx, flame_hip::launch_metric_cloud(a, map, (int*)ctx->x_blocks.p, counts, (float*)ctx->x_cloud.p, (uint32_t*)ctx->x_pix.p, rs));
+  }
+  if (w.mesh) {
+    LAUNCHCHK(ctx, flame_hip::launch_metric_vertices(a, V, (const float4*)ctx->m_P.p, (const float*)ctx->m_normals.p, (float*)ctx->x_verts.p,
+                                                     (float*)ctx->x_norms.p, rs));
+    LAUNCHCHK(ctx, flame_hip::launch_metric_triangles(T, (const int32_t*)ctx->r_tris.p, (const uint8_t*)ctx->m_tvalid.p, (int*)ctx->x_tblocks.p,
+                                                      counts + 1, (int32_t*)ctx->x_tris.p, rs));
+  }
+  char* h = ctx->metric.h.p;
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.at.counts, counts, 2 * sizeof(int), hipMemcpyDeviceToHost, rs));
+  if (w.copy_out) {  // (the dense cloud: in _end, n_points points of it)
+    if (w.depth) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.depth, ctx->x_depth.p, f * n, hipMemcpyDeviceToHost, rs));
+    if (w.depth_mm) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.depth_mm, ctx->x_mm.p, sizeof(uint16_t) * n, hipMemcpyDeviceToHost, rs));
+    if (w.organized) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.organized, ctx->x_org.p, 3 * f * n, hipMemcpyDeviceToHost, rs));
+    if (w.mesh && V > 0) {
+      HIPCHK(ctx, hipMemcpyAsync(h + mp.at.vertices, ctx->x_verts.p, 3 * f * (size_t)V, hipMemcpyDeviceToHost, rs));
+      HIPCHK(ctx, hipMemcpyAsync(h + mp.at.normals, ctx->x_norms.p, 3 * f * (size_t)V, hipMemcpyDeviceToHost, rs));
+    }
+    if (w.mesh && T > 0) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.triangles, ctx->x_tris.p, 3 * sizeof(int32_t) * (size_t)T, hipMemcpyDeviceToHost, rs));
+  }
+  ctx->metric_pending = mp;
+  return close_stage(ctx, ctx->metric);
+}
+
+int flame_nltgv2_metric_outputs_end(flame_nltgv2_ctx* ctx, flame_nltgv2_metric_outputs_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_metric_outputs_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  flame_nltgv2_ctx::MetricPending& mp = ctx->metric_pending;
+  if (!out || !ctx->metric.h.p || !ctx->metric.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  hipStream_t rs = ctx->raster_stream;
+  HIPCHK(ctx, hipStreamSynchronize(rs));
+  char* h = ctx->metric.h.p;
+  int32_t counts[2];
+  std::memcpy(counts, h + mp.at.counts, sizeof(counts));
+  const MetricWants& w = mp.want;
+  if (w.cloud && w.copy_out && !mp.cloud_fetched) {
+    if (counts[0] > 0) {
+      HIPCHK(ctx, hipMemcpyAsync(h + mp.at.cloud, ctx->x_cloud.p, 3 * sizeof(float) * (size_t)counts[0], hipMemcpyDeviceToHost, rs));
+      HIPCHK(ctx, hipMemcpyAsync(h + mp.at.cloud_pixel, ctx->x_pix.p, sizeof(uint32_t) * (size_t)counts[0], hipMemcpyDeviceToHost, rs));
+      HIPCHK(ctx, hipStreamSynchronize(rs));
+    }
+    mp.cloud_fetched = true;
+  }
+  const bool host = w.copy_out;
+  out->rows = mp.rows, out->cols = mp.cols, out->V = mp.V, out->T = mp.T;
+  out->n_points = counts[0], out->n_valid = counts[1];
+  out->depth = host && w.depth ? (const float*)(h + mp.at.depth) : nullptr;
+  out->depth_device = w.depth ? ctx->x_depth.p : nullptr;
+  out->depth_mm = host && w.depth_mm ? (const uint16_t*)(h + mp.at.depth_mm) : nullptr;
+  out->depth_mm_device = w.depth_mm ? ctx->x_mm.p : nullptr;
+  out->organized = host && w.organized ? (const float*)(h + mp.at.organized) : nullptr;
+  out->organized_device = w.organized ? ctx->x_org.p : nullptr;
+  out->cloud = host && w.cloud ? (const float*)(h + mp.at.cloud) : nullptr;
+  out->cloud_device = w.cloud ? ctx->x_cloud.p : nullptr;
+  out->cloud_pixel = host && w.cloud ? (const uint32_t*)(h + mp.at.cloud_pixel) : nullptr;
+  out->cloud_pixel_device = w.cloud ? ctx->x_pix.p : nullptr;
+  out->mesh_vertices = host && w.mesh ? (const float*)(h + mp.at.vertices) : nullptr;
+  out->mesh_vertices_device = w.mesh ? ctx->x_verts.p : nullptr;
+  out->mesh_normals = host && w.mesh ? (const float*)(h + mp.at.normals) : nullptr;
+  out->mesh_normals_device = w.mesh ? ctx->x_norms.p : nullptr;
+  out->mesh_triangles = host && w.mesh ? (const int32_t*)(h + mp.at.triangles) : nullptr;
+  out->mesh_triangles_device = w.mesh ? ctx->x_tris.p : nullptr;
+  out->device_ms = stage_ms(ctx->metric);
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_metric_outputs(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                const flame_nltgv2_metric_params* params, int rows, int cols, float* depth_out, uint16_t* depth_mm_out,
+                                float* organized_out, float* cloud_out, uint32_t* cloud_pixel_out, int32_t* n_points_out,
+                                float* mesh_vertices_out, float* mesh_normals_out, int32_t* mesh_triangles_out, int32_t* n_valid_out) {
+  flame_nltgv2_metric_params p;
+  flame_nltgv2_default_metric_params(&p);
+  if (params) p = *params;
+  p.want_depth = depth_out != nullptr, p.want_depth_mm = depth_mm_out != nullptr, p.want_organized = organized_out != nullptr;
+  p.want_cloud = cloud_out != nullptr || cloud_pixel_out != nullptr || n_points_out != nullptr;
+  p.want_mesh = mesh_vertices_out != nullptr || mesh_normals_out != nullptr || mesh_triangles_out != nullptr || n_valid_out != nullptr;
+  p.copy_out = 1;
+  int rc = flame_nltgv2_metric_outputs_begin(ctx, Kinv, T_world_cam, params ? &p : nullptr, rows, cols);
+  if (rc) return rc;
+  flame_nltgv2_metric_outputs_view v;
+  rc = flame_nltgv2_metric_outputs_end(ctx, &v);
+  if (rc) return rc;
+  const size_t n = (size_t)v.rows * (size_t)v.cols, f = sizeof(float);
+  if (depth_out) std::memcpy(depth_out, v.depth, f * n);
+  if (depth_mm_out) std::memcpy(depth_mm_out, v.depth_mm, sizeof(uint16_t) * n);
+  if (organized_out) std::memcpy(organized_out, v.organized, 3 * f * n);
+  if (cloud_out) std::memcpy(cloud_out, v.cloud, 3 * f * (size_t)v.n_points);
+  if (cloud_pixel_out) std::memcpy(cloud_pixel_out, v.cloud_pixel, sizeof(uint32_t) * (size_t)v.n_points);
+  if (n_points_out) *n_points_out = v.n_points;
+  if (mesh_vertices_out) std::memcpy(mesh_vertices_out, v.mesh_vertices, 3 * f * (size_t)v.V);
+  if (mesh_normals_out) std::memcpy(mesh_normals_out, v.mesh_normals, 3 * f * (size_t)v.V);
+  if (mesh_triangles_out) std::memcpy(mesh_triangles_out, v.mesh_triangles, 3 * sizeof(int32_t) * (size_t)v.n_valid);
+  if (n_valid_out) *n_valid_out = v.n_valid;
   return FLAME_NLTGV2_OK;
 }
 

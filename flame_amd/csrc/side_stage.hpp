@@ -1,6 +1,7 @@
 // side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
-// images, the wireframe), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
-// outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it.
+// images, the wireframe, the metric outputs), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
+// outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it (MetricLayout:
+// tests/cpp/metric_layout_test.cc).
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
@@ -99,6 +100,33 @@ inline WireLayout wire_layout(int rows, int cols, bool host_gray) {
   w.gray = w.counts + kWireCountBytes;
   w.total = w.gray + up16(host_gray ? n : 0) + 16;
   return w;
+}
+
+// Which of the metric outputs a call asks for (flame_nltgv2_metric_params), and whether they travel to the host at all.
+struct MetricWants {
+  bool depth, depth_mm, organized, cloud, mesh, copy_out;
+};
+struct MetricLayout {
+  // {n_points, n_valid} | rows*cols floats | rows*cols uint16 | 3*rows*cols floats | up to 3*rows*cols floats | up to rows*cols
+  // uint32 | 3V floats | 3V floats | up to 3T int32.  The counters are always there; an output that is not wanted, and every output
+  // without copy_out, takes no room.
+  size_t counts, depth, depth_mm, organized, cloud, cloud_pixel, vertices, normals, triangles, total;
+};
+inline MetricLayout metric_layout(int rows, int cols, int32_t V, int32_t T, const MetricWants& w) {
+  const size_t n = (size_t)rows * (size_t)cols, f = sizeof(float);
+  const bool out = w.copy_out;
+  MetricLayout m;
+  m.counts = 0;
+  m.depth = 16;
+  m.depth_mm = m.depth + up16(out && w.depth ? f * n : 0);
+  m.organized = m.depth_mm + up16(out && w.depth_mm ? sizeof(uint16_t) * n : 0);
+  m.cloud = m.organized + up16(out && w.organized ? 3 * f * n : 0);
+  m.cloud_pixel = m.cloud + up16(out && w.cloud ? 3 * f * n : 0);
+  m.vertices = m.cloud_pixel + up16(out && w.cloud ? sizeof(uint32_t) * n : 0);
+  m.normals = m.vertices + up16(out && w.mesh ? 3 * f * (size_t)V : 0);
+  m.triangles = m.normals + up16(out && w.mesh ? 3 * f * (size_t)V : 0);
+  m.total = m.triangles + up16(out && w.mesh ? 3 * sizeof(int32_t) * (size_t)T : 0) + 16;
+  return m;
 }
 
 // Every index of T triangles names one of V vertices.

@@ -80,6 +80,33 @@ class _MeshOutputsView(C.Structure):
                 ("filtered_coverage", C.c_int32), ("device_ms", C.c_float)]
 
 
+class MetricParams(C.Structure):
+    """== flame_nltgv2_metric_params (same defaults): the depth window (exclusive, metres), which map (the resident unfiltered one, the
+    filtered one of mesh_outputs_begin(want_filtered_map=True), or map_device = the address of a caller's (rows, cols) f32 device
+    map: its size is taken on trust, its writer must have completed before begin, and it must stay until _end), which outputs, and
+    whether they travel to the host."""
+
+    _fields_ = [("min_depth", C.c_float), ("max_depth", C.c_float), ("use_filtered_map", C.c_int32), ("want_depth", C.c_int32),
+                ("want_depth_mm", C.c_int32), ("want_organized", C.c_int32), ("want_cloud", C.c_int32), ("want_mesh", C.c_int32),
+                ("copy_out", C.c_int32), ("reserved", C.c_int32), ("map_device", C.c_void_p)]
+
+    def __init__(self, min_depth=0.0, max_depth=float("inf"), use_filtered_map=False, want_depth=True, want_depth_mm=True,
+                 want_organized=True, want_cloud=True, want_mesh=False, copy_out=True, map_device=None):
+        super().__init__(min_depth, max_depth, int(bool(use_filtered_map)), int(bool(want_depth)), int(bool(want_depth_mm)),
+                         int(bool(want_organized)), int(bool(want_cloud)), int(bool(want_mesh)), int(bool(copy_out)), 0,
+                         int(map_device) if map_device else None)
+
+
+_METRIC_ARRAYS = (("depth", _FP), ("depth_mm", C.POINTER(C.c_uint16)), ("organized", _FP), ("cloud", _FP),
+                  ("cloud_pixel", C.POINTER(C.c_uint32)), ("mesh_vertices", _FP), ("mesh_normals", _FP), ("mesh_triangles", _IP))
+
+
+class _MetricOutputsView(C.Structure):
+    _fields_ = ([("rows", C.c_int32), ("cols", C.c_int32), ("V", C.c_int32), ("T", C.c_int32), ("n_points", C.c_int32), ("n_valid", C.c_int32)]
+                + [f for name, typ in _METRIC_ARRAYS for f in ((name, typ), (name + "_device", C.c_void_p))]
+                + [("device_ms", C.c_float)])
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -167,6 +194,8 @@ ABI_SYMBOLS = (
     "flame_delaunay_triangulate",
     "flame_nltgv2_default_mesh_filter_params", "flame_nltgv2_oblique_cos_bound", "flame_nltgv2_mesh_outputs_begin",
     "flame_nltgv2_mesh_outputs_end", "flame_nltgv2_mesh_outputs",
+    "flame_nltgv2_default_metric_params", "flame_nltgv2_metric_outputs_begin", "flame_nltgv2_metric_outputs_end",
+    "flame_nltgv2_metric_outputs",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -248,6 +277,11 @@ def load_library():
         "flame_nltgv2_mesh_outputs_end": (C.c_int, [ctx, C.POINTER(_MeshOutputsView)]),
         "flame_nltgv2_mesh_outputs": (C.c_int, [ctx, _IP, C.c_int32, _FP, C.POINTER(MeshFilterParams), C.c_int, C.c_int, C.c_float,
                                                 C.POINTER(C.c_uint8), _FP, _FP, _IP, _FP, _IP]),
+        "flame_nltgv2_default_metric_params": (None, [C.POINTER(MetricParams)]),
+        "flame_nltgv2_metric_outputs_begin": (C.c_int, [ctx, _FP, _FP, C.POINTER(MetricParams), C.c_int, C.c_int]),
+        "flame_nltgv2_metric_outputs_end": (C.c_int, [ctx, C.POINTER(_MetricOutputsView)]),
+        "flame_nltgv2_metric_outputs": (C.c_int, [ctx, _FP, _FP, C.POINTER(MetricParams), C.c_int, C.c_int, _FP, C.POINTER(C.c_uint16), _FP,
+                                                  _FP, C.POINTER(C.c_uint32), _IP, _FP, _FP, _IP, _IP]),
         "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
         "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
                                                       C.c_int]),
@@ -620,6 +654,47 @@ class Regularizer:
         """mesh_outputs_begin; mesh_outputs_end."""
         self.mesh_outputs_begin(triangles, Kinv, rows, cols, graph_scale, filter, want_filtered_map)
         return self.mesh_outputs_end()
+
+    # -- the metric outputs: depth image, point clouds, 3-D mesh (flame_nltgv2_metric_outputs*) -----------------------------------------
+    def metric_outputs_begin(self, Kinv, rows, cols, pose=None, params=None):
+        """Enqueues the depth image / millimetre image / organised and dense cloud (and, params.want_mesh, the posed mesh with its
+        surviving triangles) on the side stream and returns.  pose: T_world_cam as 12 floats, row-major [R | t] (a (3, 4) array or
+        the top of a (4, 4) one); None: the camera frame.  The map and the mesh buffers are the ones the earlier
+        interpolate_mesh[_begin] / mesh_outputs_begin left on the device (params.use_filtered_map, params.map_device)."""
+        k = np.ascontiguousarray(Kinv, np.float32).reshape(9)
+        p = params if params is not None else MetricParams()
+        t = None if pose is None else np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1)[:12])
+        if t is not None and t.size != 12:
+            raise ValueError("pose: expected 12 floats, row-major [R | t]")
+        self._chk(self._L.flame_nltgv2_metric_outputs_begin(self._ctx, k.ctypes.data_as(_FP), None if t is None else t.ctypes.data_as(_FP),
+                                                            C.byref(p), rows, cols), "metric_outputs_begin")
+
+    def metric_outputs_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(n_points, n_valid, device_ms, device = {name: address} and, as asked for, depth (rows,cols)
+        f32, depth_mm (rows,cols) u16, organized (rows,cols,3), cloud (n_points,3), cloud_pixel (n_points,) u32, mesh_vertices (V,3),
+        mesh_normals (V,3), mesh_triangles (n_valid,3) i32).  copy=False: views of the context's pinned memory, valid until the
+        next begin.  With MetricParams(copy_out=False) only the counters and the device addresses are there."""
+        v = _MetricOutputsView()
+        self._chk(self._L.flame_nltgv2_metric_outputs_end(self._ctx, C.byref(v)), "metric_outputs_end")
+        take = (lambda a: a.copy()) if copy else (lambda a: a)
+        shapes = dict(depth=(v.rows, v.cols), depth_mm=(v.rows, v.cols), organized=(v.rows, v.cols, 3), cloud=(v.n_points, 3),
+                      cloud_pixel=(v.n_points,), mesh_vertices=(v.V, 3), mesh_normals=(v.V, 3), mesh_triangles=(v.n_valid, 3))
+        out = dict(n_points=int(v.n_points), n_valid=int(v.n_valid), device_ms=float(v.device_ms), rows=int(v.rows), cols=int(v.cols),
+                   V=int(v.V), T=int(v.T), device={})
+        for name, typ in _METRIC_ARRAYS:
+            dev = getattr(v, name + "_device")
+            if dev:
+                out["device"][name] = int(dev)
+            ptr = getattr(v, name)
+            if ptr:
+                shape = shapes[name]
+                out[name] = take(np.ctypeslib.as_array(ptr, shape=shape)) if shape[0] > 0 else np.zeros(shape, typ._type_)
+        return out
+
+    def metric_outputs(self, Kinv, rows, cols, pose=None, params=None) -> dict:
+        """metric_outputs_begin; metric_outputs_end."""
+        self.metric_outputs_begin(Kinv, rows, cols, pose, params)
+        return self.metric_outputs_end()
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

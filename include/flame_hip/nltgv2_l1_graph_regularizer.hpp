@@ -24,6 +24,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -202,6 +203,41 @@ struct MeshOutputs {
   int filtered_coverage = 0;
 };
 
+// What the metric outputs read beside the maps (flame_nltgv2_metric_params, same defaults): the depth window in metres (both bounds
+// exclusive), which map, which outputs, and whether they travel to the host.  Layout-identical to the C-ABI struct.
+struct MetricParams {
+  float min_depth = 0.0f;
+  float max_depth = std::numeric_limits<float>::infinity();
+  int32_t use_filtered_map = 0;  // 0: the resident unfiltered map; 1: the filtered map of meshOutputsBegin(want_filtered_map)
+  int32_t want_depth = 1;
+  int32_t want_depth_mm = 1;
+  int32_t want_organized = 1;
+  int32_t want_cloud = 1;
+  int32_t want_mesh = 0;         // mesh_vertices + mesh_normals + mesh_triangles (needs a meshOutputsBegin for the resident triangles)
+  int32_t copy_out = 1;          // 0: the outputs stay on the device, only the counters travel
+  int32_t reserved = 0;
+  const void* map_device = nullptr;  // a rows x cols float map in device memory of the caller's, read instead of the resident ones
+};
+static_assert(sizeof(MetricParams) == sizeof(flame_nltgv2_metric_params), "MetricParams must mirror the C-ABI struct");
+
+// What a consumer reads (flame_nltgv2_metric_outputs_view): depth image in metres, the 16-bit millimetre image, the organised and the
+// dense cloud, the posed mesh with the triangles that survived the filters.  Host pointers into pinned memory of the DeviceGraph and,
+// beside each, the device pointer of the same array; all valid until its next metricOutputsBegin().  Not asked for: nullptr.
+struct MetricOutputs {
+  int rows = 0, cols = 0;
+  size_t num_vertices = 0, num_triangles = 0;
+  size_t num_points = 0;            // points of the dense cloud
+  size_t num_valid_triangles = 0;   // triples in mesh_triangles
+  const float* depth = nullptr;             const void* depth_device = nullptr;           // [rows * cols], NaN on holes
+  const uint16_t* depth_mm = nullptr;       const void* depth_mm_device = nullptr;        // [rows * cols], 0 on holes
+  const float* organized = nullptr;         const void* organized_device = nullptr;       // [rows * cols * 3], NaN on holes
+  const float* cloud = nullptr;             const void* cloud_device = nullptr;           // [num_points * 3]
+  const uint32_t* cloud_pixel = nullptr;    const void* cloud_pixel_device = nullptr;     // [num_points] row * cols + col, ascending
+  const float* mesh_vertices = nullptr;     const void* mesh_vertices_device = nullptr;   // [num_vertices * 3]
+  const float* mesh_normals = nullptr;      const void* mesh_normals_device = nullptr;    // [num_vertices * 3]
+  const int32_t* mesh_triangles = nullptr;  const void* mesh_triangles_device = nullptr;  // [num_valid_triangles * 3]
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -368,6 +404,32 @@ class DeviceGraph {
     m.vtx_idepths = v.vtx_idepth, m.vtx_normals = v.normals, m.tri_validity = v.tri_valid;
     m.num_valid_triangles = v.n_valid;
     m.rows = v.rows, m.cols = v.cols, m.filtered_idepthmap = v.filtered_map, m.filtered_coverage = v.filtered_coverage;
+    return m;
+  }
+
+  // Depth image, millimetre image, point clouds and the posed mesh from the maps and the mesh buffers the last interpolateMesh[Begin] /
+  // meshOutputsBegin left on the device, on the side stream (flame_nltgv2_metric_outputs_begin / _end; the semantics are stated
+  // there).  T_world_cam: 12 floats, row-major [R | t], or nullptr for the camera frame.
+  void metricOutputsBegin(const float Kinv[9], const float* T_world_cam, const MetricParams& params, int rows, int cols) {
+    flame_nltgv2_metric_params c;
+    std::memcpy(&c, &params, sizeof(c));
+    check(flame_nltgv2_metric_outputs_begin(ctx_, Kinv, T_world_cam, &c, rows, cols), "metric_outputs_begin");
+  }
+  MetricOutputs metricOutputsEnd() {
+    flame_nltgv2_metric_outputs_view v;
+    check(flame_nltgv2_metric_outputs_end(ctx_, &v), "metric_outputs_end");
+    MetricOutputs m;
+    m.rows = v.rows, m.cols = v.cols;
+    m.num_vertices = static_cast<size_t>(v.V), m.num_triangles = static_cast<size_t>(v.T);
+    m.num_points = static_cast<size_t>(v.n_points), m.num_valid_triangles = static_cast<size_t>(v.n_valid);
+    m.depth = v.depth, m.depth_device = v.depth_device;
+    m.depth_mm = v.depth_mm, m.depth_mm_device = v.depth_mm_device;
+    m.organized = v.organized, m.organized_device = v.organized_device;
+    m.cloud = v.cloud, m.cloud_device = v.cloud_device;
+    m.cloud_pixel = v.cloud_pixel, m.cloud_pixel_device = v.cloud_pixel_device;
+    m.mesh_vertices = v.mesh_vertices, m.mesh_vertices_device = v.mesh_vertices_device;
+    m.mesh_normals = v.mesh_normals, m.mesh_normals_device = v.mesh_normals_device;
+    m.mesh_triangles = v.mesh_triangles, m.mesh_triangles_device = v.mesh_triangles_device;
     return m;
   }
 

@@ -350,6 +350,100 @@ int flame_nltgv2_mesh_outputs(flame_nltgv2_ctx* ctx, const int32_t* triangles, i
                               uint8_t* tri_valid_out, float* normals_out, float* vtx_idepth_out, int32_t* n_valid_out,
                               float* filtered_map_out, int32_t* filtered_coverage_out);
 
+/* ---- Metric outputs: what a consumer of the library reads -- a depth image, a point cloud, a 3-D mesh -------------------------------
+ * A planner, a TSDF fuser or a ROS front-end does not read inverse depth on a pixel grid.  This stage makes, from the maps and the mesh
+ * buffers that already stand on the device, on the context's side stream, beside the running solver: the depth image in metres, the
+ * 16-bit millimetre image, the organised and the dense point cloud in the camera or the world frame, and the mesh with 3-D vertices,
+ * normals and only the triangles that survived the filters.  Nothing of this has a counterpart in the reference; the conventions are the
+ * ones stated for flame_nltgv2_mesh_outputs above.  tests/metric_ref.py restates the operations in numpy float32 and is the checker:
+ * device and checker agree bit for bit.
+ *
+ * PER PIXEL (row, col) with map value v:
+ *   q = Kinv * (col, row, 1): the full 3x3 product, every sum of three products left to right, no FMA;
+ *   P = q / v: three divisions;  z = P.z;
+ *   the pixel is VALID iff v > 0.0f && z > min_depth && z < max_depth.  Every comparison with a NaN is false, so with the defaults
+ *   (min_depth = 0, max_depth = +infinity) a NaN, zero, negative or infinite v and an overflowing z are all holes.
+ * WORLD FRAME: with a pose T_world_cam (12 floats, row-major [R | t]) P_w = ((r0 * x + r1 * y) + r2 * z) + t, row by row; with NULL
+ *   the camera-frame P is written untouched.  A valid pixel's point is written with plain IEEE results.
+ * OUTPUTS, each chosen by its want_* flag:
+ *   depth          [rows * cols] float     z where the pixel is valid, the quiet NaN 0x7fc00000 on holes (z is the CAMERA-frame depth,
+ *                                          with a pose too)
+ *   depth_mm       [rows * cols] uint16    rintf(z * 1000.0f), ties to even; written if it lies in [1, 65535], else 0; 0 on holes
+ *   organized      [rows * cols * 3] float P or P_w; three quiet NaNs 0x7fc00000 on holes
+ *   cloud          [n_points * 3] float, cloud_pixel [n_points] uint32: the valid pixels' points and linear pixel indices
+ *                                          row * cols + col in ascending row-major order.  Deterministic: count / scan / scatter, a
+ *                                          lane's rank from the scan and the wave's 64-bit ballot, no counter that lanes race for.
+ *   mesh_vertices  [3V] float              the vertices flame_nltgv2_mesh_outputs_begin back-projected, P = (Kinv * (pos, 1)) /
+ *                                          (x * graph_scale) with ITS Kinv and graph_scale, then posed; every vertex is written, with
+ *                                          plain IEEE results (x == 0: infinite points)
+ *   mesh_normals   [3V] float              R * the vertex normals of that call ((r0 * nx + r1 * ny) + r2 * nz); without a pose copies
+ *   mesh_triangles [3 * n_valid] int32     the index triples of the triangles with non-zero validity of that call, in ascending triangle
+ *                                          index; n_valid is the n_valid it reported.  The vertices are not compacted or re-indexed.
+ * WHICH MAP: map_device != NULL: a map of the caller's own in device memory (a torch tensor, another library's output), read in
+ *   place of the resident ones by the same kernels; nothing is uploaded.  Its rules, since the library knows nothing about it:
+ *     - it holds rows * cols floats, row-major, rows of cols floats without padding, on the context's device.  The size cannot be
+ *       checked: rows and cols are taken on trust, and a smaller buffer is read out of bounds;
+ *     - it is read on the context's SIDE stream, which waits for no stream of the caller's: whatever writes the map must have
+ *       completed before begin is called (a stream or device synchronise of the caller's), and the map must stay allocated and
+ *       unchanged until _end has returned;
+ *     - use_filtered_map is ignored, no resident map is needed and none is touched; a graph is still required
+ *       (FLAME_NLTGV2_ERR_NO_GRAPH), as for every stage of this context, and want_mesh keeps its own conditions.
+ *   Otherwise use_filtered_map == 0: the resident unfiltered map of the last flame_nltgv2_interpolate_mesh[_begin];
+ *   use_filtered_map != 0: the filtered map of the last flame_nltgv2_mesh_outputs_begin(want_filtered_map != 0).
+ * The mesh outputs need the validity, the normals and the vertices of a flame_nltgv2_mesh_outputs_begin for the current topology and
+ * the current triangle upload (the rule of flame_nltgv2_wireframe_params.validity == 2). */
+typedef struct flame_nltgv2_metric_params {
+  float   min_depth;         /* 0.0        metres, exclusive */
+  float   max_depth;         /* +infinity  metres, exclusive */
+  int32_t use_filtered_map;  /* 0 */
+  int32_t want_depth;        /* 1 */
+  int32_t want_depth_mm;     /* 1 */
+  int32_t want_organized;    /* 1 */
+  int32_t want_cloud;        /* 1 */
+  int32_t want_mesh;         /* 0  mesh_vertices + mesh_normals + mesh_triangles */
+  int32_t copy_out;          /* 1  0: the outputs stay on the device; only the two counters travel */
+  int32_t reserved;          /* 0 */
+  const void* map_device;    /* NULL       a caller's own device map: see WHICH MAP above for its rules */
+} flame_nltgv2_metric_params;
+void flame_nltgv2_default_metric_params(flame_nltgv2_metric_params* p);
+
+/* Pointers into pinned memory of the context and, beside each, the device pointer of the same array; all valid until the next
+ * flame_nltgv2_metric_outputs_begin.  An output that was not asked for has two NULLs; with copy_out == 0 every host pointer is NULL. */
+typedef struct flame_nltgv2_metric_outputs_view {
+  int32_t rows, cols, V, T;
+  int32_t n_points;                  /* valid pixels (0 without want_cloud) */
+  int32_t n_valid;                   /* valid triangles (0 without want_mesh) */
+  const float* depth;                const void* depth_device;
+  const uint16_t* depth_mm;          const void* depth_mm_device;
+  const float* organized;            const void* organized_device;
+  const float* cloud;                const void* cloud_device;
+  const uint32_t* cloud_pixel;       const void* cloud_pixel_device;
+  const float* mesh_vertices;        const void* mesh_vertices_device;
+  const float* mesh_normals;         const void* mesh_normals_device;
+  const int32_t* mesh_triangles;     const void* mesh_triangles_device;
+  float device_ms;                   /* measurement aid: HIP-event time of what begin enqueued on the side stream, kernels and copies out
+                                        (the n_points points of `cloud` travel in _end, once their number is known: not in it) */
+} flame_nltgv2_metric_outputs_view;
+
+/* begin  checks the arguments -- an error (no graph; Kinv or params NULL; rows / cols <= 0 or rows * cols >= 2^31; no resident map of
+ *        the kind asked for, or one of another size than rows x cols; want_mesh without current mesh buffers; nothing wanted) is reported
+ *        before anything is enqueued and leaves the outputs of an earlier begin, and its pending _end, as they are --, then enqueues
+ *        everything on the context's side stream and returns.  The stage only READS the buffers of the other stages, in the order of
+ *        that stream: a metric_outputs_begin right behind interpolate_mesh_begin + mesh_outputs_begin describes their state, whatever
+ *        the solver does meanwhile.
+ *        Kinv: 9 floats row-major (Flame::Kinv_).  T_world_cam: 12 floats or NULL.
+ * end    waits for the side stream, brings the n_points points of the dense cloud to the host (copy_out) and fills *out.
+ * flame_nltgv2_metric_outputs == begin (with copy_out forced to 1 and the want_* flags replaced by: the array is not NULL; mesh: any of
+ *        the three); end; copies into the caller's arrays.  cloud_out / cloud_pixel_out must hold rows * cols points,
+ *        mesh_triangles_out 3T indices. */
+int flame_nltgv2_metric_outputs_begin(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                      const flame_nltgv2_metric_params* params, int rows, int cols);
+int flame_nltgv2_metric_outputs_end(flame_nltgv2_ctx* ctx, flame_nltgv2_metric_outputs_view* out);
+int flame_nltgv2_metric_outputs(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                const flame_nltgv2_metric_params* params, int rows, int cols, float* depth_out, uint16_t* depth_mm_out,
+                                float* organized_out, float* cloud_out, uint32_t* cloud_pixel_out, int32_t* n_points_out,
+                                float* mesh_vertices_out, float* mesh_normals_out, int32_t* mesh_triangles_out, int32_t* n_valid_out);
+
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
  * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
