@@ -19,6 +19,8 @@
 #include "debug_kernels.h"
 #include "detections_kernels.h"
 #include "matches_kernels.h"
+#include "input_kernels.h"
+#include "input_params.hpp"
 #include "roctx_ranges.hpp"
 
 using namespace flame_hip;
@@ -46,8 +48,15 @@ struct flame_stereo_ctx {
   std::vector<Frame> spare;  // buffers of dropped frames, reused by the next add_frame: hipFree waits for every stream of the device, also
                              // for a solver that runs beside the tracker (tools/frame_loop.py --pipelined: 0.5 ms per frame).
                              // At most kSpareFrames of them (release_frame).
-  uint8_t* d_raw = nullptr;  // staging of the unpadded upload
+  uint8_t* d_raw = nullptr;  // staging of the unpadded upload; the rectified grey image of add_raw_frame
   size_t raw_cap = 0;
+  // add_raw_frame (input_kernels.hip)
+  bool have_input = false;  // set_input since the last set_camera
+  flame_stereo_input_params input{};
+  uint8_t* d_rawsrc = nullptr;  // staging of a raw frame that comes from the host
+  size_t rawsrc_cap = 0;
+  int* d_istats = nullptr;  // kInputWords ints
+  int* h_istats = nullptr;  // pinned, the same
   StereoPoseEntry* d_poses = nullptr;
   size_t poses_cap = 0;
   StereoPoseEntry* h_poses = nullptr;  // pinned
@@ -158,6 +167,30 @@ void release_frame(flame_stereo_ctx* ctx, std::unordered_map<uint32_t, Frame>::i
 }
 
 size_t padded_pixels(const StereoCamera& c) { return (size_t)(c.width + 2 * c.border) * (size_t)(c.height + 2 * c.border); }
+
+// The buffer set of frame `frame_id` for add_frame / add_raw_frame to fill: the one the id has (adding an existing id replaces
+// it), else one from `spare`, else a new one.  On failure the id is not resident.
+int acquire_frame(flame_stereo_ctx* ctx, uint32_t frame_id, Frame** out) {
+  Frame& f = ctx->frames[frame_id];
+  const size_t px = padded_pixels(ctx->cam);
+  if (!f.img_pad && !ctx->spare.empty()) {
+    f = ctx->spare.back();
+    ctx->spare.pop_back();
+  }
+  if (!f.img_pad) {
+    hipError_t e = hipMalloc((void**)&f.img_pad, px);
+    if (e == hipSuccess) e = hipMalloc((void**)&f.gx_pad, px * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&f.gy_pad, px * sizeof(float));
+    if (e != hipSuccess) {
+      free_frame(f);
+      ctx->frames.erase(frame_id);
+      ctx->last_hip = (int)e;
+      return e == hipErrorOutOfMemory ? FLAME_NLTGV2_ERR_OOM : FLAME_NLTGV2_ERR_HIP;
+    }
+  }
+  *out = &f;
+  return 0;
+}
 
 template <typename T>
 int grow(flame_stereo_ctx* ctx, T** p, size_t* cap, size_t count) {
@@ -495,7 +528,9 @@ int flame_stereo_create(flame_stereo_ctx** out, int device) {
       hipMalloc((void**)&ctx->d_stats, kStatWords * sizeof(int)) != hipSuccess ||
       hipHostMalloc((void**)&ctx->h_stats, kStatWords * sizeof(int), hipHostMallocDefault) != hipSuccess ||
       hipMalloc((void**)&ctx->d_fstats, kFrontWords * sizeof(int)) != hipSuccess ||
-      hipHostMalloc((void**)&ctx->h_fstats, kFrontWords * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+      hipHostMalloc((void**)&ctx->h_fstats, kFrontWords * sizeof(int), hipHostMallocDefault) != hipSuccess ||
+      hipMalloc((void**)&ctx->d_istats, kInputWords * sizeof(int)) != hipSuccess ||
+      hipHostMalloc((void**)&ctx->h_istats, kInputWords * sizeof(int), hipHostMallocDefault) != hipSuccess) {
     flame_stereo_destroy(ctx);
     return FLAME_NLTGV2_ERR_HIP;
   }
@@ -517,10 +552,11 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
                   (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_keep_ids, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
                   (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel, (void*)ctx->d_owner, (void*)ctx->d_draw,
-                  (void*)ctx->d_match, (void*)ctx->d_mlist, (void*)ctx->d_mentries})
+                  (void*)ctx->d_match, (void*)ctx->d_mlist, (void*)ctx->d_mentries, (void*)ctx->d_rawsrc, (void*)ctx->d_istats})
     if (p) (void)hipFree(p);
   if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
   if (ctx->h_sel) (void)hipHostFree(ctx->h_sel);
+  if (ctx->h_istats) (void)hipHostFree(ctx->h_istats);
   if (ctx->d_stats) (void)hipFree(ctx->d_stats);
   if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -544,6 +580,7 @@ int flame_stereo_set_camera(flame_stereo_ctx* ctx, const float K[9], const float
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
   drop_all_frames(ctx);
   ctx->match_stand = false;
+  ctx->have_input = false;  // (the input describes raw frames for one working camera)
   std::memcpy(ctx->cam.K, K, sizeof ctx->cam.K);
   std::memcpy(ctx->cam.Kinv, Kinv, sizeof ctx->cam.Kinv);
   ctx->cam.width = width, ctx->cam.height = height, ctx->cam.border = border;
@@ -558,28 +595,74 @@ int flame_stereo_add_frame(flame_stereo_ctx* ctx, uint32_t frame_id, const uint8
   const int w = ctx->cam.width, h = ctx->cam.height;
   if (!img || row_stride_bytes < w) return FLAME_NLTGV2_ERR_INVALID_ARG;
   if (int rc = grow(ctx, &ctx->d_raw, &ctx->raw_cap, (size_t)w * h)) return rc;
-  Frame& f = ctx->frames[frame_id];
-  const size_t px = padded_pixels(ctx->cam);
-  if (!f.img_pad && !ctx->spare.empty()) {
-    f = ctx->spare.back();
-    ctx->spare.pop_back();
-  }
-  if (!f.img_pad) {
-    hipError_t e = hipMalloc((void**)&f.img_pad, px);
-    if (e == hipSuccess) e = hipMalloc((void**)&f.gx_pad, px * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&f.gy_pad, px * sizeof(float));
-    if (e != hipSuccess) {
-      free_frame(f);
-      ctx->frames.erase(frame_id);
-      ctx->last_hip = (int)e;
-      return e == hipErrorOutOfMemory ? FLAME_NLTGV2_ERR_OOM : FLAME_NLTGV2_ERR_HIP;
-    }
-  }
+  Frame* f = nullptr;
+  if (int rc = acquire_frame(ctx, frame_id, &f)) return rc;
   SCHK(ctx, hipMemcpy2DAsync(ctx->d_raw, (size_t)w, img, (size_t)row_stride_bytes, (size_t)w, (size_t)h,
                              hipMemcpyHostToDevice, ctx->stream));
-  SCHK(ctx, launch_frame_pad_gradient(ctx->d_raw, w, h, ctx->cam.border, f.img_pad, f.gx_pad, f.gy_pad, ctx->stream));
+  SCHK(ctx, launch_frame_pad_gradient(ctx->d_raw, w, h, ctx->cam.border, f->img_pad, f->gx_pad, f->gy_pad, ctx->stream));
   // the staging buffer is reused by the next add_frame and `img` is pageable host memory
   SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+void flame_stereo_default_input_params(flame_stereo_input_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->format = FLAME_STEREO_FMT_GREY8;
+  p->K_raw[0] = p->K_raw[4] = p->K_raw[8] = 1.0f;
+}
+
+int flame_stereo_set_input(flame_stereo_ctx* ctx, const flame_stereo_input_params* p) {
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  if (!input_params_valid(p, ctx->cam.width, ctx->cam.height)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  ctx->input = *p;
+  ctx->have_input = true;
+  return 0;
+}
+
+int flame_stereo_add_raw_frame(flame_stereo_ctx* ctx, uint32_t frame_id, const void* raw, int row_stride_bytes,
+                               int raw_on_device, flame_stereo_input_stats* stats) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_add_raw_frame");
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  const flame_stereo_input_params& in = ctx->input;
+  const int w = ctx->cam.width, h = ctx->cam.height;
+  if (!ctx->have_input || !input_params_valid(&in, w, h) || !input_frame_valid(in, raw, row_stride_bytes))
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  // (both buffers hold their size after the first frame: grow() reallocates, and so waits for the device, only then)
+  if (ctx->raw_cap < (size_t)w * h) SCHK(ctx, hipStreamSynchronize(ctx->stream));  // an enqueued frame may still read d_raw
+  if (int rc = grow(ctx, &ctx->d_raw, &ctx->raw_cap, (size_t)w * h)) return rc;
+  const uint8_t* src = (const uint8_t*)raw;
+  if (!raw_on_device) {
+    const size_t bytes = input_frame_bytes(in, row_stride_bytes);
+    if (int rc = grow(ctx, &ctx->d_rawsrc, &ctx->rawsrc_cap, bytes)) return rc;
+    src = ctx->d_rawsrc;
+  }
+  Frame* f = nullptr;
+  if (int rc = acquire_frame(ctx, frame_id, &f)) return rc;
+  if (!raw_on_device)  // rows and their padding in one run: the kernel reads the caller's stride
+    SCHK(ctx, hipMemcpyAsync(ctx->d_rawsrc, raw, input_frame_bytes(in, row_stride_bytes), hipMemcpyHostToDevice, ctx->stream));
+  InputMap m;
+  std::memcpy(m.kinv, ctx->cam.Kinv, sizeof m.kinv);
+  m.fx = in.K_raw[0], m.skew = in.K_raw[1], m.cx = in.K_raw[2], m.fy = in.K_raw[4], m.cy = in.K_raw[5];
+  m.k1 = in.dist[0], m.k2 = in.dist[1], m.p1 = in.dist[2], m.p2 = in.dist[3];
+  m.k3 = in.dist[4], m.k4 = in.dist[5], m.k5 = in.dist[6], m.k6 = in.dist[7];
+  m.raw_width = in.raw_width, m.raw_height = in.raw_height;
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, (hipError_t)launch_input_rectify(m, in.format, in.remap != 0, src, row_stride_bytes, w, h, ctx->d_istats, ctx->d_raw,
+                                             ctx->stream));
+  SCHK(ctx, launch_frame_pad_gradient(ctx->d_raw, w, h, ctx->cam.border, f->img_pad, f->gx_pad, f->gy_pad, ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  if (stats) SCHK(ctx, hipMemcpyAsync(ctx->h_istats, ctx->d_istats, kInputWords * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  // a host source is pageable memory; a device source is the caller's to keep until the stream has passed (flame_stereo.h)
+  if (!raw_on_device || stats) SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) {
+    int sum = 0;
+    for (int k = 0; k < kInputSlots; ++k) sum += ctx->h_istats[k * kInputSlotStride];
+    stats->n_outside = sum;
+  }
   return 0;
 }
 

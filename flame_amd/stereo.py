@@ -63,6 +63,39 @@ class DetectParams(C.Structure):
             setattr(self, k, v)
 
 
+FMT_GREY8, FMT_BGR8, FMT_RGB8, FMT_BGRA8, FMT_RGBA8 = range(5)  # FLAME_STEREO_FMT_*
+FORMAT_BYTES = {FMT_GREY8: 1, FMT_BGR8: 3, FMT_RGB8: 3, FMT_BGRA8: 4, FMT_RGBA8: 4}
+
+
+class InputParams(C.Structure):
+    """flame_stereo_input_params: what the raw frames of add_raw_frame look like; defaults are
+    flame_stereo_default_input_params' (GREY8, remap 0, sizes 0, K_raw = I, dist = 0).  K_raw: 9 floats, row-major; dist:
+    up to 8 floats k1 k2 p1 p2 k3 k4 k5 k6 (the rest 0)."""
+    _fields_ = [("format", C.c_int32), ("remap", C.c_int32), ("raw_width", C.c_int32), ("raw_height", C.c_int32),
+                ("K_raw", C.c_float * 9), ("dist", C.c_float * 8)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib().flame_stereo_default_input_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown input parameter %r" % k)
+            if k == "K_raw":
+                v = (C.c_float * 9)(*[float(x) for x in _f32(v, 9)])
+            elif k == "dist":
+                d = np.zeros(8, np.float32)
+                src = np.asarray(v, np.float32).reshape(-1)
+                if src.size > 8:
+                    raise ValueError("at most 8 distortion coefficients")
+                d[:src.size] = src
+                v = (C.c_float * 8)(*[float(x) for x in d])
+            setattr(self, k, v)
+
+
+class _InputStats(C.Structure):
+    _fields_ = [("n_outside", C.c_int32)]
+
+
 class _FeatureStats(C.Structure):
     _fields_ = [("num_features", C.c_int32), ("num_examined", C.c_int32), ("error_feature", C.c_int32)]
 
@@ -130,7 +163,8 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_prune_features", "flame_stereo_clear_features", "flame_stereo_default_graph_params",
     "flame_stereo_select_graph_features", "flame_stereo_select_graph_features_arrays",
     "flame_stereo_draw_features", "flame_stereo_frame_image_device", "flame_stereo_draw_matches",
-    "flame_stereo_draw_detections",
+    "flame_stereo_draw_detections", "flame_stereo_default_input_params", "flame_stereo_set_input",
+    "flame_stereo_add_raw_frame",
 )
 OPT_LANES_PER_FEATURE = 1
 OPT_GRAPH_COPY = 2
@@ -194,6 +228,10 @@ def _lib():
             "flame_stereo_draw_matches": (C.c_int, [ctx, C.c_int, C.c_void_p, C.POINTER(_MatchesStats)]),
             "flame_stereo_draw_detections": (C.c_int, [ctx, PP, C.POINTER(DetectParams), C.c_uint32, _FP, _FP, C.c_float,
                                                        C.c_int, C.c_void_p, C.POINTER(_DetectionsStats)]),
+            "flame_stereo_default_input_params": (None, [C.POINTER(InputParams)]),
+            "flame_stereo_set_input": (C.c_int, [ctx, C.POINTER(InputParams)]),
+            "flame_stereo_add_raw_frame": (C.c_int, [ctx, C.c_uint32, C.c_void_p, C.c_int, C.c_int,
+                                                     C.POINTER(_InputStats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -218,6 +256,7 @@ class FeatureTracker:
         self._ctx = C.c_void_p()
         self._chk(self._L.flame_stereo_create(C.byref(self._ctx), device), "create")
         self.width, self.height, self.border = width, height, border
+        self._input = None  # (format, raw_width, raw_height) of the last set_input
         K, Kinv = _f32(K, 9), _f32(Kinv, 9)
         self._chk(self._L.flame_stereo_set_camera(self._ctx, K.ctypes.data_as(_FP), Kinv.ctypes.data_as(_FP), width, height,
                                                   border), "set_camera")
@@ -243,6 +282,60 @@ class FeatureTracker:
         if img.shape != (self.height, self.width):
             raise ValueError("image must be %dx%d" % (self.height, self.width))
         self._chk(self._L.flame_stereo_add_frame(self._ctx, frame_id, img.ctypes.data, img.strides[0]), "add_frame")
+
+    def set_camera(self, K, Kinv, width: int, height: int, border: int = 5):
+        """flame_stereo_set_camera: another working camera.  Drops all frames and forgets set_input."""
+        K, Kinv = _f32(K, 9), _f32(Kinv, 9)
+        self._chk(self._L.flame_stereo_set_camera(self._ctx, K.ctypes.data_as(_FP), Kinv.ctypes.data_as(_FP), width, height,
+                                                  border), "set_camera")
+        self.width, self.height, self.border = width, height, border
+        self._input = None
+
+    def set_input(self, params: InputParams = None, **kw):
+        """flame_stereo_set_input: what the raw frames of add_raw_frame look like -- an InputParams, or its fields as
+        keywords (format, remap, raw_width, raw_height, K_raw, dist)."""
+        if params is None:
+            params = InputParams(**kw)
+        elif kw:
+            raise TypeError("an InputParams or keywords, not both")
+        self._chk(self._L.flame_stereo_set_input(self._ctx, C.byref(params)), "set_input")
+        self._input = (int(params.format), int(params.raw_width), int(params.raw_height))
+
+    def add_raw_frame(self, frame_id: int, raw, *, device_ptr=None, stride=None, want_stats=True):
+        """flame_stereo_add_raw_frame: colour to grey, undistort / resize and Frame::create level 0 on the device, from a
+        raw camera frame as set_input describes it.  `raw`: a uint8 numpy array of raw_height rows ((rows, cols) for GREY8,
+        (rows, cols, channels) or (rows, bytes) otherwise; its row stride is taken from the array unless `stride` is
+        given, its rows must be contiguous), or None together with `device_ptr`, the device address of such a frame with
+        `stride` bytes per row (default: tight).  A device source with want_stats=False is enqueued only: the caller keeps
+        the buffer alive and unchanged until the tracker's stream has passed it.  Returns the stats dict (n_outside), or
+        None when want_stats is False."""
+        if (raw is None) == (device_ptr is None):
+            raise ValueError("raw or device_ptr, one of the two")
+        if raw is not None:
+            if raw.dtype != np.uint8 or raw.ndim not in (2, 3):
+                raise ValueError("raw must be a uint8 array of 2 or 3 dimensions")
+            if raw.strides[-1] != 1 or (raw.ndim == 3 and raw.strides[1] != raw.shape[2]):
+                raw = np.ascontiguousarray(raw)
+            row_bytes = raw.shape[1] * (raw.shape[2] if raw.ndim == 3 else 1)
+            if stride is None:
+                stride = raw.strides[0]
+            inp = self._input
+            if inp is not None:  # (without set_input the library answers; this keeps its reads inside the array)
+                if raw.shape[0] != inp[2] or row_bytes < inp[1] * FORMAT_BYTES[inp[0]] or stride > raw.strides[0]:
+                    raise ValueError("raw does not hold %d rows of %d pixels" % (inp[2], inp[1]))
+            ptr = raw.ctypes.data
+        else:
+            ptr = int(device_ptr)
+            if stride is None:
+                inp = self._input
+                if inp is None:
+                    raise ValueError("stride is needed without set_input")
+                stride = inp[1] * FORMAT_BYTES[inp[0]]
+        st = _InputStats()
+        rc = self._L.flame_stereo_add_raw_frame(self._ctx, frame_id, C.c_void_p(ptr), int(stride), int(raw is None),
+                                                C.byref(st) if want_stats else None)
+        self._chk(rc, "add_raw_frame")
+        return {"n_outside": int(st.n_outside)} if want_stats else None
 
     def drop_frame(self, frame_id: int):
         self._chk(self._L.flame_stereo_drop_frame(self._ctx, frame_id), "drop_frame")

@@ -187,6 +187,16 @@ class FeatureTracker {
   void addFrame(uint32_t frame_id, const uint8_t* img, int row_stride_bytes) {
     check(flame_stereo_add_frame(ctx_, frame_id, img, row_stride_bytes), -1, "flame_stereo_add_frame");
   }
+  // Where the front-end ran cv::cvtColor and cv::undistort before Flame::update: setInput once per camera (after the
+  // constructor; flame_stereo_default_input_params fills the struct), then addRawFrame per frame with the frame as the camera
+  // delivered it, in host memory (on_device false: waits, as addFrame) or in device memory (on_device true: with stats NULL
+  // only enqueued -- the caller keeps `raw` alive and unchanged until the tracker's stream has passed it).
+  void setInput(const flame_stereo_input_params& input) { check(flame_stereo_set_input(ctx_, &input), -1, "flame_stereo_set_input"); }
+  void addRawFrame(uint32_t frame_id, const void* raw, int row_stride_bytes, bool on_device = false,
+                   flame_stereo_input_stats* stats = nullptr) {
+    check(flame_stereo_add_raw_frame(ctx_, frame_id, raw, row_stride_bytes, on_device ? 1 : 0, stats), -1,
+          "flame_stereo_add_raw_frame");
+  }
   void dropFrame(uint32_t frame_id) { check(flame_stereo_drop_frame(ctx_, frame_id), -1, "flame_stereo_drop_frame"); }
   int frameCount() const { return flame_stereo_frame_count(ctx_); }
 

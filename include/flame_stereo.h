@@ -123,6 +123,75 @@ int flame_stereo_set_camera(flame_stereo_ctx* ctx, const float K[9], const float
 int flame_stereo_add_frame(flame_stereo_ctx* ctx, uint32_t frame_id, const uint8_t* img, int row_stride_bytes);
 int flame_stereo_drop_frame(flame_stereo_ctx* ctx, uint32_t frame_id);
 int flame_stereo_frame_count(const flame_stereo_ctx* ctx);
+
+/* ---- Raw camera frames: colour to grey, undistort / resize, then Frame::create ------------------------------------------
+ * flame_stereo_add_frame takes what Flame::update takes: an 8-bit grey image, rectified, of the camera's size, in host memory.
+ * The reference's front-end (flame_ros, not part of the reference tree) makes that image on the host with cv::cvtColor and
+ * cv::undistort.  flame_stereo_add_raw_frame takes the frame as the camera delivers it -- grey or colour, any row stride,
+ * with lens distortion, of another size, in host or device memory -- and leaves the same resident frame under the same id
+ * (img_pad, gradx_pad, grady_pad): a kernel writes the rectified grey image, and the kernel behind flame_stereo_add_frame
+ * builds the padded planes from it, unchanged.  THE DEFINITION (tests/input_ref.py restates it; all of it is this library's
+ * own statement, see UNPINNED below):
+ *   Grey of a tap.  Integer arithmetic on the tap's bytes: (4899 * R + 9617 * G + 1868 * B + 8192) >> 14; alpha is ignored;
+ *      GREY8 is taken as is.  These are the coefficients of OpenCV's 8-bit cvtColor (they sum to 16384).  No OpenCV is part of
+ *      this tree or of the reference tree, so the formula is stated, not checked against OpenCV: it is the definition.
+ *   remap == 0.  The rectified pixel (u, v) is the grey of the raw pixel (u, v).
+ *   remap == 1.  For the rectified pixel (u, v), in float32, one rounding per operation, in exactly this association (the
+ *      library is built with -ffp-contract=off); Kinv is the context's (set_camera; its third row is not read), dist =
+ *      k1 k2 p1 p2 k3 k4 k5 k6:
+ *        x  = (Kinv[0]*u + Kinv[1]*v) + Kinv[2]          y  = (Kinv[3]*u + Kinv[4]*v) + Kinv[5]
+ *        r2 = x*x + y*y     r4 = r2*r2     r6 = r4*r2
+ *        rad = (((1 + k1*r2) + k2*r4) + k3*r6) / (((1 + k4*r2) + k5*r4) + k6*r6)
+ *        tx = 2*x   ty = 2*y   a1 = tx*y   a2 = r2 + tx*x   a3 = r2 + ty*y
+ *        xd = (x*rad + p1*a1) + p2*a2                    yd = (y*rad + p1*a3) + p2*a1
+ *        xs = (K_raw[0]*xd + K_raw[1]*yd) + K_raw[2]     ys = K_raw[4]*yd + K_raw[5]
+ *        inside = xs >= 0 && ys >= 0 && xs < (float)(raw_width - 1) && ys < (float)(raw_height - 1)
+ *      `inside` has the bounds bilinearInterp asserts in the reference (utils/image_utils.h:233-236); a NaN or an infinity
+ *      fails it by itself.  It is decided before any conversion to an integer and before any address is formed.  An outside
+ *      pixel is 0 and is counted in n_outside.  An inside pixel has x0 = (int)xs, y0 = (int)ys, dx = xs - x0, dy = ys - y0
+ *      and the reference's weights (bilinearWeights, image_utils.h:199-214):
+ *        w11 = dx*dy    w01 = dx - w11    w10 = dy - w11    w00 = ((1 - dx) - dy) + w11
+ *      over the grey g of its four taps, g00 at (x0, y0), g01 at (x0 + 1, y0), g10 at (x0, y0 + 1), g11 at (x0 + 1, y0 + 1):
+ *        value = ((w00*g00 + w01*g01) + w10*g10) + w11*g11       stored as (uint8_t)(int)(value + 0.5f)
+ *   UNPINNED: cv::undistort interpolates in fixed point (INTER_BITS = 5) from a map it builds in double, so neither the map
+ *      nor the rounding above equals OpenCV's to the bit, and the grey coefficients are restated, not checked against OpenCV.
+ *   OUT OF SCOPE: the fisheye (equidistant) model needs atan, which a host checker and the device do not reproduce bit for
+ *      bit; a rectifying rotation (cv::initUndistortRectifyMap's R); tilted-sensor and thin-prism terms. */
+enum { FLAME_STEREO_FMT_GREY8 = 0, FLAME_STEREO_FMT_BGR8 = 1, FLAME_STEREO_FMT_RGB8 = 2, FLAME_STEREO_FMT_BGRA8 = 3,
+       FLAME_STEREO_FMT_RGBA8 = 4 };
+
+typedef struct flame_stereo_input_params {
+  int32_t format;                /* one of the above */
+  int32_t remap;                 /* 0: raw is rectified already and has the camera's size; 1: undistort / resize */
+  int32_t raw_width, raw_height; /* >= 2 each */
+  float K_raw[9];                /* the raw camera, row-major; [0] [1] [2] [4] [5] are read */
+  float dist[8];                 /* k1 k2 p1 p2 k3 k4 k5 k6, OpenCV's order (radial-tangential + rational) */
+} flame_stereo_input_params;
+
+typedef struct flame_stereo_input_stats {
+  int32_t n_outside;             /* rectified pixels that have no source in the raw frame (written as 0) */
+} flame_stereo_input_stats;
+
+/* GREY8, remap 0, sizes 0, K_raw = I, dist = 0. */
+void flame_stereo_default_input_params(flame_stereo_input_params* p);
+/* What the raw frames look like.  After set_camera; set_camera forgets it.  FLAME_NLTGV2_ERR_NO_GRAPH without a camera;
+ * FLAME_NLTGV2_ERR_INVALID_ARG for an unknown format, a raw dimension below 2 or above 16384, a remap other than 0 or 1, or
+ * remap == 0 with a raw size other than the camera's; the input set before stays as it was then. */
+int flame_stereo_set_input(flame_stereo_ctx* ctx, const flame_stereo_input_params* p);
+/* Adds (or replaces) resident frame `frame_id` from a raw frame of raw_height rows of row_stride_bytes bytes, the first
+ * raw_width * bytes_per_pixel of each being pixels; neither `raw` nor the stride needs any alignment.
+ *   raw_on_device == 0: `raw` is host memory.  It is staged through a device buffer the context owns, and the call waits for
+ *      the stream, as flame_stereo_add_frame does (the source is pageable memory).
+ *   raw_on_device != 0: `raw` is device memory, read in place.  With stats == NULL the call only enqueues on the context's
+ *      stream and returns: no copy, no allocation once the frame's buffers exist (flame_stereo_drop_frame hands them on), no
+ *      wait.  THE CALLER keeps `raw` alive and unchanged until the context's stream has passed the call, and orders the work
+ *      that produces `raw` before it: either by producing it on the stream given to flame_stereo_set_stream, or by waiting
+ *      for its own stream before the call.  With stats != NULL the call waits once and fills `stats`.
+ * FLAME_NLTGV2_ERR_NO_GRAPH when no camera is set; FLAME_NLTGV2_ERR_INVALID_ARG without flame_stereo_set_input since the last
+ * set_camera, for raw == NULL, or for row_stride_bytes < raw_width * bytes_per_pixel.  A call that fails these checks leaves
+ * flame_stereo_frame_count and every resident frame as they were.  flame_stereo_last_kernel_ms covers its two kernels. */
+int flame_stereo_add_raw_frame(flame_stereo_ctx* ctx, uint32_t frame_id, const void* raw, int row_stride_bytes,
+                               int raw_on_device, flame_stereo_input_stats* stats);
 /* Copies a resident frame's derived images back ((height + 2 border) x (width + 2 border) each; any may be NULL). */
 int flame_stereo_download_frame(flame_stereo_ctx* ctx, uint32_t frame_id, uint8_t* img_pad, float* gradx_pad,
                                 float* grady_pad);
