@@ -791,8 +791,21 @@ __global__ __launch_bounds__(64) void k_update_feature_idepths(
 
 
 
+// cv::borderInterpolate(BORDER_REFLECT_101) of a coordinate that one reflection left outside [0, len): the reference repeats
+// p < 0 -> -p, p >= len -> 2 (len - 1) - p until p is inside, which is this closed form.  The map is even (p and -p meet the
+// same pixel) and has the period 2 (len - 1), and on one period it is m for m < len and period - m behind it.  len >= 2
+// (set_camera), so the period is at least 2.
+__device__ __forceinline__ int reflect_101_far(int p, int len) {
+  const int period = 2 * (len - 1);
+  const int m = (p < 0 ? -p : p) % period;
+  return m < len ? m : period - m;
+}
+
 // utils::Frame::create level 0: img_pad = copyMakeBorder(REFLECT_101), grad*_pad = copyMakeBorder(
 // getCentralGradient(img), CONSTANT 0).  The differences of two bytes (and their halves) are exact in float.
+// A border below the frame's size needs one reflection, which every lane takes branch-free; set_camera allows a border of 64
+// on a frame of 2, and only the lanes that one reflection leaves outside (border >= len on the right and bottom, border >
+// 2 (len - 1) on the left and top) take the closed form, so a frame wider than its border never enters it.
 __global__ __launch_bounds__(256) void k_frame_pad_gradient(const uint8_t* __restrict__ img, int width, int height,
                                                             int border, uint8_t* __restrict__ img_pad,
                                                             float* __restrict__ gx_pad, float* __restrict__ gy_pad) {
@@ -815,6 +828,8 @@ __global__ __launch_bounds__(256) void k_frame_pad_gradient(const uint8_t* __res
   if (sx >= width) sx = 2 * (width - 1) - sx;
   if (sy < 0) sy = -sy;
   if (sy >= height) sy = 2 * (height - 1) - sy;
+  if ((unsigned)sx >= (unsigned)width) sx = reflect_101_far(sx, width);
+  if ((unsigned)sy >= (unsigned)height) sy = reflect_101_far(sy, height);
   const size_t o = (size_t)y * pw + x;
   img_pad[o] = img[(size_t)sy * width + sx];
   gx_pad[o] = gx;

@@ -118,8 +118,11 @@ int flame_stereo_set_camera(flame_stereo_ctx* ctx, const float K[9], const float
 /* (drop_frame hands the frame's buffers to the next add_frame; at most 4 sets wait there, the rest is freed.)  */
 /* utils::Frame::create, level 0 (frame.cc:33-71): uploads the width x height 8-bit image and builds, on the
  * device, img_pad (cv::BORDER_REFLECT_101) and gradx_pad / grady_pad (getCentralGradient, image_utils.h:425-470,
- * then cv::BORDER_CONSTANT 0).  The frame stays resident until dropped (a pose-frame is read by every later
- * frame); adding an existing id replaces it. */
+ * then cv::BORDER_CONSTANT 0).  BORDER_REFLECT_101 is cv::borderInterpolate's rule, per axis of length len: a source
+ * coordinate p outside [0, len) becomes -p where p < 0 and 2 (len - 1) - p where p >= len, REPEATED until it lies inside.
+ * set_camera relates border to neither width nor height, so a border of len or more (up to 64 on a frame of 2) takes
+ * several rounds; the result has the period 2 (len - 1) in p.  The frame stays resident until dropped (a pose-frame is
+ * read by every later frame); adding an existing id replaces it. */
 int flame_stereo_add_frame(flame_stereo_ctx* ctx, uint32_t frame_id, const uint8_t* img, int row_stride_bytes);
 int flame_stereo_drop_frame(flame_stereo_ctx* ctx, uint32_t frame_id);
 int flame_stereo_frame_count(const flame_stereo_ctx* ctx);

@@ -809,19 +809,25 @@ long stereo_update_feature_idepths(const stereo_params* P, const float* K, const
                                               new_grady_pad, curr_pf_id, n, feats, stats, 0);
 }
 
-/* utils::Frame::create, level 0 (frame.cc:33-71): padded image (BORDER_REFLECT_101) and padded central
- * gradients (BORDER_CONSTANT 0).  getCentralGradient<uint8_t,float>: image_utils.h:425-470. */
+/* cv::borderInterpolate(p, len, BORDER_REFLECT_101) for len >= 2: reflect until p lies in [0, len).  A border wider than the
+ * frame needs more than one round (two rounds take 2 (len - 1) >= 2 off a p that is still too large, so the loop ends). */
+static int reflect_101(int p, int len) {
+  while (p < 0 || p >= len) {
+    if (p < 0) p = -p;
+    else p = 2 * (len - 1) - p;
+  }
+  return p;
+}
+
+/* utils::Frame::create, level 0 (frame.cc:33-71): padded image (BORDER_REFLECT_101, reflected as often as the border
+ * needs) and padded central gradients (BORDER_CONSTANT 0).  getCentralGradient<uint8_t,float>: image_utils.h:425-470. */
 void stereo_make_frame(const uint8_t* img, int width, int height, int border, uint8_t* img_pad, float* gradx_pad,
                        float* grady_pad) {
   const int pw = width + 2 * border, ph = height + 2 * border;
   for (int y = 0; y < ph; ++y) {
-    int sy = y - border;
-    if (sy < 0) sy = -sy;
-    if (sy >= height) sy = 2 * (height - 1) - sy;
+    const int sy = reflect_101(y - border, height);
     for (int x = 0; x < pw; ++x) {
-      int sx = x - border;
-      if (sx < 0) sx = -sx;
-      if (sx >= width) sx = 2 * (width - 1) - sx;
+      const int sx = reflect_101(x - border, width);
       img_pad[(long)y * pw + x] = img[(long)sy * width + sx];
     }
   }
