@@ -53,8 +53,17 @@ class FrameRef(C.Structure):
                 ("q_to_pf", C.c_float * 4), ("t_to_pf", C.c_float * 3)]
 
 
-# columns of the optional walk trace (stereo_oracle.c, line_match_walk); a row of -1 = the match was never reached
-TRACE_COLS = ("steps", "c_best", "c_second", "n_ties", "tie16", "second_eq_best", "subpixel", "match_rc")
+# columns of the optional trace (stereo_oracle.c): eight of the walk (line_match_walk; -1 in all = the match was never
+# reached), then three of the per-feature driver
+TRACE_COLS = ("steps", "c_best", "c_second", "n_ties", "tie16", "second_eq_best", "subpixel", "match_rc",
+              "stage", "fail_bits", "forced_one")
+# values of the "stage" column (the STAGE_* enum of stereo_oracle.c); -1 = reference assert / unknown frame / behind one
+STAGES = ("baseline skip", "predict no", "moved", "move failed: predict", "move failed: rectangle",
+          "no region: empty idepth window", "no region: zero length", "no region: first clip",
+          "no region: zero length after the clip", "no region: second clip", "outside the valid rectangle",
+          "search status 1", "search status 2", "search status 3", "meas: disp < 1e-3", "meas: mu < 0",
+          "meas: gnorm < 1e-3", "meas: |edn| < 1e-3", "outlier", "updated, prior > 0", "updated, prior <= 0")
+STAGE = {n: i for i, n in enumerate(STAGES)}
 
 _READY = False
 
@@ -105,6 +114,10 @@ def lib():
         L.stereo_line_match.restype = C.c_int
         L.stereo_make_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, _FP, _FP]
         L.stereo_make_frame.restype = None
+        L.stereo_predict.argtypes = [GP, f, f, f, f, f, _FP, _FP, _FP, _FP]
+        L.stereo_predict.restype = C.c_int
+        L.stereo_meas_idepth.argtypes = [C.POINTER(Params), GP, _FP, _FP, C.c_int, C.c_int, C.c_int, f, f, f, f, _FP, _FP]
+        L.stereo_meas_idepth.restype = C.c_int
         _READY = True
     return L
 
@@ -197,6 +210,23 @@ def fuse(mu_pred, var_pred, mu_meas, var_meas, thresh=2.0):
     return bool(rc), np.float32(a.value), np.float32(b.value)
 
 
+def predict(g, process_var_factor, ux, uy, mu, var):
+    """inverse_depth_filter::predict: (rc, u_cmp.x, u_cmp.y, mu_pred, var_pred); rc 0 ok, 1 behind the camera, -1 assert."""
+    v = [C.c_float() for _ in range(4)]
+    rc = lib().stereo_predict(C.byref(g), process_var_factor, ux, uy, mu, var, *[C.byref(x) for x in v])
+    return (int(rc),) + tuple(np.float32(x.value) for x in v)
+
+
+def meas_idepth(params: Params, g, gradx_pad, grady_pad, ux, uy, cx, cy):
+    """InverseDepthMeasModel::idepth on padded gradient images: (rc, mu, var); rc 1 ok, 0 no measurement, -1 assert."""
+    gx, gy = np.ascontiguousarray(gradx_pad, np.float32), np.ascontiguousarray(grady_pad, np.float32)
+    rows, cols = gx.shape
+    mu, var = C.c_float(), C.c_float()
+    rc = lib().stereo_meas_idepth(C.byref(params), C.byref(g), _fp(gx), _fp(gy), rows, cols, cols, ux, uy, cx, cy,
+                                  C.byref(mu), C.byref(var))
+    return int(rc), np.float32(mu.value), np.float32(var.value)
+
+
 def make_frame(img: np.ndarray, border: int):
     """Frame::create level 0: (img_pad u8, gradx_pad f32, grady_pad f32), each (H+2b) x (W+2b)."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
@@ -231,7 +261,7 @@ def line_match(params: Params, rescale_factor, ref_patch, img_pad, sx, sy, ex, e
 
 def update_feature_idepths(params: Params, K, Kinv, width, height, pad, frames, new_frame, curr_pf_id, feats, trace=None):
     """frames: list of dicts {id, img_pad, q_to_new, t_to_new, q_to_pf, t_to_pf}; new_frame = (img_pad, gradx_pad,
-    grady_pad).  `feats` (FEATURE_DTYPE) is updated in place.  `trace`: None, or a C-contiguous int32 [n, 8] array that
+    grady_pad).  `feats` (FEATURE_DTYPE) is updated in place.  `trace`: None, or a C-contiguous int32 [n, 11] array that
     receives one row of TRACE_COLS per feature (outputs are the same bits either way).  Returns (rc, stats[7])."""
     if trace is not None:
         assert trace.dtype == np.int32 and trace.flags.c_contiguous and trace.shape == (feats.shape[0], len(TRACE_COLS))

@@ -20,7 +20,10 @@
  * getCentralGradient by :171-326 (ramp images).  Everything else here (predict, search
  * region, line search, measurement model, fusion, the per-feature driver) has NO reference test and the
  * reference translation units cannot be built in this image (Eigen, Sophus and OpenCV are absent and
- * stand-in headers are not allowed): PARITY UNPINNED for those parts.
+ * stand-in headers are not allowed): PARITY UNPINNED for those parts.  They are cross-checked against float64
+ * restatements written from the formulas, decision by decision and value by value within float32 roundoff bounds: the
+ * walk in tests/test_stereo_walk_edges.py, the stages around it (predict, search region, rectangle, gradient gate,
+ * measurement model, fusion, fail_feature) in tests/test_stereo_update_edges.py.
  *
  * Third-party semantics restated (dependencies of the reference that are not vendored):
  *   Eigen 3 (find_package(Eigen3) in the reference's cmake/setup):
@@ -355,9 +358,16 @@ int stereo_predict(const stereo_geometry* g, float process_var_factor, float ux,
   return 0;
 }
 
-/* inverse_depth_filter.cc:64-176; 1 = region found, 0 = none, -1 = reference assert */
-int stereo_search_region(const stereo_params* P, const stereo_geometry* g, int width, int height, float ux, float uy,
-                         float mu, float var, float* sx, float* sy, float* ex, float* ey, float* epx, float* epy) {
+/* inverse_depth_filter.cc:64-176; 1 = region found, 0 = none, -1 = reference assert.
+ * `why`: NULL, or receives which of the five "no region" exits was taken (0..4 in source order; unchanged otherwise). */
+static int search_region_why(const stereo_params* P, const stereo_geometry* g, int width, int height, float ux, float uy,
+                             float mu, float var, float* sx, float* sy, float* ex, float* ey, float* epx, float* epy,
+                             int* why) {
+#define NO_REGION(k)    \
+  do {                  \
+    if (why) *why = (k); \
+    return 0;           \
+  } while (0)
   float id_min = P->idepth_min, id_max = P->idepth_max;
   if (!isnan(mu) && !isnan(var)) {
     const float sigma = sqrtf(var);
@@ -366,23 +376,23 @@ int stereo_search_region(const stereo_params* P, const stereo_geometry* g, int w
   }
   id_min = (id_min < P->idepth_min) ? P->idepth_min : id_min;
   id_max = (id_max > P->idepth_max) ? P->idepth_max : id_max;
-  if (id_max < id_min) return 0;
+  if (id_max < id_min) NO_REGION(0);
   float ax, ay, bx, by;
   if (stereo_project(g, ux, uy, id_min, &ax, &ay)) return -1;
   if (stereo_project(g, ux, uy, id_max, &bx, &by)) return -1;
   float dx = bx - ax, dy = by - ay;
   float epilength = sqrtf(dx * dx + dy * dy);
-  if (epilength <= 0) return 0;
+  if (epilength <= 0) NO_REGION(1);
   const float epix = dx / epilength, epiy = dy / epilength;
   *epx = epix, *epy = epiy;
   const float xmin = 1.0f, ymin = 1.0f, xmax = (float)(1 + width - 2), ymax = (float)(1 + height - 2);
   if (isnan(ax) || isnan(ay) || isnan(bx) || isnan(by)) return -1;
   float cax, cay, cbx, cby;
-  if (!stereo_clip_liang_barsky(xmin, xmax, ymin, ymax, ax, ay, bx, by, &cax, &cay, &cbx, &cby)) return 0;
+  if (!stereo_clip_liang_barsky(xmin, xmax, ymin, ymax, ax, ay, bx, by, &cax, &cay, &cbx, &cby)) NO_REGION(2);
   ax = cax, ay = cay, bx = cbx, by = cby;
   dx = bx - ax, dy = by - ay;
   epilength = sqrtf(dx * dx + dy * dy);
-  if (epilength <= 0) return 0;
+  if (epilength <= 0) NO_REGION(3);
   if (epilength < P->epilength_min) {
     const float pad = (P->epilength_min - epilength) / 2.0f;
     ax -= epix * pad, ay -= epiy * pad;
@@ -393,9 +403,15 @@ int stereo_search_region(const stereo_params* P, const stereo_geometry* g, int w
     bx = ax + epix * epilength, by = ay + epiy * epilength;
   }
   if (isnan(ax) || isnan(ay) || isnan(bx) || isnan(by)) return -1;
-  if (!stereo_clip_liang_barsky(xmin, xmax, ymin, ymax, ax, ay, bx, by, &cax, &cay, &cbx, &cby)) return 0;
+  if (!stereo_clip_liang_barsky(xmin, xmax, ymin, ymax, ax, ay, bx, by, &cax, &cay, &cbx, &cby)) NO_REGION(4);
+#undef NO_REGION
   *sx = cax, *sy = cay, *ex = cbx, *ey = cby;
   return 1;
+}
+
+int stereo_search_region(const stereo_params* P, const stereo_geometry* g, int width, int height, float ux, float uy,
+                         float mu, float var, float* sx, float* sy, float* ex, float* ey, float* epx, float* epy) {
+  return search_region_why(P, g, width, height, ux, uy, mu, var, sx, sy, ex, ey, epx, epy, 0);
 }
 
 /* ---- walk trace (optional, off unless a caller passes rows to stereo_update_feature_idepths_traced) ------------
@@ -407,8 +423,28 @@ int stereo_search_region(const stereo_params* P, const stereo_geometry* g, int w
  *   [4] 1 when one of those lies a multiple of 16 steps after the best
  *   [5] 1 when second_err == best_err
  *   [6] sub-pixel branch: 0 none, 1 pre, 2 post
- *   [7] the match's return value (0 success, 1 ambiguous, 2 max cost, -1 reference assert) */
-#define STEREO_TRACE_COLS 8
+ *   [7] the match's return value (0 success, 1 ambiguous, 2 max cost, -1 reference assert)
+ * and three columns written by the per-feature driver (stereo_update_feature_idepths_traced), for every feature:
+ *   [8] the exit the feature took, a STAGE_* code (-1: a reference assert, an unknown frame id, or a feature behind one)
+ *   [9] fail_feature: bit 0 = invalidated for idepth_var_max, bit 1 = invalidated for max_dropouts (0: not failed or kept)
+ *   [10] variance factor forced to 1: bit 0 = by predict into the new frame (mu < 1e-6), bit 1 = on the move to the newest
+ *        pose-frame (idepth_pf < 1e-6) */
+#define STEREO_WALK_COLS 8
+#define STEREO_TRACE_COLS 11
+enum {
+  STAGE_BASELINE_SKIP = 0,
+  STAGE_PREDICT_NO = 1,
+  STAGE_MOVED = 2,
+  STAGE_MOVE_FAILED_PREDICT = 3,
+  STAGE_MOVE_FAILED_RECT = 4,
+  STAGE_NO_REGION = 5, /* 5..9: empty idepth window, zero length, first clip, zero length after it, second clip */
+  STAGE_OUTSIDE_RECT = 10,
+  STAGE_SEARCH_STATUS_1 = 11, /* 11..13: search status 1, 2, 3 */
+  STAGE_MEAS = 14,            /* 14..17: disp < 1e-3, mu < 0, gnorm < 1e-3, |edn| < 1e-3 */
+  STAGE_OUTLIER = 18,
+  STAGE_UPDATED = 19,         /* prior > 0 */
+  STAGE_UPDATED_NO_PRIOR = 20 /* prior <= 0 (or NaN): the measurement replaces it */
+};
 int stereo_trace_cols(void) { return STEREO_TRACE_COLS; }
 
 /* line_stereo.h:73-385.  Returns 0 success, 1 ambiguous, 2 max cost, -1 reference assert (sample outside image).
@@ -538,7 +574,7 @@ static int line_match_traced(const stereo_params* P, float rescale_factor, const
                              int rows, int cols, int step, float sx, float sy, float ex, float ey, float* mx, float* my,
                              float* residual, int32_t* tr) {
   if (tr) {
-    for (int k = 0; k < STEREO_TRACE_COLS; ++k) tr[k] = 0;
+    for (int k = 0; k < STEREO_WALK_COLS; ++k) tr[k] = 0;
     tr[1] = tr[2] = -1;
   }
   const int r = line_match_walk(P, rescale_factor, ref_patch, img, rows, cols, step, sx, sy, ex, ey, mx, my, residual, tr);
@@ -608,18 +644,22 @@ int stereo_fuse(float mu_pred, float var_pred, float mu_meas, float var_meas, fl
 }
 
 /* inverse_depth_meas_model.cc:48-154; 1 ok, 0 no measurement, -1 reference assert.
- * gradx/grady: padded gradient images of the comparison frame, `gstep` floats per row, grows x gcols. */
-int stereo_meas_idepth(const stereo_params* P, const stereo_geometry* g, const float* gradx, const float* grady,
-                       int grows, int gcols, int gstep, float ux, float uy, float cx, float cy, float* mu, float* var) {
+ * gradx/grady: padded gradient images of the comparison frame, `gstep` floats per row, grows x gcols.
+ * `why`: NULL, or receives which of the four "no measurement" exits was taken (0..3 in source order). */
+static int meas_idepth_why(const stereo_params* P, const stereo_geometry* g, const float* gradx, const float* grady,
+                           int grows, int gcols, int gstep, float ux, float uy, float cx, float cy, float* mu, float* var,
+                           int* why) {
   float ix, iy, ex, ey, disp;
   if (stereo_disparity(g, ux, uy, cx, cy, &ix, &iy, &ex, &ey, &disp)) return -1;
   if ((double)disp < 1e-3) {
     *mu = 0.0f, *var = 1e10f;
+    if (why) *why = 0;
     return 0;
   }
   *mu = stereo_disparity_to_idepth(g, ux, uy, ix, iy, ex, ey, disp);
   if (*mu < 0.0f) {
     *mu = 0.0f, *var = 1e10f;
+    if (why) *why = 1;
     return 0;
   }
   const float off = (float)(P->z_win_size / 2 + 1);
@@ -629,6 +669,7 @@ int stereo_meas_idepth(const stereo_params* P, const stereo_geometry* g, const f
   const float gnorm = sqrtf(gx * gx + gy * gy);
   if ((double)gnorm < 1e-3) {
     *mu = 0.0f, *var = 1e10f;
+    if (why) *why = 2;
     return 0;
   }
   const float ngx = gx / gnorm, ngy = gy / gnorm;
@@ -636,6 +677,7 @@ int stereo_meas_idepth(const stereo_params* P, const stereo_geometry* g, const f
   const float geo_var = P->epipolar_line_var / (edn * edn);
   if ((double)((edn > 0) ? edn : -edn) < 1e-3) {
     *mu = 0.0f, *var = 1e10f;
+    if (why) *why = 3;
     return 0;
   }
   const float edg = gx * ex + gy * ey;
@@ -648,6 +690,11 @@ int stereo_meas_idepth(const stereo_params* P, const stereo_geometry* g, const f
   if (isnan(meas_var) || isinf(meas_var)) return -1;
   *var = meas_var;
   return 1;
+}
+
+int stereo_meas_idepth(const stereo_params* P, const stereo_geometry* g, const float* gradx, const float* grady,
+                       int grows, int gcols, int gstep, float ux, float uy, float cx, float cy, float* mu, float* var) {
+  return meas_idepth_why(P, g, gradx, grady, grows, gcols, gstep, ux, uy, cx, cy, mu, var, 0);
 }
 
 /* cv::Rect(x, y, w, h).contains(Point2f): the point converts to Point2i by cvRound (round half to even) */
@@ -667,11 +714,19 @@ typedef struct stereo_frame_ref {
 static int track_feature(const stereo_params* P, const float* K, const float* Kinv, const stereo_frame_ref* fr,
                          const stereo_geometry* epigeo, int width, int height, int pad, const uint8_t* new_img_pad,
                          uint32_t curr_pf_id, stereo_feature* f, float* flow_x, float* flow_y, int32_t* tr) {
+#define STAGE(k) \
+  do {           \
+    if (tr) tr[8] = (k); \
+  } while (0)
   float ucx, ucy, idepth_cmp, var_cmp;
   const int pr = stereo_predict(epigeo, P->process_var_factor, f->x, f->y, f->idepth_mu, f->idepth_var, &ucx, &ucy,
                                 &idepth_cmp, &var_cmp);
   if (pr < 0) return -1;
-  if (pr != 0) return 0;
+  if (pr != 0) {
+    STAGE(STAGE_PREDICT_NO);
+    return 0;
+  }
+  if (tr) tr[10] = ((double)f->idepth_mu < 1e-6) ? 1 : 0;
   int row_offset = 0;
   if (P->do_letterbox) row_offset = height / 3;
   const int border = (int)(P->rescale_factor_max * P->win_size / 2 + 1);
@@ -687,6 +742,7 @@ static int track_feature(const stereo_params* P, const float* K, const float* Ki
                                   &idepth_pf, &var_pf);
     if (mr < 0) return -1;
     if (mr != 0 || !rect_contains(vx, vy, vw, vh, upx, upy)) {
+      STAGE(mr != 0 ? STAGE_MOVE_FAILED_PREDICT : STAGE_MOVE_FAILED_RECT);
       f->valid = 0;
       return 0;
     }
@@ -697,47 +753,66 @@ static int track_feature(const stereo_params* P, const float* K, const float* Ki
     float v4 = idepth_pf / old;
     v4 *= v4;
     v4 *= v4;
-    if ((double)idepth_pf < 1e-6) v4 = 1;
+    if ((double)idepth_pf < 1e-6) {
+      v4 = 1;
+      if (tr) tr[10] |= 2;
+    }
     f->idepth_var *= v4;
+    STAGE(STAGE_MOVED);
     return 0;
   }
   float sx, sy, ex, ey, epx, epy;
-  const int sr = stereo_search_region(P, epigeo, width, height, f->x, f->y, f->idepth_mu, f->idepth_var, &sx, &sy, &ex,
-                                      &ey, &epx, &epy);
+  int why = 0;
+  const int sr = search_region_why(P, epigeo, width, height, f->x, f->y, f->idepth_mu, f->idepth_var, &sx, &sy, &ex, &ey,
+                                   &epx, &epy, &why);
   if (sr < 0) return -1;
-  if (sr == 0) return 0;
+  if (sr == 0) {
+    STAGE(STAGE_NO_REGION + why);
+    return 0;
+  }
   const float off = (float)pad;
-  if (!rect_contains(vx, vy, vw, vh, f->x, f->y)) return 0;
+  if (!rect_contains(vx, vy, vw, vh, f->x, f->y)) {
+    STAGE(STAGE_OUTSIDE_RECT);
+    return 0;
+  }
   float mx = ucx, my = ucy;
   const int rows = height + 2 * pad, cols = width + 2 * pad;
   const int st = search_traced(P, epigeo, rescale, fr->img_pad, new_img_pad, rows, cols, cols, f->x + off, f->y + off,
                                sx + off, sy + off, ex + off, ey + off, &mx, &my, tr);
   if (st < 0) return -1;
   f->search_status = st;
-  if (st != 0) return 0;
+  if (st != 0) {
+    STAGE(STAGE_SEARCH_STATUS_1 + st - 1);
+    return 0;
+  }
   *flow_x = mx - off, *flow_y = my - off;
   return 1;
+#undef STAGE
 }
 
-static void fail_feature(const stereo_params* P, stereo_feature* f, int32_t* stats) {
+static void fail_feature(const stereo_params* P, stereo_feature* f, int32_t* stats, int32_t* tr) {
+  int bits = 0;
   f->idepth_var *= P->process_fail_var_factor;
   if (f->idepth_var > P->idepth_var_max) {
     f->valid = 0;
     ++stats[1];
+    bits |= 1;
   }
   f->num_dropouts++;
   if (f->num_dropouts > (uint32_t)P->max_dropouts) {
     f->valid = 0;
     ++stats[2];
+    bits |= 2;
   }
+  if (tr) tr[9] = bits;
 }
 
 /* flame.cc:1280-1536.  stats[0..5] = num_idepth_updates, num_fail_max_var, num_fail_max_dropouts,
  * num_fail_ref_patch_grad, num_fail_ambiguous_match, num_fail_max_cost; stats[6] = the function's bool.
  * Returns 0, -(1 + i) when feature i hits a reference assert, or 1 + i when its frame id is unknown
  * (pfs.at() would throw).
- * `trace`: NULL, or n rows of STEREO_TRACE_COLS int32 (see line_match_walk); every row is written, also those of
- * the features behind an early return. */
+ * `trace`: NULL, or n rows of STEREO_TRACE_COLS int32 (see line_match_walk and the STAGE_* codes); every row is written,
+ * also those of the features behind an early return. */
 long stereo_update_feature_idepths_traced(const stereo_params* P, const float* K, const float* Kinv, int width,
                                           int height, int pad, int n_frames, const stereo_frame_ref* frames,
                                           const uint8_t* new_img_pad, const float* new_gradx_pad,
@@ -760,33 +835,41 @@ long stereo_update_feature_idepths_traced(const stereo_params* P, const float* K
     stereo_load_geometry(&epigeo, K, Kinv, fr->q_to_new, fr->t_to_new);
     const float* t = fr->t_to_new;
     const float baseline = sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
-    if (baseline < P->min_baseline) continue;
+    int32_t* row = trace ? trace + (long)i * STEREO_TRACE_COLS : 0;
+    if (baseline < P->min_baseline) {
+      if (row) row[8] = STAGE_BASELINE_SKIP, row[9] = 0, row[10] = 0;
+      continue;
+    }
+    if (row) row[9] = 0, row[10] = 0;
     float flow_x = 0, flow_y = 0;
-    const int tr = track_feature(P, K, Kinv, fr, &epigeo, width, height, pad, new_img_pad, curr_pf_id, f, &flow_x, &flow_y,
-                                 trace ? trace + (long)i * STEREO_TRACE_COLS : 0);
+    const int tr = track_feature(P, K, Kinv, fr, &epigeo, width, height, pad, new_img_pad, curr_pf_id, f, &flow_x, &flow_y, row);
     if (tr < 0) return -(1 + (long)i);
     if (f->search_status == 1) ++stats[3];
     else if (f->search_status == 2) ++stats[4];
     else if (f->search_status == 3) ++stats[5];
     if (tr == 0) {
-      fail_feature(P, f, stats);
+      fail_feature(P, f, stats, row);
       continue;
     }
     /* the measurement model reloads the same geometry from the frame the feature belongs to (flame.cc:1381-1383) */
     float mu_meas, var_meas;
-    const int sr = stereo_meas_idepth(P, &epigeo, new_gradx_pad, new_grady_pad, rows, cols, cols, f->x, f->y, flow_x,
-                                      flow_y, &mu_meas, &var_meas);
+    int why = 0;
+    const int sr = meas_idepth_why(P, &epigeo, new_gradx_pad, new_grady_pad, rows, cols, cols, f->x, f->y, flow_x, flow_y,
+                                   &mu_meas, &var_meas, &why);
     if (sr < 0) return -(1 + (long)i);
     if (sr == 0) {
-      fail_feature(P, f, stats);
+      if (row) row[8] = STAGE_MEAS + why;
+      fail_feature(P, f, stats, row);
       continue;
     }
     float mu_post, var_post;
     if (!stereo_fuse(f->idepth_mu, f->idepth_var, mu_meas, var_meas, &mu_post, &var_post, P->outlier_sigma_thresh)) {
-      fail_feature(P, f, stats);
+      if (row) row[8] = STAGE_OUTLIER;
+      fail_feature(P, f, stats, row);
       continue;
     }
     if (isnan(mu_post) || isnan(var_post) || !(var_post >= 0)) return -(1 + (long)i);
+    if (row) row[8] = (!isnan(f->idepth_mu) && f->idepth_mu > 0.0f) ? STAGE_UPDATED : STAGE_UPDATED_NO_PRIOR;
     if (P->do_meas_fusion) {
       f->idepth_mu = mu_post, f->idepth_var = var_post;
     } else {

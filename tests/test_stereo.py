@@ -555,25 +555,65 @@ def test_gpu_feature_move_to_newest_poseframe(built):
     assert np.all(out["num_dropouts"][moved] == 1)
 
 
-@gpu
-def test_gpu_edge_case_features(built):
+def _edge_case_features():
+    """The inputs of test_gpu_edge_case_features, and the proof from the checker's trace (stage, fail_bits, forced_one;
+    oracle/stereo_oracle.c) that every group reaches the exit its comment names."""
     sc, imgs, feats, poses = _scene_case(320, 240, 300, seed=8)
     f = feats.copy()
     n = f.shape[0]
     f["idepth_mu"][0:20] = 0.0                      # maxDepthProjection path, var_factor4 = 1
-    f["idepth_var"][20:40] = 0.24                   # fails push the variance past idepth_var_max
-    f["num_dropouts"][40:60] = 5                    # one more dropout invalidates
-    f["x"][60:70] = 2.0                             # outside the valid region (flame.cc:1677)
-    f["y"][70:80] = 238.5
+    f["idepth_var"][20:40] = 0.24                   # fails push the variance past idepth_var_max ...
+    f["idepth_mu"][20:40] = 5.0                     # ... and an idepth window above idepth_max makes them fail
+    f["num_dropouts"][40:60] = 5                    # one more dropout invalidates ...
+    f["idepth_mu"][40:60] = 5.0                     # ... when the feature fails
+    f["x"][60:70] = 317.0                           # outside the valid region (flame.cc:1677), inside the search box
+    f["y"][70:80] = 236.5                           # (a tie: rounds to 236, the first row outside)
+    f["x"][70:80] = 60.0 + 20.0 * np.arange(10)     # ... where the segment, which runs to the left, stays in the box
     f["idepth_mu"][80:100] *= 3.0                   # far off priors: outliers / failed matches
     f["idepth_var"][100:120] = 1e-6                 # tiny variance: search region padded to epilength_min
     f["idepth_var"][120:140] = 0.0                  # zero variance: empty search segment
-    f["search_status"][140:160] = 2                 # stale status of a previous frame is counted again
+    f["search_status"][140:160] = 2                 # stale status of a previous frame is counted again ...
+    f["idepth_var"][140:160] = 0.0                  # ... when the feature does not get as far as the search
     f["idepth_mu"][160:170] = 1e-7                  # mu < 1e-6
     f["idepth_mu"][170:180] = 5.0                   # beyond idepth_max: empty search interval
     assert n > 180
+    frames = [dict(p, img_pad=so.make_frame(imgs[p["id"]], 5)[0]) for p in poses]
+    out = f.copy()
+    tr = np.zeros((n, len(so.TRACE_COLS)), np.int32)
+    rc, stats = so.update_feature_idepths(so.Params(), sc.K32, sc.Kinv32, sc.width, sc.height, 5, frames,
+                                          so.make_frame(imgs[12], 5), 11, out, trace=tr)
+    assert rc == 0
+    stage, fail, forced = (tr[:, so.TRACE_COLS.index(c)] for c in ("stage", "fail_bits", "forced_one"))
+    S = so.STAGE
+    assert (forced[0:20] == 1).all() and (forced[160:170] == 1).all() and (forced[20:160] == 0).all()
+    assert (stage[20:60] == S["no region: empty idepth window"]).all() and (stage[170:180] == S["no region: empty idepth window"]).all()
+    assert (fail[20:40] == 1).all() and (out["valid"][20:40] == 0).all()          # invalidated for the variance
+    assert (fail[40:60] == 2).all() and (out["valid"][40:60] == 0).all()          # invalidated for the dropouts
+    assert stats[1] == (fail & 1).sum() >= 20 and stats[2] == (fail >> 1).sum() >= 20
+    assert (stage[60:80] == S["outside the valid rectangle"]).all()
+    far_off = stage[80:100]
+    assert (far_off != S["updated, prior > 0"]).sum() >= 4 and ((far_off == S["outlier"]) | (far_off == S["search status 2"])
+                                                              | (far_off == S["search status 3"])).sum() >= 4, far_off
+    geos = {p["id"]: so.load_geometry(sc.K32, sc.Kinv32, p["q_to_new"], p["t_to_new"]) for p in poses}
+    for i in range(100, 120):    # padded: the segment is epilength_min long, its idepth window would give far less
+        r = so.search_region(so.Params(), geos[int(f["frame_id"][i])], sc.width, sc.height, f["x"][i], f["y"][i],
+                             f["idepth_mu"][i], f["idepth_var"][i])
+        assert r[0] == 1 and abs(math.hypot(r[3] - r[1], r[4] - r[2]) - 3.0) < 1e-3, (i, r)
+        assert stage[i] >= S["search status 1"]
+    assert (stage[120:160] == S["no region: zero length"]).all()
+    assert (out["search_status"][140:160] == 2).all() and stats[4] >= 20             # the stale status, counted again
+    return sc, imgs, f, poses
+
+
+def test_edge_case_features_reach_their_exits():
+    _edge_case_features()
+
+
+@gpu
+def test_gpu_edge_case_features(built):
+    sc, imgs, f, poses = _edge_case_features()
     st, out = _assert_same(sc, imgs, f, poses)
-    assert (out["valid"][20:60] == 0).any()
+    assert (out["valid"][20:60] == 0).all()
 
 
 @gpu
@@ -719,7 +759,9 @@ def test_gpu_randomized_differential(built, trial):
     else:
         assert rc_o == 0 and rc_g == 0, (rc_o, rc_g, st_g)
         assert out_g.tobytes() == out_o.tobytes()
-        assert st_g["num_idepth_updates"] == st_o[0] and st_g["num_fail_max_cost"] == st_o[5]
+        names = ("num_idepth_updates", "num_fail_max_var", "num_fail_max_dropouts", "num_fail_ref_patch_grad",
+                 "num_fail_ambiguous_match", "num_fail_max_cost", "success")
+        assert [st_g[k] for k in names] == [int(v) for v in st_o], (st_g, st_o)
 
 
 @gpu
