@@ -8,7 +8,11 @@ Layout:
 There is no CPU fallback in this package: without the HIP library / a GPU every compute call raises.
 """
 from .regularizer import (  # noqa: F401
+    MAP_ERROR_PHOTO,
+    MAP_ERROR_TRUTH,
     DebugImageParams,
+    MapErrorParams,
+    MapErrorStats,
     MeshFilterParams,
     MetricParams,
     NLTGV2Error,

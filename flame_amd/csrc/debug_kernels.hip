@@ -10,7 +10,8 @@
 //
 // drawWireframe is wireframe_kernels.hip, the matches picture matches_kernels.hip, drawDetections detections_kernels.hip; the
 // colour map and the pixel stores these files share are debug_pixel.hpp.
-// Not here (include/flame_nltgv2.h says why): cv::putText (debug_draw_text_overlay is taken as false), debug_draw_photo_error.
+// Not here (include/flame_nltgv2.h says why): cv::putText (debug_draw_text_overlay is taken as false).  debug_draw_photo_error is
+// map_error_kernels.hip.
 //
 // Streaming kernels: a thread owns four consecutive OUTPUT pixels, 12 bytes, and stores them as three dwords.
 #include <hip/hip_runtime.h>

@@ -10,7 +10,8 @@
 //   nltgv2_run.hip         which kernels run n steps (planner), enqueue / settle / roll back, the run entry points
 //   nltgv2_graph_capi.hip  graph in / out: upload, per-frame sync, projection, rescale, state download, costs, export
 //   nltgv2_frame_capi.hip  the rows around the solver that work on its device state: the dense map, the mesh outputs, the debug images and
-//                          the wireframe (begin / end stages on the side stream; their pure part: side_stage.hpp), photometric residual
+//                          the wireframe, the metric outputs, the map error (begin / end stages on the side stream; their pure part:
+//                          side_stage.hpp), photometric residual
 #ifndef FLAME_AMD_NLTGV2_CONTEXT_HPP_
 #define FLAME_AMD_NLTGV2_CONTEXT_HPP_
 
@@ -359,6 +360,18 @@ struct flame_nltgv2_ctx {
     bool cloud_fetched = false;       // _end has brought the n_points points to the host
     MetricLayout at{};
   } metric_pending;
+  // flame_nltgv2_map_error_begin / _end (map_error_kernels.hip): device outputs, pinned outputs and timing events of its own; the
+  // resident maps and the images of photo_set_images are only read.  Pinned: map_error_layout
+  DevBuf e_err, e_smooth, e_stats, e_partials, e_img, e_truth, e_gray;
+  SideStage merr;
+  bool merr_reads_images = false;     // the stage enqueued last reads img_ref / img_cmp on the side stream: photo_set_images waits for it
+  struct MapErrorPending {
+    int rows = 0, cols = 0, source = 0, win_size = 0;
+    float hist_scale = 0.0f;
+    MapErrorWants want{};
+    const void* err_device = nullptr;  // the (smoothed) error image
+    MapErrorLayout at{};
+  } merr_pending;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

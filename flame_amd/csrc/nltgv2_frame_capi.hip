@@ -4,8 +4,9 @@
 //   the debug images          debug_images_begin / _end: idepth colours, normals, the w1 / w2 maps
 //   the wireframe             debug_wireframe_begin / _end
 //   the metric outputs        metric_outputs_begin / _end: depth image, millimetre image, point clouds, 3-D mesh
+//   the map error             map_error_begin / _end: photometric or against a true map; box mean, histogram, ranks, sum, picture
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
-// The five begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// The six begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
 // they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
 // the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
@@ -14,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "debug_kernels.h"
+#include "map_error_kernels.h"
 #include "mesh_kernels.h"
 #include "metric_kernels.h"
 #include "nltgv2_context.hpp"
@@ -91,6 +93,8 @@ static flame_hip::WireBuffers wire_buffers(const flame_nltgv2_ctx* ctx) {
   return wb;
 }
 static_assert(flame_hip::kWireCounts * sizeof(int) <= kWireCountBytes, "wire_layout reserves too little for the counters");
+static_assert(sizeof(flame_hip::MapErrorStats) == sizeof(flame_nltgv2_map_error_stats) && sizeof(flame_nltgv2_map_error_stats) == kMapErrorStatsBytes,
+              "the statistics on the device, in the header and in map_error_layout are one struct");
 
 extern "C" {
 
@@ -574,6 +578,165 @@ int flame_nltgv2_metric_outputs(flame_nltgv2_ctx* ctx, const float* Kinv, const 
   return FLAME_NLTGV2_OK;
 }
 
+void flame_nltgv2_default_map_error_params(flame_nltgv2_map_error_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->KRKinv[0] = p->KRKinv[4] = p->KRKinv[8] = 1.0f;
+  p->source = FLAME_NLTGV2_MAP_ERROR_PHOTO;
+  p->border = 3;
+  p->relative = 1;
+  p->ptile_num = 99, p->ptile_den = 100;
+  p->max_error = 32.0f;
+  p->want_stats = p->want_error_map = p->copy_out = 1;
+}
+
+// The map error on the side stream (see flame_nltgv2.h).  Like the metric outputs it reads what the other stages left on the device, in
+// the order of that stream, and nothing of the canonical arrays: no mesh_state_on, no side_kernels_read_last.
+int flame_nltgv2_map_error_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_error_params* params, int rows, int cols) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_map_error_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  if (!params || rows <= 0 || cols <= 0 || (uint64_t)rows * (uint64_t)cols >= (1ull << 31)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const flame_nltgv2_map_error_params& p = *params;
+  const bool photo = p.source == FLAME_NLTGV2_MAP_ERROR_PHOTO;
+  if (!photo && p.source != FLAME_NLTGV2_MAP_ERROR_TRUTH) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  MapErrorWants w;
+  w.stats = p.want_stats != 0, w.error_map = p.want_error_map != 0, w.image = p.want_image != 0, w.copy_out = p.copy_out != 0;
+  w.host_truth = !photo && p.truth_host != nullptr;
+  w.host_gray = !photo && w.image && p.gray_host != nullptr;
+  if (!w.stats && !w.error_map && !w.image) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const float* map = nullptr;
+  if (p.map_device) {
+    map = (const float*)p.map_device;
+  } else if (p.use_filtered_map) {
+    if (ctx->fmap_rows != rows || ctx->fmap_cols != cols || !ctx->m_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    map = (const float*)ctx->m_img.p;
+  } else {
+    if (ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    map = (const float*)ctx->r_img.p;
+  }
+  flame_hip::MapErrorPhoto ph{};
+  bool ctx_images = false;
+  if (photo) {
+    if (p.border < 1) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    if (p.ref_device || p.cmp_device) {
+      if (!p.ref_device || !p.cmp_device || p.image_step_bytes < cols) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      ph.ref = (const uint8_t*)p.ref_device, ph.cmp = (const uint8_t*)p.cmp_device, ph.step = p.image_step_bytes;
+    } else {
+      if (ctx->img_rows != rows || ctx->img_cols != cols || !ctx->img_ref.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      ph.ref = (const uint8_t*)ctx->img_ref.p, ph.cmp = (const uint8_t*)ctx->img_cmp.p, ph.step = ctx->img_step;
+      ctx_images = true;
+    }
+    std::memcpy(ph.geo.KRKinv, p.KRKinv, sizeof(ph.geo.KRKinv));
+    std::memcpy(ph.geo.Kt, p.Kt, sizeof(ph.geo.Kt));
+    ph.border = p.border;
+  } else {
+    if ((p.truth_host != nullptr) == (p.truth_device != nullptr)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  }
+  const int win = map_error_window(p.win_size, cols, flame_hip::kMapErrorMaxWin);
+  if (win == 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  float hist_scale = p.hist_scale;
+  if (hist_scale == 0.0f) hist_scale = photo ? 1.0f : 1000.0f;
+  if (!(hist_scale > 0.0f) || !(hist_scale <= 3.402823466e+38f)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (p.ptile_den <= 0 || p.ptile_num < 0 || p.ptile_num > p.ptile_den) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (w.image) {
+    if (!(p.max_error > 0.0f)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    if (!photo && ((p.gray_host != nullptr) == (p.gray_device != nullptr) || p.gray_step_bytes < cols)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  }
+  const size_t n = (size_t)rows * (size_t)cols, f = sizeof(float);
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::MapErrorPending mp;
+  mp.rows = rows, mp.cols = cols, mp.source = p.source, mp.win_size = win, mp.hist_scale = hist_scale, mp.want = w;
+  mp.at = map_error_layout(rows, cols, w);
+  rc = open_stage(ctx, ctx->merr, mp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->e_err, f * n);
+  if (!rc && win > 1) rc = ensure(ctx, ctx->e_smooth, f * n);
+  if (!rc && w.stats) rc = ensure(ctx, ctx->e_stats, sizeof(flame_hip::MapErrorStats));
+  if (!rc && w.stats) rc = ensure(ctx, ctx->e_partials, sizeof(double) * (size_t)flame_hip::map_error_chunks((long)n));
+  if (!rc && w.image) rc = ensure(ctx, ctx->e_img, 3 * n + 16);
+  if (!rc && w.host_truth) rc = ensure(ctx, ctx->e_truth, f * n);
+  if (!rc && w.host_gray) rc = ensure(ctx, ctx->e_gray, n + 16);
+  if (rc) return rc;
+  ctx->merr.active = false;  // (from here on the pinned outputs are being rewritten)
+  char* h = ctx->merr.h.p;
+  const float* truth = (const float*)p.truth_device;
+  if (w.host_truth) {  // through pinned memory: the caller's array is free when this returns
+    std::memcpy(h + mp.at.truth, p.truth_host, f * n);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->e_truth.p, h + mp.at.truth, f * n, hipMemcpyHostToDevice, rs));
+    truth = (const float*)ctx->e_truth.p;
+  }
+  const uint8_t* gray = ph.ref;
+  int gray_step = ph.step;
+  if (!photo && w.image) {
+    rc = stage_gray(ctx, p.gray_host, p.gray_device, p.gray_step_bytes, rows, cols, h + mp.at.gray, ctx->e_gray, &gray, &gray_step);
+    if (rc) return rc;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->merr.ev0, rs));
+  float* err = (float*)ctx->e_err.p;
+  if (photo) LAUNCHCHK(ctx, flame_hip::launch_map_error_photo(rows, cols, ph, map, err, rs));
+  else LAUNCHCHK(ctx, flame_hip::launch_map_error_truth(rows, cols, map, truth, p.relative != 0, err, rs));
+  ctx->merr_reads_images = ctx_images;
+  if (win > 1) {
+    LAUNCHCHK(ctx, flame_hip::launch_map_error_box(rows, cols, win, err, (float*)ctx->e_smooth.p, rs));
+    err = (float*)ctx->e_smooth.p;
+  }
+  if (w.stats)
+    LAUNCHCHK(ctx, flame_hip::launch_map_error_stats((long)n, err, hist_scale, p.ptile_num, p.ptile_den, (double*)ctx->e_partials.p,
+                                                     (flame_hip::MapErrorStats*)ctx->e_stats.p, rs));
+  if (w.image) LAUNCHCHK(ctx, flame_hip::launch_map_error_picture(rows, cols, gray, gray_step, err, p.max_error, p.flip != 0, (uint8_t*)ctx->e_img.p, rs));
+  if (w.stats) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.stats, ctx->e_stats.p, sizeof(flame_hip::MapErrorStats), hipMemcpyDeviceToHost, rs));
+  if (w.copy_out) {
+    if (w.error_map) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.error_map, err, f * n, hipMemcpyDeviceToHost, rs));
+    if (w.image) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.image, ctx->e_img.p, 3 * n, hipMemcpyDeviceToHost, rs));
+  }
+  mp.err_device = err;
+  ctx->merr_pending = mp;
+  return close_stage(ctx, ctx->merr);
+}
+
+int flame_nltgv2_map_error_end(flame_nltgv2_ctx* ctx, flame_nltgv2_map_error_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_map_error_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::MapErrorPending& mp = ctx->merr_pending;
+  if (!out || !ctx->merr.h.p || !ctx->merr.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  ctx->merr_reads_images = false;
+  const char* h = ctx->merr.h.p;
+  const MapErrorWants& w = mp.want;
+  out->rows = mp.rows, out->cols = mp.cols, out->source = mp.source, out->win_size = mp.win_size;
+  out->hist_scale = mp.hist_scale;
+  out->device_ms = stage_ms(ctx->merr);
+  out->stats = w.stats ? (const flame_nltgv2_map_error_stats*)(h + mp.at.stats) : nullptr;
+  out->stats_device = w.stats ? ctx->e_stats.p : nullptr;
+  out->error_map = w.copy_out && w.error_map ? (const float*)(h + mp.at.error_map) : nullptr;
+  out->error_map_device = w.error_map ? mp.err_device : nullptr;
+  out->image = w.copy_out && w.image ? (const uint8_t*)(h + mp.at.image) : nullptr;
+  out->image_device = w.image ? ctx->e_img.p : nullptr;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_map_error(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_error_params* params, int rows, int cols, float* error_map_out,
+                           uint8_t* image_out, flame_nltgv2_map_error_stats* stats_out) {
+  flame_nltgv2_map_error_params p;
+  flame_nltgv2_default_map_error_params(&p);
+  if (params) p = *params;
+  p.want_error_map = error_map_out != nullptr, p.want_image = image_out != nullptr, p.want_stats = stats_out != nullptr;
+  p.copy_out = 1;
+  int rc = flame_nltgv2_map_error_begin(ctx, params ? &p : nullptr, rows, cols);
+  if (rc) return rc;
+  flame_nltgv2_map_error_view v;
+  rc = flame_nltgv2_map_error_end(ctx, &v);
+  if (rc) return rc;
+  const size_t n = (size_t)v.rows * (size_t)v.cols;
+  if (error_map_out) std::memcpy(error_map_out, v.error_map, sizeof(float) * n);
+  if (image_out) std::memcpy(image_out, v.image, 3 * n);
+  if (stats_out) *stats_out = *v.stats;
+  return FLAME_NLTGV2_OK;
+}
+
 void flame_nltgv2_default_debug_image_params(flame_nltgv2_debug_image_params* p) {
   if (!p) return;
   p->scene_color_scale = 1.0f;  // params.h:109
@@ -822,6 +985,10 @@ int flame_nltgv2_photo_set_images(flame_nltgv2_ctx* ctx, const uint8_t* ref, con
   if (!ref || !cmp || rows < 2 || cols < 2 || step_bytes < cols) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   // the last row ends at its cols-th byte: the caller's buffer need not hold that row's padding
   const size_t bytes = (size_t)(rows - 1) * (size_t)step_bytes + (size_t)cols;
+  if (ctx->merr_reads_images) {  // (a map_error_begin without its _end may still read the images that are about to be replaced)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+    ctx->merr_reads_images = false;
+  }
   HIPCHK(ctx, wait_solver_stream(ctx));
   rc = ensure(ctx, ctx->img_ref, bytes + 16);
   if (!rc) rc = ensure(ctx, ctx->img_cmp, bytes + 16);

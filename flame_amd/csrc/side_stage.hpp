@@ -1,7 +1,7 @@
 // side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
-// images, the wireframe, the metric outputs), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
+// images, the wireframe, the metric outputs, the map error), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
 // outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it (MetricLayout:
-// tests/cpp/metric_layout_test.cc).
+// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc).
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
@@ -127,6 +127,36 @@ inline MetricLayout metric_layout(int rows, int cols, int32_t V, int32_t T, cons
   m.triangles = m.normals + up16(out && w.mesh ? 3 * f * (size_t)V : 0);
   m.total = m.triangles + up16(out && w.mesh ? 3 * sizeof(int32_t) * (size_t)T : 0) + 16;
   return m;
+}
+
+// What a map-error call asks for (flame_nltgv2_map_error_params) and what it stages on its way up.
+struct MapErrorWants {
+  bool stats, error_map, image, copy_out;
+  bool host_truth, host_gray;  // a true map / a grey image of the caller's in host memory goes up through this buffer
+};
+constexpr size_t kMapErrorStatsBytes = 256 * sizeof(int32_t) + 3 * sizeof(int32_t) + sizeof(float) + sizeof(double);  // flame_nltgv2_map_error_stats
+struct MapErrorLayout {
+  // the statistics | rows*cols floats | 3*rows*cols bytes | a host true map on its way up | a host grey image on its way up.  The
+  // statistics are always there; the error map and the picture take room only if wanted and copy_out.
+  size_t stats, error_map, image, truth, gray, total;
+};
+inline MapErrorLayout map_error_layout(int rows, int cols, const MapErrorWants& w) {
+  const size_t n = (size_t)rows * (size_t)cols;
+  MapErrorLayout m;
+  m.stats = 0;
+  m.error_map = up16(kMapErrorStatsBytes);
+  m.image = m.error_map + up16(w.copy_out && w.error_map ? sizeof(float) * n : 0);
+  m.truth = m.image + up16(w.copy_out && w.image ? 3 * n : 0);
+  m.gray = m.truth + up16(w.host_truth ? sizeof(float) * n : 0);
+  m.total = m.gray + up16(w.host_gray ? n : 0) + 16;
+  return m;
+}
+
+// The reference's choice of the box (flame.cc:919-922) where the caller names none; 0 for a size that is no odd number of
+// 1 .. max_win.
+inline int map_error_window(int win_size, int cols, int max_win) {
+  if (win_size == 0) return cols < 640 ? 5 : 11;
+  return (win_size >= 1 && win_size <= max_win && win_size % 2 == 1) ? win_size : 0;
 }
 
 // Every index of T triangles names one of V vertices.

@@ -107,6 +107,69 @@ class _MetricOutputsView(C.Structure):
                 + [("device_ms", C.c_float)])
 
 
+MAP_ERROR_PHOTO, MAP_ERROR_TRUTH = 0, 1
+
+
+class MapErrorParams(C.Structure):
+    """== flame_nltgv2_map_error_params (same defaults).  source: MAP_ERROR_PHOTO (KRKinv, Kt, border; the images of photo_set_images or
+    ref_device / cmp_device with image_step_bytes) or MAP_ERROR_TRUTH (a true inverse-depth map: truth = a (rows, cols) f32 array,
+    or truth_device = an address; relative).  win_size 0: the reference's choice; hist_scale 0: the source's default.  The arrays
+    given here are kept alive by the object."""
+
+    _fields_ = [("map_device", C.c_void_p), ("ref_device", C.c_void_p), ("cmp_device", C.c_void_p), ("truth_host", _FP),
+                ("truth_device", C.c_void_p), ("gray_host", C.c_void_p), ("gray_device", C.c_void_p), ("KRKinv", C.c_float * 9),
+                ("Kt", C.c_float * 3), ("source", C.c_int32), ("use_filtered_map", C.c_int32), ("image_step_bytes", C.c_int32),
+                ("border", C.c_int32), ("relative", C.c_int32), ("win_size", C.c_int32), ("hist_scale", C.c_float),
+                ("ptile_num", C.c_int32), ("ptile_den", C.c_int32), ("gray_step_bytes", C.c_int32), ("max_error", C.c_float),
+                ("flip", C.c_int32), ("want_stats", C.c_int32), ("want_error_map", C.c_int32), ("want_image", C.c_int32),
+                ("copy_out", C.c_int32)]
+
+    def __init__(self, source=MAP_ERROR_PHOTO, KRKinv=None, Kt=None, border=3, ref_device=None, cmp_device=None, image_step_bytes=0,
+                 truth=None, truth_device=None, relative=True, map_device=None, use_filtered_map=False, win_size=0, hist_scale=0.0,
+                 ptile_num=99, ptile_den=100, gray=None, gray_device=None, gray_step_bytes=None, max_error=32.0, flip=False,
+                 want_stats=True, want_error_map=True, want_image=False, copy_out=True):
+        super().__init__()
+        self.map_device = int(map_device) if map_device else None
+        self.ref_device = int(ref_device) if ref_device else None
+        self.cmp_device = int(cmp_device) if cmp_device else None
+        self.image_step_bytes = int(image_step_bytes)
+        self._keep = []
+        if truth is not None:
+            t = np.ascontiguousarray(truth, np.float32)
+            self._keep.append(t)
+            self.truth_host = t.ctypes.data_as(_FP)
+        self.truth_device = int(truth_device) if truth_device else None
+        if gray is not None:
+            g = gray if isinstance(gray, np.ndarray) and _rows_contiguous_u8(gray) else np.ascontiguousarray(gray, np.uint8)
+            self._keep.append(g)
+            self.gray_host = g.ctypes.data
+            self.gray_step_bytes = int(g.strides[0]) if gray_step_bytes is None else int(gray_step_bytes)
+        else:
+            self.gray_step_bytes = int(gray_step_bytes or 0)
+        self.gray_device = int(gray_device) if gray_device else None
+        k = np.eye(3, dtype=np.float32).reshape(9) if KRKinv is None else np.ascontiguousarray(KRKinv, np.float32).reshape(9)
+        t3 = np.zeros(3, np.float32) if Kt is None else np.ascontiguousarray(Kt, np.float32).reshape(3)
+        self.KRKinv = (C.c_float * 9)(*k.tolist())
+        self.Kt = (C.c_float * 3)(*t3.tolist())
+        self.source, self.use_filtered_map, self.border, self.relative = int(source), int(bool(use_filtered_map)), int(border), int(bool(relative))
+        self.win_size, self.hist_scale, self.ptile_num, self.ptile_den = int(win_size), float(hist_scale), int(ptile_num), int(ptile_den)
+        self.max_error, self.flip = float(max_error), int(bool(flip))
+        self.want_stats, self.want_error_map, self.want_image, self.copy_out = (int(bool(v)) for v in (want_stats, want_error_map, want_image, copy_out))
+
+
+class MapErrorStats(C.Structure):
+    """== flame_nltgv2_map_error_stats."""
+
+    _fields_ = [("hist", C.c_int32 * 256), ("n_valid", C.c_int32), ("median_bin", C.c_int32), ("ptile_bin", C.c_int32),
+                ("mean", C.c_float), ("sum", C.c_double)]
+
+
+class _MapErrorView(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("source", C.c_int32), ("win_size", C.c_int32), ("hist_scale", C.c_float),
+                ("device_ms", C.c_float), ("stats", C.POINTER(MapErrorStats)), ("stats_device", C.c_void_p), ("error_map", _FP),
+                ("error_map_device", C.c_void_p), ("image", C.POINTER(C.c_uint8)), ("image_device", C.c_void_p)]
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -196,6 +259,7 @@ ABI_SYMBOLS = (
     "flame_nltgv2_mesh_outputs_end", "flame_nltgv2_mesh_outputs",
     "flame_nltgv2_default_metric_params", "flame_nltgv2_metric_outputs_begin", "flame_nltgv2_metric_outputs_end",
     "flame_nltgv2_metric_outputs",
+    "flame_nltgv2_default_map_error_params", "flame_nltgv2_map_error_begin", "flame_nltgv2_map_error_end", "flame_nltgv2_map_error",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -282,6 +346,11 @@ def load_library():
         "flame_nltgv2_metric_outputs_end": (C.c_int, [ctx, C.POINTER(_MetricOutputsView)]),
         "flame_nltgv2_metric_outputs": (C.c_int, [ctx, _FP, _FP, C.POINTER(MetricParams), C.c_int, C.c_int, _FP, C.POINTER(C.c_uint16), _FP,
                                                   _FP, C.POINTER(C.c_uint32), _IP, _FP, _FP, _IP, _IP]),
+        "flame_nltgv2_default_map_error_params": (None, [C.POINTER(MapErrorParams)]),
+        "flame_nltgv2_map_error_begin": (C.c_int, [ctx, C.POINTER(MapErrorParams), C.c_int, C.c_int]),
+        "flame_nltgv2_map_error_end": (C.c_int, [ctx, C.POINTER(_MapErrorView)]),
+        "flame_nltgv2_map_error": (C.c_int, [ctx, C.POINTER(MapErrorParams), C.c_int, C.c_int, _FP, C.POINTER(C.c_uint8),
+                                             C.POINTER(MapErrorStats)]),
         "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
         "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
                                                       C.c_int]),
@@ -695,6 +764,41 @@ class Regularizer:
         """metric_outputs_begin; metric_outputs_end."""
         self.metric_outputs_begin(Kinv, rows, cols, pose, params)
         return self.metric_outputs_end()
+
+    # -- the map error: photometric or against a true map (flame_nltgv2_map_error*; the dead block flame.cc:854-984) ------------------
+    def map_error_begin(self, params: MapErrorParams, rows, cols):
+        """Enqueues the error image of the chosen map (params.map_device, params.use_filtered_map, else the resident map of the last
+        interpolate_mesh[_begin]), its box mean, the statistics and the picture on the side stream and returns."""
+        self._chk(self._L.flame_nltgv2_map_error_begin(self._ctx, C.byref(params), rows, cols), "map_error_begin")
+
+    def map_error_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(rows, cols, source, win_size, hist_scale, device_ms, device = {name: address} and, as asked
+        for, n_valid, hist (256,) i32, median_bin, ptile_bin, sum (a Python float: the double), mean (np.float32), error_map
+        (rows, cols) f32 with NaN where no error is defined, image (rows, cols, 3) u8).  copy=False: views of the context's pinned
+        memory, valid until the next begin.  With MapErrorParams(copy_out=False) only the statistics and the addresses are there."""
+        v = _MapErrorView()
+        self._chk(self._L.flame_nltgv2_map_error_end(self._ctx, C.byref(v)), "map_error_end")
+        take = (lambda a: a.copy()) if copy else (lambda a: a)
+        out = dict(rows=int(v.rows), cols=int(v.cols), source=int(v.source), win_size=int(v.win_size), hist_scale=float(v.hist_scale),
+                   device_ms=float(v.device_ms), device={})
+        for name in ("stats", "error_map", "image"):
+            dev = getattr(v, name + "_device")
+            if dev:
+                out["device"][name] = int(dev)
+        if v.stats:
+            s = v.stats.contents
+            out.update(hist=np.ctypeslib.as_array(s.hist).copy(), n_valid=int(s.n_valid), median_bin=int(s.median_bin),
+                       ptile_bin=int(s.ptile_bin), mean=np.float32(s.mean), sum=float(s.sum))
+        if v.error_map:
+            out["error_map"] = take(np.ctypeslib.as_array(v.error_map, shape=(v.rows, v.cols)))
+        if v.image:
+            out["image"] = take(np.ctypeslib.as_array(v.image, shape=(v.rows, v.cols, 3)))
+        return out
+
+    def map_error(self, params: MapErrorParams, rows, cols) -> dict:
+        """map_error_begin; map_error_end."""
+        self.map_error_begin(params, rows, cols)
+        return self.map_error_end()
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

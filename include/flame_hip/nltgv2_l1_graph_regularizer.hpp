@@ -238,6 +238,24 @@ struct MetricOutputs {
   const int32_t* mesh_triangles = nullptr;  const void* mesh_triangles_device = nullptr;  // [num_valid_triangles * 3]
 };
 
+// What the map error reads (flame_nltgv2_map_error_params, constructed with its defaults): the source -- photometric against another
+// frame (KRKinv, Kt, border, the two images) or a true inverse-depth map (update()'s idepths_true) --, the box, the histogram's scale
+// and rank, the picture, which outputs, and whether they travel to the host.  The C-ABI struct itself: the header states every rule.
+struct MapErrorParams : flame_nltgv2_map_error_params {
+  MapErrorParams() { flame_nltgv2_default_map_error_params(this); }
+};
+
+// What flame.cc:854-984 computed (flame_nltgv2_map_error_view): photo_error_ (the smoothed error image, NaN where undefined), the
+// histogram with its median and percentile bins, total_photo_error / avg_photo_error, and the debug_draw_photo_error picture.  Host
+// pointers into pinned memory of the DeviceGraph and the device pointers of the same arrays; all valid until its next mapErrorBegin().
+struct MapError {
+  int rows = 0, cols = 0, source = 0, win_size = 0;
+  float hist_scale = 0.0f;
+  const flame_nltgv2_map_error_stats* stats = nullptr;  const void* stats_device = nullptr;
+  const float* error = nullptr;                         const void* error_device = nullptr;      // [rows * cols]
+  const uint8_t* debug_img_photo_error = nullptr;       const void* image_device = nullptr;      // [rows * cols * 3]
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -430,6 +448,22 @@ class DeviceGraph {
     m.mesh_vertices = v.mesh_vertices, m.mesh_vertices_device = v.mesh_vertices_device;
     m.mesh_normals = v.mesh_normals, m.mesh_normals_device = v.mesh_normals_device;
     m.mesh_triangles = v.mesh_triangles, m.mesh_triangles_device = v.mesh_triangles_device;
+    return m;
+  }
+
+  // The error of the dense map the last interpolateMesh[Begin] / meshOutputsBegin left on the device (or params.map_device), on the
+  // side stream beside the running solver (flame_nltgv2_map_error_begin / _end; the semantics are stated there).
+  void mapErrorBegin(const MapErrorParams& params, int rows, int cols) {
+    check(flame_nltgv2_map_error_begin(ctx_, &params, rows, cols), "map_error_begin");
+  }
+  MapError mapErrorEnd() {
+    flame_nltgv2_map_error_view v;
+    check(flame_nltgv2_map_error_end(ctx_, &v), "map_error_end");
+    MapError m;
+    m.rows = v.rows, m.cols = v.cols, m.source = v.source, m.win_size = v.win_size, m.hist_scale = v.hist_scale;
+    m.stats = v.stats, m.stats_device = v.stats_device;
+    m.error = v.error_map, m.error_device = v.error_map_device;
+    m.debug_img_photo_error = v.image, m.image_device = v.image_device;
     return m;
   }
 

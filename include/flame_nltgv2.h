@@ -444,6 +444,126 @@ int flame_nltgv2_metric_outputs(flame_nltgv2_ctx* ctx, const float* Kinv, const 
                                 float* organized_out, float* cloud_out, uint32_t* cloud_pixel_out, int32_t* n_points_out,
                                 float* mesh_vertices_out, float* mesh_normals_out, int32_t* mesh_triangles_out, int32_t* n_valid_out);
 
+/* ---- Map error: how good the dense inverse-depth map is -- photometrically, or against a true map ---------------------------------------
+ * The reference was built around this measurement: getPoseFrame picks a comparison pose-frame (photo_error_num_pfs), DetectionData::cmp
+ * carries it, Flame::photo_error_ is handed to detectFeatures, Params::debug_draw_photo_error exists and update() takes idepths_true "for
+ * debugging" -- but the code that used all of it is the commented-out block flame.cc:854-984: the per-pixel error, a box mean, a 256-bin
+ * histogram with median and 99th percentile, total_photo_error / avg_photo_error.  This stage computes that block's quantities on the
+ * context's side stream, beside the running solver, from live, test-pinned pieces.  Nothing of the dead block is pinned by a reference
+ * test, and three of its rules are replaced on purpose (marked UNPINNED below).  tests/map_error_ref.py restates every rule in numpy
+ * float32 (no FMA) and is the checker: device and checker agree bit for bit.  The stage only READS other stages' buffers.
+ *
+ * WHICH MAP: as flame_nltgv2_metric_params: map_device (under the rules stated there), else use_filtered_map, else the resident
+ *   unfiltered map; a resident map must be rows x cols.
+ * 1. ERROR IMAGE, rows * cols floats, NaN = "no error defined here".
+ *   source == FLAME_NLTGV2_MAP_ERROR_PHOTO: for pixel (row, col) with map value v the per-vertex residual of flame_nltgv2_photo_residual
+ *     at u = (col, row): |I_cmp(project(u, v)) - I_ref(u)| with KRKinv (9 floats) and Kt (3 floats) as there.  NaN where v is NaN or
+ *     negative, where u or the projection lies outside [border, size - border) in x or y, or where the projection is NaN; v == 0 uses the
+ *     infinite-depth projection.  border >= 1.  The images: ref_device / cmp_device, two u8 images in device memory with rows of
+ *     image_step_bytes (>= cols) bytes each, read in place (two frames resident in the stereo context: flame_stereo_frame_image_device;
+ *     the rules of map_device hold for them), or, both NULL, the images of flame_nltgv2_photo_set_images, whose size must be rows x cols
+ *     (they must not be replaced before _end; flame_nltgv2_photo_set_images waits for a pending stage).  It equals the checker's
+ *     oracle.capi.photo_residual on the pixel grid bit for bit.
+ *   source == FLAME_NLTGV2_MAP_ERROR_TRUTH: with a true inverse-depth map t of the same size (truth_host: rows * cols floats, staged
+ *     through pinned memory, free when begin returns; or truth_device, under the rules of map_device; exactly one of the two) a pixel
+ *     is valid iff !(v != v) && t > 0.0f -- a NaN, zero or negative t is a hole --, err = fabsf(v - t), with relative != 0
+ *     err = fabsf(v - t) / t (an IEEE division); infinite operands whose result is a NaN (inf - inf, inf / inf) give a hole.  Every hole
+ *     of either source is the quiet NaN 0x7fc00000.  This is update()'s idepths_true.
+ * 2. BOX MEAN, win_size odd in [1, 31]; 1: none; 0: the reference's choice, 11, or 5 when cols < 640.  h = win_size / 2.  A pixel whose
+ *   own error is NaN stays NaN.  Every other pixel gets sum / (float)count over the window [row - h, row + h] x [col - h, col + h]:
+ *   count = the non-NaN errors in the window (>= 1: the pixel itself); sum is taken separably in float32 in a fixed order: for every row
+ *   of the window a horizontal sum that starts from +0.0f and goes left to right over the window's columns, then, over the window's
+ *   rows top to bottom, the sum of those horizontal sums, again from +0.0f.  A NaN or a position outside the image contributes +0.0f
+ *   (adding it or skipping it gives the same bits).  The kernel's tiling does not show.
+ *   UNPINNED, deviates from the dead block, which box-sums an integral image with NaN set to 0, divides by win * win -- diluting
+ *   errors at the edge of coverage and turning holes into zeros -- and has a first-row / first-column bug (flame.cc:903).
+ * 3. STATISTICS over the non-NaN pixels of the (smoothed) error image (want_stats):
+ *   n_valid     their number.
+ *   hist[256]   s = err * hist_scale (a float multiply); bin = s >= 255.0f ? 255 : (int)(s + 0.5f): the clamp comes before the
+ *               conversion, so +inf lands in bin 255.  hist_scale == 0 selects the default: 1.0 for PHOTO (the bins are the reference's
+ *               fast_roundf(err) grey levels), 1000.0 for TRUTH (relative: bins 0.1 % wide up to 25.5 %); otherwise it must be finite
+ *               and > 0.
+ *   median_bin  the smallest m with 2 * cum[m] > n_valid, cum[m] = hist[0] + ... + hist[m].
+ *   ptile_bin   the smallest m with ptile_den * cum[m] > ptile_num * n_valid, in 64-bit integers (default 99 / 100; 0 <= ptile_num <=
+ *               ptile_den, ptile_den > 0; ptile_num == ptile_den: no such m, -1).  Both are -1 when n_valid == 0.
+ *               UNPINNED: replaces the dead block's float comparison and its `else if`, which cannot find both ranks in one bin.
+ *   sum, mean   the reference's total_photo_error / avg_photo_error: sum is a double, mean = (float)(sum / n_valid), 0 when n_valid
+ *               == 0.  The order of the sum is part of the definition and independent of the launch: the float errors are converted to
+ *               double, holes are +0.0; every block of 1024 consecutive linear pixel indices (the last one padded with +0.0) is reduced
+ *               pairwise, p[t] += p[t + s] for s = 512, 256, ..., 1; the block partials b[0 .. B) are combined as
+ *               flame_nltgv2_rescale_data's sum: q[t] = b[t] + b[t + 1024] + ... in turn from +0.0, t < 1024, then q pairwise in the same
+ *               way.  No floating-point atomics anywhere: two calls give the same bytes.
+ * 4. PICTURE (want_image), rows * cols * 3 bytes: the grey reference image (cvtColor(GRAY2RGB)) with every non-NaN error pixel replaced
+ *   by jet(err, 0, max_error) (utils/visualization.h:142-167; max_error > 0), flip as in flame_nltgv2_debug_image_params; no text.
+ *   PHOTO: the grey image is the reference image of the call.  TRUTH: gray_host or gray_device with gray_step_bytes, exactly one, as in
+ *   flame_nltgv2_debug_images_begin; without one the picture cannot be requested.
+ * 5. want_stats, want_error_map, want_image, copy_out as in the metric stage: with copy_out == 0 the error map and the picture stay on
+ *   the device and only the statistics travel (1048 bytes). */
+#define FLAME_NLTGV2_MAP_ERROR_PHOTO 0
+#define FLAME_NLTGV2_MAP_ERROR_TRUTH 1
+typedef struct flame_nltgv2_map_error_params {
+  const void*    map_device;        /* NULL */
+  const void*    ref_device;        /* NULL     PHOTO */
+  const void*    cmp_device;        /* NULL     PHOTO */
+  const float*   truth_host;        /* NULL     TRUTH */
+  const void*    truth_device;      /* NULL     TRUTH */
+  const uint8_t* gray_host;         /* NULL     TRUTH with want_image */
+  const void*    gray_device;       /* NULL     TRUTH with want_image */
+  float   KRKinv[9];                /* identity PHOTO */
+  float   Kt[3];                    /* 0        PHOTO */
+  int32_t source;                   /* FLAME_NLTGV2_MAP_ERROR_PHOTO */
+  int32_t use_filtered_map;         /* 0 */
+  int32_t image_step_bytes;         /* 0        of ref_device and cmp_device */
+  int32_t border;                   /* 3        PHOTO */
+  int32_t relative;                 /* 1        TRUTH */
+  int32_t win_size;                 /* 0        the reference's choice */
+  float   hist_scale;               /* 0        the default of the source */
+  int32_t ptile_num;                /* 99 */
+  int32_t ptile_den;                /* 100 */
+  int32_t gray_step_bytes;          /* 0 */
+  float   max_error;                /* 32.0     the error painted in the last colour of the picture */
+  int32_t flip;                     /* 0 */
+  int32_t want_stats;               /* 1 */
+  int32_t want_error_map;           /* 1 */
+  int32_t want_image;               /* 0 */
+  int32_t copy_out;                 /* 1 */
+} flame_nltgv2_map_error_params;
+void flame_nltgv2_default_map_error_params(flame_nltgv2_map_error_params* p);
+
+/* The statistics, as they lie on the device and in pinned memory. */
+typedef struct flame_nltgv2_map_error_stats {
+  int32_t hist[256];
+  int32_t n_valid, median_bin, ptile_bin;
+  float   mean;
+  double  sum;
+} flame_nltgv2_map_error_stats;
+
+/* Pointers into pinned memory of the context and the device pointers of the same arrays; all valid until the next
+ * flame_nltgv2_map_error_begin.  What was not asked for is NULL; with copy_out == 0 error_map and image are NULL. */
+typedef struct flame_nltgv2_map_error_view {
+  int32_t rows, cols, source, win_size;  /* win_size: the one that was used */
+  float   hist_scale;                    /* the one that was used */
+  float   device_ms;                     /* measurement aid: HIP-event time of what begin enqueued on the side stream */
+  const flame_nltgv2_map_error_stats* stats;  const void* stats_device;
+  const float* error_map;                     const void* error_map_device;
+  const uint8_t* image;                       const void* image_device;
+} flame_nltgv2_map_error_view;
+
+/* begin  checks the arguments -- an error (no graph; params NULL; rows / cols <= 0 or rows * cols >= 2^31; an unknown source; no resident
+ *        map of the kind asked for or one of another size; PHOTO: border < 1, one of ref_device / cmp_device without the other or with
+ *        image_step_bytes < cols, neither and no images of flame_nltgv2_photo_set_images or images of another size; TRUTH: not exactly one
+ *        true map; win_size even, negative or above 31; hist_scale negative, NaN or infinite; ptile_den <= 0, ptile_num < 0 or
+ *        ptile_num > ptile_den; want_image with max_error not > 0, or in TRUTH mode without exactly one grey image of gray_step_bytes
+ *        >= cols; nothing wanted) is reported before anything is enqueued and leaves the outputs of an earlier begin, and its pending
+ *        _end, as they are --, then enqueues everything on the context's side stream and returns.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_map_error == begin (with copy_out forced to 1 and the want_* flags replaced by: the array is not NULL); end; copies into
+ *        the caller's arrays: error_map_out rows * cols floats, image_out rows * cols * 3 bytes, *stats_out. */
+int flame_nltgv2_map_error_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_error_params* params, int rows, int cols);
+int flame_nltgv2_map_error_end(flame_nltgv2_ctx* ctx, flame_nltgv2_map_error_view* out);
+int flame_nltgv2_map_error(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_error_params* params, int rows, int cols,
+                           float* error_map_out, uint8_t* image_out, flame_nltgv2_map_error_stats* stats_out);
+
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
  * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
@@ -453,7 +573,8 @@ int flame_nltgv2_metric_outputs(flame_nltgv2_ctx* ctx, const float* Kinv, const 
  *
  * NOT covered, on purpose:
  *   cv::putText        debug_draw_text_overlay is treated as false.
- *   debug_draw_photo_error   feeds on commented-out code in the reference.
+ * (debug_draw_photo_error feeds on commented-out code in the reference, flame.cc:854-984; what that block computed, and a picture of
+ * it, is flame_nltgv2_map_error_begin above, with its unpinned parts marked there.)
  * (getDebugImageMatches, debug_draw_matches: live code too; flame_stereo_draw_matches, flame_stereo.h.  getDebugImageDetections,
  * drawDetections, whose `score` is written at flame.cc:1249: flame_stereo_draw_detections, flame_stereo.h.  With them every
  * getDebugImage* getter of flame.h has a counterpart.)
