@@ -18,6 +18,8 @@ from .regularizer import (  # noqa: F401
     NLTGV2Error,
     Params,
     Regularizer,
+    ViewCounts,
+    ViewParams,
     WireframeParams,
     delaunay,
     library_path,

@@ -10,7 +10,7 @@
 //   nltgv2_run.hip         which kernels run n steps (planner), enqueue / settle / roll back, the run entry points
 //   nltgv2_graph_capi.hip  graph in / out: upload, per-frame sync, projection, rescale, state download, costs, export
 //   nltgv2_frame_capi.hip  the rows around the solver that work on its device state: the dense map, the mesh outputs, the debug images and
-//                          the wireframe, the metric outputs, the map error (begin / end stages on the side stream; their pure part:
+//                          the wireframe, the metric outputs, the map error, the view renderer (begin / end stages on the side stream; their pure part:
 //                          side_stage.hpp), photometric residual
 #ifndef FLAME_AMD_NLTGV2_CONTEXT_HPP_
 #define FLAME_AMD_NLTGV2_CONTEXT_HPP_
@@ -372,6 +372,17 @@ struct flame_nltgv2_ctx {
     const void* err_device = nullptr;  // the (smoothed) error image
     MapErrorLayout at{};
   } merr_pending;
+  // flame_nltgv2_render_view_begin / _end / _arrays (view_kernels.hip): device outputs, a key image, pinned outputs and timing events
+  // of its own; the resident triangles, the filters' validity and the canonical pos / x are only read.  Pinned: view_layout.
+  // v_atris / v_apos / v_aid: the caller's mesh of the _arrays form
+  DevBuf v_vtx, v_keys, v_map, v_tri, v_counts, v_big, v_tvalid, v_atris, v_apos, v_aid;
+  SideStage view;
+  struct ViewPending {
+    int rows = 0, cols = 0;
+    int32_t T = 0;
+    ViewWants want{};
+    ViewLayout at{};
+  } view_pending;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

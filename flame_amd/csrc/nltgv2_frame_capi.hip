@@ -5,8 +5,9 @@
 //   the wireframe             debug_wireframe_begin / _end
 //   the metric outputs        metric_outputs_begin / _end: depth image, millimetre image, point clouds, 3-D mesh
 //   the map error             map_error_begin / _end: photometric or against a true map; box mean, histogram, ranks, sum, picture
+//   the view renderer         render_view_begin / _end, render_view_arrays: the mesh seen from another camera, the nearest surface kept
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
-// The six begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// The seven begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
 // they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
 // the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
@@ -19,6 +20,7 @@
 #include "mesh_kernels.h"
 #include "metric_kernels.h"
 #include "nltgv2_context.hpp"
+#include "view_kernels.h"
 #include "wireframe_kernels.h"
 
 // Which state a mesh stage on the side stream describes (interpolate_mesh_begin, mesh_outputs_begin), and the wait that lets `rs` read
@@ -95,6 +97,8 @@ static flame_hip::WireBuffers wire_buffers(const flame_nltgv2_ctx* ctx) {
 static_assert(flame_hip::kWireCounts * sizeof(int) <= kWireCountBytes, "wire_layout reserves too little for the counters");
 static_assert(sizeof(flame_hip::MapErrorStats) == sizeof(flame_nltgv2_map_error_stats) && sizeof(flame_nltgv2_map_error_stats) == kMapErrorStatsBytes,
               "the statistics on the device, in the header and in map_error_layout are one struct");
+static_assert(sizeof(flame_hip::ViewCounts) == sizeof(flame_nltgv2_view_counts) && sizeof(flame_nltgv2_view_counts) == kViewCountBytes,
+              "the counters on the device, in the header and in view_layout are one struct");
 
 extern "C" {
 
@@ -735,6 +739,188 @@ int flame_nltgv2_map_error(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_error_p
   if (image_out) std::memcpy(image_out, v.image, 3 * n);
   if (stats_out) *stats_out = *v.stats;
   return FLAME_NLTGV2_OK;
+}
+
+void flame_nltgv2_default_view_params(flame_nltgv2_view_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->Kinv_src[0] = p->Kinv_src[4] = p->Kinv_src[8] = 1.0f;
+  p->K_dst[0] = p->K_dst[4] = p->K_dst[8] = 1.0f;
+  p->R[0] = p->R[4] = p->R[8] = 1.0f;
+  p->want_map = p->want_tri_index = p->copy_out = 1;
+}
+
+// The mesh a view-renderer call draws, on the device.  Of the graph: the resident triangles and the canonical pos / x; of the caller:
+// host arrays that go up into buffers of the stage.
+struct ViewMesh {
+  int32_t T = 0, V = 0;
+  bool own = false;                    // the _arrays form: the three host arrays
+  const int32_t* host_tris = nullptr;
+  const float* host_xy = nullptr;
+  const float* host_id = nullptr;
+  const uint8_t* host_valid = nullptr;    // validity == 1
+  const uint8_t* device_valid = nullptr;  // validity == 2
+  float value_scale = 1.0f;
+};
+
+// What begin and the _arrays form share, behind their argument checks: open_stage, the stage's buffers, everything enqueued on the
+// side stream, close_stage.
+static int view_enqueue(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params& p, const ViewMesh& m, int rows, int cols) {
+  const bool own = m.own;
+  const int32_t T = m.T, V = m.V;
+  const size_t n = (size_t)rows * (size_t)cols;
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::ViewPending vp;
+  vp.rows = rows, vp.cols = cols, vp.T = T;
+  vp.want.map = p.want_map != 0, vp.want.tri_index = p.want_tri_index != 0, vp.want.copy_out = p.copy_out != 0;
+  vp.at = view_layout(rows, cols, vp.want);
+  int rc = open_stage(ctx, ctx->view, vp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->v_vtx, sizeof(flame_hip::ViewVertex) * (size_t)V + 16);
+  if (!rc) rc = ensure(ctx, ctx->v_keys, sizeof(unsigned long long) * n);
+  if (!rc) rc = ensure(ctx, ctx->v_counts, sizeof(flame_hip::ViewCounts));
+  if (!rc) rc = ensure(ctx, ctx->v_big, sizeof(int) * ((size_t)T + 1));
+  if (!rc && vp.want.map) rc = ensure(ctx, ctx->v_map, sizeof(float) * n);
+  if (!rc && vp.want.tri_index) rc = ensure(ctx, ctx->v_tri, sizeof(int32_t) * n);
+  if (!rc && m.host_valid) rc = ensure(ctx, ctx->v_tvalid, (size_t)T + 16);
+  if (!rc && own) {
+    rc = ensure(ctx, ctx->v_atris, sizeof(int32_t) * 3 * (size_t)T + 16);
+    if (!rc) rc = ensure(ctx, ctx->v_apos, sizeof(float) * 2 * (size_t)V + 16);
+    if (!rc) rc = ensure(ctx, ctx->v_aid, sizeof(float) * (size_t)V + 16);
+  }
+  if (rc) return rc;
+  ctx->view.active = false;  // (from here on the pinned outputs are being rewritten)
+  // (pageable memory: each copy holds the host until the bytes have left the caller's array)
+  const uint8_t* d_tv = m.device_valid;
+  if (m.host_valid && T > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->v_tvalid.p, m.host_valid, (size_t)T, hipMemcpyHostToDevice, rs));
+    d_tv = (const uint8_t*)ctx->v_tvalid.p;
+  }
+  const int32_t* d_tris = (const int32_t*)ctx->r_tris.p;
+  const float2* d_pos = ctx->c.pos;
+  const float* d_val = ctx->c.x;
+  if (own) {
+    if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->v_atris.p, m.host_tris, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
+    if (V > 0) {
+      HIPCHK(ctx, hipMemcpyAsync(ctx->v_apos.p, m.host_xy, sizeof(float) * 2 * (size_t)V, hipMemcpyHostToDevice, rs));
+      HIPCHK(ctx, hipMemcpyAsync(ctx->v_aid.p, m.host_id, sizeof(float) * (size_t)V, hipMemcpyHostToDevice, rs));
+    }
+    d_tris = (const int32_t*)ctx->v_atris.p, d_pos = (const float2*)ctx->v_apos.p, d_val = (const float*)ctx->v_aid.p;
+  } else {
+    rc = mesh_state_on(ctx, rs);
+    if (rc) return rc;
+  }
+  flame_hip::ViewCamera cam;
+  std::memcpy(cam.Kinv_src, p.Kinv_src, sizeof(cam.Kinv_src));
+  std::memcpy(cam.K_dst, p.K_dst, sizeof(cam.K_dst));
+  std::memcpy(cam.R, p.R, sizeof(cam.R));
+  std::memcpy(cam.t, p.t, sizeof(cam.t));
+  cam.near_depth = p.near_depth;
+  flame_hip::ViewVertex* vtx = (flame_hip::ViewVertex*)ctx->v_vtx.p;
+  unsigned long long* keys = (unsigned long long*)ctx->v_keys.p;
+  flame_hip::ViewCounts* counts = (flame_hip::ViewCounts*)ctx->v_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->view.ev0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_view_vertices(V, d_pos, d_val, m.value_scale, cam, vtx, rs));
+  if (!own) {  // the vertex kernel is the last reader of the canonical pos / x
+    rc = side_kernels_read_last(ctx);
+    if (rc) return rc;
+  }
+  LAUNCHCHK(ctx, flame_hip::launch_view_clear((long)n, keys, counts, (int*)ctx->v_big.p, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_view_raster(T, d_tris, d_tv, vtx, keys, counts, (int*)ctx->v_big.p, rows, cols, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_view_resolve((long)n, keys, vp.want.map ? (float*)ctx->v_map.p : nullptr,
+                                                vp.want.tri_index ? (int32_t*)ctx->v_tri.p : nullptr, counts, rs));
+  char* h = ctx->view.h.p;
+  HIPCHK(ctx, hipMemcpyAsync(h + vp.at.counts, counts, sizeof(flame_hip::ViewCounts), hipMemcpyDeviceToHost, rs));
+  if (vp.want.copy_out) {
+    if (vp.want.map) HIPCHK(ctx, hipMemcpyAsync(h + vp.at.map, ctx->v_map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    if (vp.want.tri_index) HIPCHK(ctx, hipMemcpyAsync(h + vp.at.tri_index, ctx->v_tri.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, rs));
+  }
+  ctx->view_pending = vp;
+  return close_stage(ctx, ctx->view);
+}
+
+static bool view_size_ok(int rows, int cols) { return rows >= 1 && cols >= 1 && rows <= 32767 && cols <= 32767; }
+
+// The view renderer on the side stream (see flame_nltgv2.h).
+int flame_nltgv2_render_view_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params* params, const uint8_t* tri_valid, int rows, int cols,
+                                   float graph_scale) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_render_view_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  if (!params || !view_size_ok(rows, cols)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (params->validity < 0 || params->validity > 2 || (tri_valid != nullptr) != (params->validity == 1)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (params->validity == 2 && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  ViewMesh m;
+  m.T = ctx->tris.T(), m.V = ctx->L.V;
+  m.host_valid = tri_valid;
+  if (params->validity == 2) m.device_valid = (const uint8_t*)ctx->m_tvalid.p;
+  m.value_scale = graph_scale;
+  return view_enqueue(ctx, *params, m, rows, cols);
+}
+
+int flame_nltgv2_render_view_end(flame_nltgv2_ctx* ctx, flame_nltgv2_view_outputs_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_render_view_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::ViewPending& vp = ctx->view_pending;
+  if (!out || !ctx->view.h.p || !ctx->view.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  const char* h = ctx->view.h.p;
+  const bool host = vp.want.copy_out;
+  out->rows = vp.rows, out->cols = vp.cols, out->T = vp.T;
+  std::memcpy(&out->counts, h + vp.at.counts, sizeof(out->counts));
+  out->device_ms = stage_ms(ctx->view);
+  out->map = host && vp.want.map ? (const float*)(h + vp.at.map) : nullptr;
+  out->map_device = vp.want.map ? ctx->v_map.p : nullptr;
+  out->tri_index = host && vp.want.tri_index ? (const int32_t*)(h + vp.at.tri_index) : nullptr;
+  out->tri_index_device = vp.want.tri_index ? ctx->v_tri.p : nullptr;
+  return FLAME_NLTGV2_OK;
+}
+
+// _end and the copies into the caller's arrays: the tail of the two synchronous forms
+static int view_finish(flame_nltgv2_ctx* ctx, float* map_out, int32_t* tri_index_out, flame_nltgv2_view_counts* counts_out) {
+  flame_nltgv2_view_outputs_view v;
+  const int rc = flame_nltgv2_render_view_end(ctx, &v);
+  if (rc) return rc;
+  const size_t n = (size_t)v.rows * (size_t)v.cols;
+  if (map_out) std::memcpy(map_out, v.map, sizeof(float) * n);
+  if (tri_index_out) std::memcpy(tri_index_out, v.tri_index, sizeof(int32_t) * n);
+  if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_render_view(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params* params, const uint8_t* tri_valid, int rows, int cols,
+                             float graph_scale, float* map_out, int32_t* tri_index_out, flame_nltgv2_view_counts* counts_out) {
+  flame_nltgv2_view_params p;
+  flame_nltgv2_default_view_params(&p);
+  if (params) p = *params;
+  p.want_map = map_out != nullptr, p.want_tri_index = tri_index_out != nullptr, p.copy_out = 1;
+  const int rc = flame_nltgv2_render_view_begin(ctx, params ? &p : nullptr, tri_valid, rows, cols, graph_scale);
+  if (rc) return rc;
+  return view_finish(ctx, map_out, tri_index_out, counts_out);
+}
+
+int flame_nltgv2_render_view_arrays(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params* params, const int32_t* triangles, int32_t T,
+                                    const float* vertices_xy, const float* idepths, int32_t V, const uint8_t* tri_valid, int rows, int cols,
+                                    float* map_out, int32_t* tri_index_out, flame_nltgv2_view_counts* counts_out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_render_view_arrays");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!params || !view_size_ok(rows, cols) || T < 0 || V < 0 || (T > 0 && !triangles) || (V > 0 && (!vertices_xy || !idepths)))
+    return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (params->validity < 0 || params->validity > 1 || (tri_valid != nullptr) != (params->validity == 1)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!triangles_in_range(triangles, T, V)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  flame_nltgv2_view_params p = *params;
+  p.want_map = map_out != nullptr, p.want_tri_index = tri_index_out != nullptr, p.copy_out = 1;
+  ViewMesh m;
+  m.T = T, m.V = V, m.own = true;
+  m.host_tris = triangles, m.host_xy = vertices_xy, m.host_id = idepths;
+  m.host_valid = tri_valid;
+  rc = view_enqueue(ctx, p, m, rows, cols);
+  if (rc) return rc;
+  return view_finish(ctx, map_out, tri_index_out, counts_out);
 }
 
 void flame_nltgv2_default_debug_image_params(flame_nltgv2_debug_image_params* p) {

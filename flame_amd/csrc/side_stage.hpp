@@ -1,7 +1,7 @@
 // side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
-// images, the wireframe, the metric outputs, the map error), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
+// images, the wireframe, the metric outputs, the map error, the view renderer), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
 // outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it (MetricLayout:
-// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc).
+// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc).
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
@@ -157,6 +157,26 @@ inline MapErrorLayout map_error_layout(int rows, int cols, const MapErrorWants& 
 inline int map_error_window(int win_size, int cols, int max_win) {
   if (win_size == 0) return cols < 640 ? 5 : 11;
   return (win_size >= 1 && win_size <= max_win && win_size % 2 == 1) ? win_size : 0;
+}
+
+// Which outputs a view-renderer call asks for (flame_nltgv2_view_params), and whether they travel to the host at all.
+struct ViewWants {
+  bool map, tri_index, copy_out;
+};
+constexpr size_t kViewCountBytes = 4 * sizeof(int32_t);  // flame_nltgv2_view_counts
+struct ViewLayout {
+  // the counters | rows*cols floats | rows*cols int32.  The counters are always there; the map and the owner indices take room only
+  // if wanted and copy_out.
+  size_t counts, map, tri_index, total;
+};
+inline ViewLayout view_layout(int rows, int cols, const ViewWants& w) {
+  const size_t n = (size_t)rows * (size_t)cols;
+  ViewLayout v;
+  v.counts = 0;
+  v.map = up16(kViewCountBytes);
+  v.tri_index = v.map + up16(w.copy_out && w.map ? sizeof(float) * n : 0);
+  v.total = v.tri_index + up16(w.copy_out && w.tri_index ? sizeof(int32_t) * n : 0) + 16;
+  return v;
 }
 
 // Every index of T triangles names one of V vertices.

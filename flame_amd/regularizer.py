@@ -170,6 +170,35 @@ class _MapErrorView(C.Structure):
                 ("error_map_device", C.c_void_p), ("image", C.POINTER(C.c_uint8)), ("image_device", C.c_void_p)]
 
 
+class ViewParams(C.Structure):
+    """== flame_nltgv2_view_params (same defaults): the camera the mesh is rendered into -- Kinv_src, K_dst, R (3x3 each) and t (3) with
+    P_dst = R P_src + t --, near_depth, where the triangle validity comes from (0: all valid, 1: a host array, 2: what the last
+    mesh_outputs_begin left on the device), which outputs, and whether they travel to the host."""
+
+    _fields_ = [("Kinv_src", C.c_float * 9), ("K_dst", C.c_float * 9), ("R", C.c_float * 9), ("t", C.c_float * 3), ("near_depth", C.c_float),
+                ("validity", C.c_int32), ("want_map", C.c_int32), ("want_tri_index", C.c_int32), ("copy_out", C.c_int32)]
+
+    def __init__(self, Kinv_src=None, K_dst=None, R=None, t=None, near_depth=0.0, validity=0, want_map=True, want_tri_index=True, copy_out=True):
+        super().__init__()
+        eye = np.eye(3, dtype=np.float32)
+        for name, m in (("Kinv_src", Kinv_src), ("K_dst", K_dst), ("R", R)):
+            setattr(self, name, (C.c_float * 9)(*np.ascontiguousarray(eye if m is None else m, np.float32).reshape(9).tolist()))
+        self.t = (C.c_float * 3)(*np.ascontiguousarray(np.zeros(3) if t is None else t, np.float32).reshape(3).tolist())
+        self.near_depth, self.validity = float(near_depth), int(validity)
+        self.want_map, self.want_tri_index, self.copy_out = (int(bool(v)) for v in (want_map, want_tri_index, copy_out))
+
+
+class ViewCounts(C.Structure):
+    """== flame_nltgv2_view_counts."""
+
+    _fields_ = [("coverage", C.c_int32), ("tris_drawn", C.c_int32), ("tris_culled_vertex", C.c_int32), ("tris_culled_facing", C.c_int32)]
+
+
+class _ViewOutputsView(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("T", C.c_int32), ("counts", ViewCounts), ("device_ms", C.c_float), ("map", _FP),
+                ("map_device", C.c_void_p), ("tri_index", _IP), ("tri_index_device", C.c_void_p)]
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -260,6 +289,8 @@ ABI_SYMBOLS = (
     "flame_nltgv2_default_metric_params", "flame_nltgv2_metric_outputs_begin", "flame_nltgv2_metric_outputs_end",
     "flame_nltgv2_metric_outputs",
     "flame_nltgv2_default_map_error_params", "flame_nltgv2_map_error_begin", "flame_nltgv2_map_error_end", "flame_nltgv2_map_error",
+    "flame_nltgv2_default_view_params", "flame_nltgv2_render_view_begin", "flame_nltgv2_render_view_end", "flame_nltgv2_render_view",
+    "flame_nltgv2_render_view_arrays",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -351,6 +382,13 @@ def load_library():
         "flame_nltgv2_map_error_end": (C.c_int, [ctx, C.POINTER(_MapErrorView)]),
         "flame_nltgv2_map_error": (C.c_int, [ctx, C.POINTER(MapErrorParams), C.c_int, C.c_int, _FP, C.POINTER(C.c_uint8),
                                              C.POINTER(MapErrorStats)]),
+        "flame_nltgv2_default_view_params": (None, [C.POINTER(ViewParams)]),
+        "flame_nltgv2_render_view_begin": (C.c_int, [ctx, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int, C.c_float]),
+        "flame_nltgv2_render_view_end": (C.c_int, [ctx, C.POINTER(_ViewOutputsView)]),
+        "flame_nltgv2_render_view": (C.c_int, [ctx, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int, C.c_float, _FP, _IP,
+                                               C.POINTER(ViewCounts)]),
+        "flame_nltgv2_render_view_arrays": (C.c_int, [ctx, C.POINTER(ViewParams), _IP, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p, C.c_int,
+                                                      C.c_int, _FP, _IP, C.POINTER(ViewCounts)]),
         "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
         "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
                                                       C.c_int]),
@@ -799,6 +837,53 @@ class Regularizer:
         """map_error_begin; map_error_end."""
         self.map_error_begin(params, rows, cols)
         return self.map_error_end()
+
+    # -- the mesh rendered into another camera (flame_nltgv2_render_view*) --------------------------------------------------------------
+    def render_view_begin(self, params: ViewParams, rows, cols, graph_scale=1.0, tri_valid=None):
+        """Enqueues the resident triangles over the state's pos / x, seen from the camera of `params`, on the side stream and returns.
+        rows x cols is the target's size.  tri_valid: a (T,) u8 array, for params.validity == 1."""
+        tv = None if tri_valid is None else np.ascontiguousarray(tri_valid, np.uint8)
+        self._chk(self._L.flame_nltgv2_render_view_begin(self._ctx, C.byref(params), None if tv is None else C.c_void_p(tv.ctypes.data), rows, cols,
+                                                         C.c_float(graph_scale)), "render_view_begin")
+
+    def render_view_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(rows, cols, T, coverage, tris_drawn, tris_culled_vertex, tris_culled_facing, device_ms,
+        device = {name: address} and, as asked for, map (rows, cols) f32 with NaN on holes, tri_index (rows, cols) i32 with -1 on
+        holes).  copy=False: views of the context's pinned memory, valid until the next begin.  With ViewParams(copy_out=False) only
+        the counters and the addresses are there."""
+        v = _ViewOutputsView()
+        self._chk(self._L.flame_nltgv2_render_view_end(self._ctx, C.byref(v)), "render_view_end")
+        take = (lambda a: a.copy()) if copy else (lambda a: a)
+        out = dict(rows=int(v.rows), cols=int(v.cols), T=int(v.T), device_ms=float(v.device_ms), device={})
+        out.update({k: int(getattr(v.counts, k)) for k, _ in ViewCounts._fields_})
+        for name in ("map", "tri_index"):
+            dev = getattr(v, name + "_device")
+            if dev:
+                out["device"][name] = int(dev)
+            if getattr(v, name):
+                out[name] = take(np.ctypeslib.as_array(getattr(v, name), shape=(v.rows, v.cols)))
+        return out
+
+    def render_view(self, params: ViewParams, rows, cols, graph_scale=1.0, tri_valid=None) -> dict:
+        """render_view_begin; render_view_end."""
+        self.render_view_begin(params, rows, cols, graph_scale, tri_valid)
+        return self.render_view_end()
+
+    def render_view_arrays(self, params: ViewParams, triangles, vertices, idepths, rows, cols, tri_valid=None) -> dict:
+        """The same for a mesh of the caller's (a pose-frame's stored triangles, vertices and idepths), synchronously; the resident
+        triangles and maps stay as they are.  -> dict(map, tri_index, coverage, tris_drawn, tris_culled_vertex, tris_culled_facing)."""
+        tr = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        xy = np.ascontiguousarray(vertices, np.float32).reshape(-1, 2)
+        val = _as(idepths, np.float32, xy.shape[0], "idepths")
+        tv = None if tri_valid is None else np.ascontiguousarray(tri_valid, np.uint8)
+        img, idx, cnt = np.empty((rows, cols), np.float32), np.empty((rows, cols), np.int32), ViewCounts()
+        self._chk(self._L.flame_nltgv2_render_view_arrays(
+            self._ctx, C.byref(params), tr.ctypes.data_as(_IP), tr.shape[0], xy.ctypes.data_as(_FP), val.ctypes.data_as(_FP), xy.shape[0],
+            None if tv is None else C.c_void_p(tv.ctypes.data), rows, cols, img.ctypes.data_as(_FP), idx.ctypes.data_as(_IP), C.byref(cnt)),
+            "render_view_arrays")
+        out = dict(map=img, tri_index=idx)
+        out.update({k: int(getattr(cnt, k)) for k, _ in ViewCounts._fields_})
+        return out
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

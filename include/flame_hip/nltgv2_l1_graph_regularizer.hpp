@@ -256,6 +256,23 @@ struct MapError {
   const uint8_t* debug_img_photo_error = nullptr;       const void* image_device = nullptr;      // [rows * cols * 3]
 };
 
+// The camera the mesh is rendered into and what is wanted of it (flame_nltgv2_view_params, constructed with its defaults): Kinv_src,
+// K_dst, R, t with P_dst = R * P_src + t, near_depth, where the triangle validity comes from, which outputs, and whether they travel
+// to the host.  The C-ABI struct itself: the header states every rule.
+struct ViewParams : flame_nltgv2_view_params {
+  ViewParams() { flame_nltgv2_default_view_params(this); }
+};
+
+// The mesh seen from another camera (flame_nltgv2_view_outputs_view): the inverse depth of the nearest surface per pixel (NaN on
+// holes), the triangle that owns the pixel (-1 on holes) and the counters.  Host pointers into pinned memory of the DeviceGraph and the
+// device pointers of the same arrays; all valid until its next renderViewBegin().
+struct RenderedView {
+  int rows = 0, cols = 0, num_triangles = 0;
+  flame_nltgv2_view_counts counts = {0, 0, 0, 0};
+  const float* idepthmap = nullptr;    const void* idepthmap_device = nullptr;  // [rows * cols]
+  const int32_t* tri_index = nullptr;  const void* tri_index_device = nullptr;  // [rows * cols]
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -465,6 +482,26 @@ class DeviceGraph {
     m.error = v.error_map, m.error_device = v.error_map_device;
     m.debug_img_photo_error = v.image, m.image_device = v.image_device;
     return m;
+  }
+
+  // The triangles the last interpolateMesh[Begin] / meshOutputsBegin left on the device over the state's positions and x * graph_scale,
+  // seen from the camera of `params`, on the side stream (flame_nltgv2_render_view_begin / _end; the rules are stated there).
+  // rows x cols: the target's size.  tri_validity: a host array of one byte per triangle with params.validity == 1, else nullptr.
+  void renderViewBegin(const ViewParams& params, const uint8_t* tri_validity, int rows, int cols, float graph_scale) {
+    check(flame_nltgv2_render_view_begin(ctx_, &params, tri_validity, rows, cols, graph_scale), "render_view_begin");
+  }
+  RenderedView renderViewEnd() {
+    flame_nltgv2_view_outputs_view v;
+    check(flame_nltgv2_render_view_end(ctx_, &v), "render_view_end");
+    RenderedView r;
+    r.rows = v.rows, r.cols = v.cols, r.num_triangles = v.T, r.counts = v.counts;
+    r.idepthmap = v.map, r.idepthmap_device = v.map_device;
+    r.tri_index = v.tri_index, r.tri_index_device = v.tri_index_device;
+    return r;
+  }
+  RenderedView renderView(const ViewParams& params, const uint8_t* tri_validity, int rows, int cols, float graph_scale) {
+    renderViewBegin(params, tri_validity, rows, cols, graph_scale);
+    return renderViewEnd();
   }
 
   // drawInverseDepthMap (flame.cc:2699-2719) and interpolateMesh(w1), interpolateMesh(w2), drawNormals (flame.cc:497-506, 2667-2697) over

@@ -564,6 +564,103 @@ int flame_nltgv2_map_error_end(flame_nltgv2_ctx* ctx, flame_nltgv2_map_error_vie
 int flame_nltgv2_map_error(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_error_params* params, int rows, int cols,
                            float* error_map_out, uint8_t* image_out, flame_nltgv2_map_error_stats* stats_out);
 
+/* ---- The mesh rendered into another camera ------------------------------------------------------------------------------------------------
+ * Every other output is tied to the camera and the instant of the frame the solver works on.  This stage looks at the mesh -- a 3-D
+ * surface -- from anywhere else: depth registered to a second camera with its own intrinsics and size, the map predicted at a newer
+ * pose, or the current mesh in the previous pose-frame's view, whose difference to the map that pose-frame kept
+ * (flame_nltgv2_map_error_begin, TRUTH, truth_device) measures consistency where there is no true map.  The reference has no
+ * counterpart, so the rules are stated here in full; tests/view_ref.py restates them in numpy float32 and Python integers and is the
+ * checker: device and checker agree bit for bit.  It is not the rasteriser of flame_nltgv2_interpolate_mesh: in its own view the mesh
+ * never overlaps itself and "the later triangle wins" on whole-pixel vertices; from another viewpoint the surface folds over itself,
+ * so here the NEAREST wins and vertices keep 1/16 pixel.
+ *
+ * All arithmetic is float32 without FMA; every sum of three products is taken left to right, (a + b) + c.
+ * Inputs: vertices pos[v] in source pixels; id[v] = x[v] * graph_scale (the _arrays form: the caller's idepths); triangles (a, b, c)
+ * with optional validity; Kinv_src, K_dst, R (9 floats each, row-major) and t (3 floats) with P_dst = R * P_src + t; a target of
+ * rows x cols pixels, each in 1 .. 32767, which need not be the source's size; near_depth.
+ *   1 vertex      q = Kinv_src * (pos.x, pos.y, 1); P = q / id (three divisions); P' = R * P, then + t per component; h = K_dst * P';
+ *                 u = h.x / h.z, w = h.y / h.z; sx = u * 16.0f, sy = w * 16.0f.  The vertex is USABLE iff id > 0.0f, P'.z > near_depth,
+ *                 fabsf(sx) <= 1048576.0f and fabsf(sy) <= 1048576.0f (every comparison with a NaN is false), and its source position
+ *                 keeps the same bound: fabsf(pos.x * 16.0f), fabsf(pos.y * 16.0f) <= 1048576.0f.  Then X = (int)rintf(sx),
+ *                 Y = (int)rintf(sy), Xs = (int)rintf(pos.x * 16.0f), Ys = (int)rintf(pos.y * 16.0f) -- ties to even, positions in 1/16
+ *                 pixel -- and id' = 1.0f / P'.z.
+ *   2 triangle    drawn iff its validity byte is non-zero (where validity is in force), all three vertices are usable, and the doubled
+ *                 signed areas A = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) and As, the same on Xs, Ys, both exact in int64, are both
+ *                 non-zero and of the same sign: a triangle whose orientation flipped is seen from behind and culled.  No clipping: a
+ *                 triangle with an unusable vertex is dropped whole.
+ *   3 coverage    pixel centres lie at integer pixel coordinates, (16 col, 16 row).  s = sign(A); w_a = s * E(b, c), w_b = s * E(c, a),
+ *                 w_c = s * E(a, b) with E(i, j) = (Xj - Xi)(16 row - Yi) - (Yj - Yi)(16 col - Xi) in int64.  A pixel inside the image
+ *                 is covered iff all three weights are >= 0, edges and corners included.  Nothing outside the image is touched.
+ *   4 value       val = (id'_a * (float)w_a + (id'_b * (float)w_b + id'_c * (float)w_c)) / (float)|A|, every int64 -> float conversion
+ *                 rounding to nearest even.  A covered pixel is a CANDIDATE iff val > 0.0f && val < +infinity.
+ *   5 depth test  the candidate with the largest val owns the pixel (the nearest surface); among equal bit patterns the larger triangle
+ *                 index.  One 64-bit integer maximum over {bits(val) << 32 | (t + 1)}; the key image is cleared per call, and the
+ *                 result does not depend on scheduling: two calls give the same bytes.
+ *   6 outputs     map: rows * cols floats, the owner's val, the quiet NaN 0x7fc00000 on holes.  tri_index: rows * cols int32, the
+ *                 owner's triangle index, -1 on holes (a consumer interpolates colour or normals in the target view with it).  The
+ *                 counters: coverage = the non-hole pixels; tris_drawn, tris_culled_vertex (a vertex not usable), tris_culled_facing
+ *                 (zero area in either view, or flipped) -- a triangle whose validity byte is zero is in none of the three.
+ * want_map, want_tri_index, copy_out as in the metric stage: with copy_out == 0 only the counters travel (16 bytes) and map_device /
+ * tri_index_device of the view serve flame_nltgv2_metric_params.map_device, flame_nltgv2_map_error_params.map_device / truth_device.
+ * Not done: clipping against the near plane, anti-aliasing, lens distortion of the target camera. */
+typedef struct flame_nltgv2_view_params {
+  float   Kinv_src[9];     /* identity  the source camera's inverse intrinsics (Flame::Kinv_) */
+  float   K_dst[9];        /* identity  the target camera's intrinsics */
+  float   R[9];            /* identity  P_dst = R * P_src + t */
+  float   t[3];            /* 0 */
+  float   near_depth;      /* 0.0       a vertex at or below this depth in the target camera is not usable */
+  int32_t validity;        /* 0: every triangle is valid (tri_valid must be NULL); 1: tri_valid is a host array of T bytes;
+                              2: the validity the last flame_nltgv2_mesh_outputs_begin left on the device for the resident
+                                 triangles (tri_valid must be NULL; an error if there is none for the current triangles and topology;
+                                 an error in the _arrays form) */
+  int32_t want_map;        /* 1 */
+  int32_t want_tri_index;  /* 1 */
+  int32_t copy_out;        /* 1  0: the outputs stay on the device; only the counters travel */
+} flame_nltgv2_view_params;
+void flame_nltgv2_default_view_params(flame_nltgv2_view_params* p);
+
+/* The counters, as they lie on the device and in pinned memory. */
+typedef struct flame_nltgv2_view_counts {
+  int32_t coverage, tris_drawn, tris_culled_vertex, tris_culled_facing;
+} flame_nltgv2_view_counts;
+
+/* Pointers into pinned memory of the context and the device pointers of the same arrays; all valid until the next
+ * flame_nltgv2_render_view_begin or flame_nltgv2_render_view_arrays.  What was not asked for has two NULLs; with copy_out == 0 every
+ * host pointer is NULL. */
+typedef struct flame_nltgv2_view_outputs_view {
+  int32_t rows, cols, T;
+  flame_nltgv2_view_counts counts;
+  float   device_ms;                 /* measurement aid: HIP-event time of what begin enqueued on the side stream, kernels and copies out */
+  const float* map;                  const void* map_device;        /* [rows * cols] */
+  const int32_t* tri_index;          const void* tri_index_device;  /* [rows * cols] */
+} flame_nltgv2_view_outputs_view;
+
+/* begin  checks the arguments -- an error (no graph; params NULL; rows or cols outside 1 .. 32767; no resident triangles for the current
+ *        topology; validity outside 0 .. 2; a tri_valid pointer with validity != 1 or none with validity == 1; validity == 2 without a
+ *        matching flame_nltgv2_mesh_outputs_begin) is reported before anything is enqueued and leaves the outputs of an earlier begin,
+ *        and its pending _end, as they are --, then enqueues everything on the context's side stream, beside a running solver, and
+ *        returns.  The triangles are the ones the last flame_nltgv2_interpolate_mesh[_begin] or flame_nltgv2_mesh_outputs_begin left on
+ *        the device; pos and x are read from the state flame_nltgv2_interpolate_mesh_begin would read (FLAME_NLTGV2_OPT_MESH_STATE
+ *        decides in the same way).  Only the vertex kernel reads pos / x: whoever rewrites them waits for that kernel, not for the
+ *        picture.  The stage only READS the buffers of the other stages, and they leave this stage's alone.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_render_view == begin (with copy_out forced to 1 and the want_* flags replaced by: the array is not NULL); end; copies into
+ *        the caller's arrays: map_out rows * cols floats, tri_index_out rows * cols int32, *counts_out (each may be NULL).
+ * flame_nltgv2_render_view_arrays  the same for a mesh of the caller's, synchronously: T triangles that index V vertices_xy (2V floats,
+ *        source pixels) with V idepths -- a pose-frame's stored mesh, curr_pf_->tris / vtx / vtx_idepths --, tri_valid NULL or T bytes
+ *        (params->validity must say 0 or 1 accordingly).  An error (also: T or V negative, a missing array, an index outside 0 .. V - 1)
+ *        is reported before anything is enqueued.  It needs no graph and uses this stage's buffers only: the resident triangles, the
+ *        rasteriser's key image and the resident maps stay as they are; what a pending flame_nltgv2_render_view_end would have returned
+ *        is replaced by this call's outputs. */
+int flame_nltgv2_render_view_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params* params, const uint8_t* tri_valid, int rows,
+                                   int cols, float graph_scale);
+int flame_nltgv2_render_view_end(flame_nltgv2_ctx* ctx, flame_nltgv2_view_outputs_view* out);
+int flame_nltgv2_render_view(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params* params, const uint8_t* tri_valid, int rows, int cols,
+                             float graph_scale, float* map_out, int32_t* tri_index_out, flame_nltgv2_view_counts* counts_out);
+int flame_nltgv2_render_view_arrays(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params* params, const int32_t* triangles, int32_t T,
+                                    const float* vertices_xy, const float* idepths, int32_t V, const uint8_t* tri_valid, int rows,
+                                    int cols, float* map_out, int32_t* tri_index_out, flame_nltgv2_view_counts* counts_out);
+
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
  * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
