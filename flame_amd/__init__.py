@@ -11,6 +11,9 @@ from .regularizer import (  # noqa: F401
     MAP_ERROR_PHOTO,
     MAP_ERROR_TRUTH,
     DebugImageParams,
+    FuseCounts,
+    FuseParams,
+    FuseSource,
     MapErrorParams,
     MapErrorStats,
     MeshFilterParams,

@@ -383,6 +383,23 @@ struct flame_nltgv2_ctx {
     ViewWants want{};
     ViewLayout at{};
   } view_pending;
+  // flame_nltgv2_keep_mesh / _keep_mesh_arrays / _drop_mesh: the meshes pose-frames keep (flame.cc:417-426), written and read on the
+  // side stream only.  V < 0: the slot is empty (its buffers stay for the next mesh).
+  struct KeptMesh {
+    DevBuf pos, id, tris, valid;
+    int32_t V = -1, T = -1;
+    bool has_valid = false;
+  } kept[FLAME_NLTGV2_KEPT_MESHES];
+  // flame_nltgv2_fuse_views_begin / _end (fuse_kernels.hip): key layers, vertices, big list, device outputs, pinned outputs and timing
+  // events of its own; the kept slots, the resident triangles, the filters' validity and the canonical pos / x are only read.
+  // Pinned: fuse_layout
+  DevBuf f_vtx, f_keys, f_counts, f_big, f_fused, f_pmask, f_imask, f_spread, f_layers;
+  SideStage fuse;
+  struct FusePending {
+    int rows = 0, cols = 0, n_sources = 0;
+    FuseWants want{};
+    FuseLayout at{};
+  } fuse_pending;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

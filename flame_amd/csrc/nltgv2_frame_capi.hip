@@ -6,8 +6,10 @@
 //   the metric outputs        metric_outputs_begin / _end: depth image, millimetre image, point clouds, 3-D mesh
 //   the map error             map_error_begin / _end: photometric or against a true map; box mean, histogram, ranks, sum, picture
 //   the view renderer         render_view_begin / _end, render_view_arrays: the mesh seen from another camera, the nearest surface kept
+//   the kept meshes           keep_mesh, keep_mesh_arrays, drop_mesh, kept_mesh_info, get_kept_mesh: what a pose-frame keeps of its mesh
+//   the fusion of views       fuse_views_begin / _end: up to eight kept or live meshes in one camera, a vote per pixel
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
-// The seven begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// The eight begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
 // they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
 // the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
@@ -16,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "debug_kernels.h"
+#include "fuse_kernels.h"
 #include "map_error_kernels.h"
 #include "mesh_kernels.h"
 #include "metric_kernels.h"
@@ -99,6 +102,9 @@ static_assert(sizeof(flame_hip::MapErrorStats) == sizeof(flame_nltgv2_map_error_
               "the statistics on the device, in the header and in map_error_layout are one struct");
 static_assert(sizeof(flame_hip::ViewCounts) == sizeof(flame_nltgv2_view_counts) && sizeof(flame_nltgv2_view_counts) == kViewCountBytes,
               "the counters on the device, in the header and in view_layout are one struct");
+static_assert(sizeof(flame_hip::FuseCounts) == sizeof(flame_nltgv2_fuse_counts) && sizeof(flame_nltgv2_fuse_counts) == kFuseCountBytes,
+              "the counters on the device, in the header and in fuse_layout are one struct");
+static_assert(flame_hip::kFuseSources == FLAME_NLTGV2_FUSE_SOURCES, "the kernels' and the header's number of sources");
 
 extern "C" {
 
@@ -921,6 +927,285 @@ int flame_nltgv2_render_view_arrays(flame_nltgv2_ctx* ctx, const flame_nltgv2_vi
   rc = view_enqueue(ctx, p, m, rows, cols);
   if (rc) return rc;
   return view_finish(ctx, map_out, tri_index_out, counts_out);
+}
+
+// ---- the kept meshes (see flame_nltgv2.h) ----------------------------------------------------------------------------------------------
+static bool slot_ok(int32_t slot) { return slot >= 0 && slot < FLAME_NLTGV2_KEPT_MESHES; }
+
+// The slot's buffers hold V vertices and T triangles.  The side stream may still hold a fusion that reads the slot, or a snapshot that
+// writes it.  A buffer that is large enough is reused, and stream order covers both.  A buffer that must grow is replaced by ensure(),
+// which releases the old one with hipFree: hipFree returns only after the device has finished all work enqueued before it, on every
+// stream (ensure asks an open run to stop first, so that the wait is short).  That guarantee is the one relied on here; the slot keeps
+// no event of its own.
+static int kept_reserve(flame_nltgv2_ctx* ctx, flame_nltgv2_ctx::KeptMesh& k, int32_t V, int32_t T, bool valid) {
+  int rc = ensure(ctx, k.pos, sizeof(float) * 2 * (size_t)V + 16);
+  if (!rc) rc = ensure(ctx, k.id, sizeof(float) * (size_t)V + 16);
+  if (!rc) rc = ensure(ctx, k.tris, sizeof(int32_t) * 3 * (size_t)T + 16);
+  if (!rc && valid) rc = ensure(ctx, k.valid, (size_t)T + 16);
+  return rc;
+}
+
+int flame_nltgv2_keep_mesh(flame_nltgv2_ctx* ctx, int32_t slot, float graph_scale, int32_t validity) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_keep_mesh");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!slot_ok(slot)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (validity != 0 && validity != 2) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (validity == 2 && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t V = ctx->L.V, T = ctx->tris.T();
+  flame_nltgv2_ctx::KeptMesh& k = ctx->kept[slot];
+  k.V = k.T = -1, k.has_valid = false;  // (from here on the slot is being rewritten: empty until everything is enqueued)
+  rc = kept_reserve(ctx, k, V, T, validity == 2);
+  if (rc) return rc;
+  hipStream_t rs = ctx->raster_stream;
+  rc = mesh_state_on(ctx, rs);
+  if (rc) return rc;
+  LAUNCHCHK(ctx, flame_hip::launch_keep_vertices(V, ctx->c.pos, ctx->c.x, graph_scale, (float2*)k.pos.p, (float*)k.id.p, rs));
+  rc = side_kernels_read_last(ctx);  // the snapshot kernel is the last reader of the canonical pos / x
+  if (rc) return rc;
+  if (T > 0) HIPCHK(ctx, hipMemcpyAsync(k.tris.p, ctx->r_tris.p, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyDeviceToDevice, rs));
+  if (validity == 2 && T > 0) HIPCHK(ctx, hipMemcpyAsync(k.valid.p, ctx->m_tvalid.p, (size_t)T, hipMemcpyDeviceToDevice, rs));
+  k.V = V, k.T = T, k.has_valid = validity == 2;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_keep_mesh_arrays(flame_nltgv2_ctx* ctx, int32_t slot, const int32_t* triangles, int32_t T, const float* vertices_xy,
+                                  const float* idepths, int32_t V, const uint8_t* tri_valid) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_keep_mesh_arrays");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!slot_ok(slot) || T < 0 || V < 0 || (T > 0 && !triangles) || (V > 0 && (!vertices_xy || !idepths))) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!triangles_in_range(triangles, T, V)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  flame_nltgv2_ctx::KeptMesh& k = ctx->kept[slot];
+  k.V = k.T = -1, k.has_valid = false;
+  rc = kept_reserve(ctx, k, V, T, tri_valid != nullptr);
+  if (rc) return rc;
+  hipStream_t rs = ctx->raster_stream;
+  // (pageable memory: each copy holds the host until the bytes have left the caller's array)
+  if (V > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(k.pos.p, vertices_xy, sizeof(float) * 2 * (size_t)V, hipMemcpyHostToDevice, rs));
+    HIPCHK(ctx, hipMemcpyAsync(k.id.p, idepths, sizeof(float) * (size_t)V, hipMemcpyHostToDevice, rs));
+  }
+  if (T > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(k.tris.p, triangles, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
+    if (tri_valid) HIPCHK(ctx, hipMemcpyAsync(k.valid.p, tri_valid, (size_t)T, hipMemcpyHostToDevice, rs));
+  }
+  k.V = V, k.T = T, k.has_valid = tri_valid != nullptr;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_drop_mesh(flame_nltgv2_ctx* ctx, int32_t slot) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!slot_ok(slot)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  ctx->kept[slot].V = ctx->kept[slot].T = -1, ctx->kept[slot].has_valid = false;  // (a fusion still in flight reads the buffers, which stay)
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_kept_mesh_info(flame_nltgv2_ctx* ctx, int32_t slot, int32_t* V, int32_t* T, int32_t* has_validity) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!slot_ok(slot)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const flame_nltgv2_ctx::KeptMesh& k = ctx->kept[slot];
+  if (V) *V = k.V;
+  if (T) *T = k.T;
+  if (has_validity) *has_validity = k.has_valid ? 1 : 0;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_get_kept_mesh(flame_nltgv2_ctx* ctx, int32_t slot, float* vertices_xy, float* idepths, int32_t* triangles, uint8_t* tri_valid) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!slot_ok(slot) || ctx->kept[slot].V < 0 || (tri_valid && !ctx->kept[slot].has_valid)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const flame_nltgv2_ctx::KeptMesh& k = ctx->kept[slot];
+  hipStream_t rs = ctx->raster_stream;
+  if (vertices_xy && k.V > 0) HIPCHK(ctx, hipMemcpyAsync(vertices_xy, k.pos.p, sizeof(float) * 2 * (size_t)k.V, hipMemcpyDeviceToHost, rs));
+  if (idepths && k.V > 0) HIPCHK(ctx, hipMemcpyAsync(idepths, k.id.p, sizeof(float) * (size_t)k.V, hipMemcpyDeviceToHost, rs));
+  if (triangles && k.T > 0) HIPCHK(ctx, hipMemcpyAsync(triangles, k.tris.p, sizeof(int32_t) * 3 * (size_t)k.T, hipMemcpyDeviceToHost, rs));
+  if (tri_valid && k.T > 0) HIPCHK(ctx, hipMemcpyAsync(tri_valid, k.valid.p, (size_t)k.T, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipStreamSynchronize(rs));
+  return FLAME_NLTGV2_OK;
+}
+
+// ---- the fusion of views (see flame_nltgv2.h) --------------------------------------------------------------------------------------------
+void flame_nltgv2_default_fuse_params(flame_nltgv2_fuse_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->n_sources = 1;
+  for (flame_nltgv2_fuse_source& s : p->sources) {
+    s.slot = -1, s.graph_scale = 1.0f, s.weight = 1.0f;
+    s.Kinv_src[0] = s.Kinv_src[4] = s.Kinv_src[8] = 1.0f;
+    s.R[0] = s.R[4] = s.R[8] = 1.0f;
+  }
+  p->K_dst[0] = p->K_dst[4] = p->K_dst[8] = 1.0f;
+  p->rel_tol = 0.05f;
+  p->min_support = 1;
+  p->want_fused = p->want_masks = p->want_spread = p->copy_out = 1;
+}
+
+int flame_nltgv2_fuse_views_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_params* params, int rows, int cols) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_fuse_views_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!params || !view_size_ok(rows, cols)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const flame_nltgv2_fuse_params& p = *params;
+  const int N = p.n_sources;
+  if (N < 1 || N > FLAME_NLTGV2_FUSE_SOURCES) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!std::isfinite(p.rel_tol) || p.rel_tol < 0.0f || p.min_support < 1 || p.min_support > N) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  int live = -1;
+  for (int s = 0; s < N; ++s) {
+    const flame_nltgv2_fuse_source& src = p.sources[s];
+    if (!(std::isfinite(src.weight) && src.weight > 0.0f)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    if (src.slot == -1) {
+      if (live >= 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      live = s;
+      if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+      if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      if (src.validity != 0 && src.validity != 2) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      if (src.validity == 2 && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    } else if (!slot_ok(src.slot) || ctx->kept[src.slot].V < 0) {
+      return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    }
+  }
+  // the source table: cameras, device meshes, prefix sums of V and T
+  flame_hip::FuseTable tab;
+  std::memset(&tab, 0, sizeof(tab));
+  tab.n = N;
+  int64_t v_sum = 0, t_sum = 0;
+  for (int s = 0; s < N; ++s) {
+    const flame_nltgv2_fuse_source& src = p.sources[s];
+    flame_hip::FuseSource& o = tab.s[s];
+    std::memcpy(o.cam.Kinv_src, src.Kinv_src, sizeof(o.cam.Kinv_src));
+    std::memcpy(o.cam.K_dst, p.K_dst, sizeof(o.cam.K_dst));
+    std::memcpy(o.cam.R, src.R, sizeof(o.cam.R));
+    std::memcpy(o.cam.t, src.t, sizeof(o.cam.t));
+    o.cam.near_depth = p.near_depth;
+    o.weight = src.weight;
+    int32_t V, T;
+    if (s == live) {
+      V = ctx->L.V, T = ctx->tris.T();
+      o.pos = ctx->c.pos, o.values = ctx->c.x, o.tris = (const int32_t*)ctx->r_tris.p;
+      o.tri_valid = src.validity == 2 ? (const uint8_t*)ctx->m_tvalid.p : nullptr;
+      o.value_scale = src.graph_scale;
+    } else {
+      const flame_nltgv2_ctx::KeptMesh& k = ctx->kept[src.slot];
+      V = k.V, T = k.T;
+      o.pos = (const float2*)k.pos.p, o.values = (const float*)k.id.p, o.tris = (const int32_t*)k.tris.p;
+      o.tri_valid = k.has_valid ? (const uint8_t*)k.valid.p : nullptr;
+      o.value_scale = 1.0f;  // (id * 1.0f == id: what the snapshot stored)
+    }
+    o.v0 = (int32_t)v_sum, o.t0 = (int32_t)t_sum;
+    v_sum += V, t_sum += T;
+    if (v_sum > INT32_MAX / 4 || t_sum > INT32_MAX / 4) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (3 t and 2 + 2 t stay ints)
+  }
+  tab.v_end = (int32_t)v_sum, tab.t_end = (int32_t)t_sum;
+
+  const size_t n = (size_t)rows * (size_t)cols;
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::FusePending fp;
+  fp.rows = rows, fp.cols = cols, fp.n_sources = N;
+  fp.want.fused = p.want_fused != 0, fp.want.masks = p.want_masks != 0, fp.want.spread = p.want_spread != 0;
+  fp.want.layers = p.want_layers != 0, fp.want.copy_out = p.copy_out != 0;
+  fp.at = fuse_layout(rows, cols, N, fp.want);
+  rc = open_stage(ctx, ctx->fuse, fp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->f_vtx, sizeof(flame_hip::ViewVertex) * (size_t)tab.v_end + 16);
+  if (!rc) rc = ensure(ctx, ctx->f_keys, sizeof(unsigned long long) * n * (size_t)N);
+  if (!rc) rc = ensure(ctx, ctx->f_counts, sizeof(flame_hip::FuseCounts));
+  if (!rc) rc = ensure(ctx, ctx->f_big, sizeof(int) * (2 * (size_t)tab.t_end + 2));
+  if (!rc && fp.want.fused) rc = ensure(ctx, ctx->f_fused, sizeof(float) * n);
+  if (!rc && fp.want.masks) rc = ensure(ctx, ctx->f_pmask, n);
+  if (!rc && fp.want.masks) rc = ensure(ctx, ctx->f_imask, n);
+  if (!rc && fp.want.spread) rc = ensure(ctx, ctx->f_spread, sizeof(float) * n);
+  if (!rc && fp.want.layers) rc = ensure(ctx, ctx->f_layers, sizeof(float) * n * (size_t)N);
+  if (rc) return rc;
+  ctx->fuse.active = false;  // (from here on the pinned outputs are being rewritten)
+  if (live >= 0) {
+    rc = mesh_state_on(ctx, rs);
+    if (rc) return rc;
+  }
+  flame_hip::ViewVertex* vtx = (flame_hip::ViewVertex*)ctx->f_vtx.p;
+  unsigned long long* keys = (unsigned long long*)ctx->f_keys.p;
+  flame_hip::FuseCounts* counts = (flame_hip::FuseCounts*)ctx->f_counts.p;
+  int* big = (int*)ctx->f_big.p;
+  HIPCHK(ctx, hipEventRecord(ctx->fuse.ev0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_fuse_vertices(tab, vtx, rs));
+  if (live >= 0) {  // the vertex kernel is the last reader of the canonical pos / x
+    rc = side_kernels_read_last(ctx);
+    if (rc) return rc;
+  }
+  LAUNCHCHK(ctx, flame_hip::launch_fuse_clear((long)(n * (size_t)N), keys, counts, big, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_fuse_raster(tab, vtx, keys, counts, big, rows, cols, rs));
+  flame_hip::FuseOutputs out;
+  out.fused = fp.want.fused ? (float*)ctx->f_fused.p : nullptr;
+  out.present_mask = fp.want.masks ? (uint8_t*)ctx->f_pmask.p : nullptr;
+  out.inlier_mask = fp.want.masks ? (uint8_t*)ctx->f_imask.p : nullptr;
+  out.spread = fp.want.spread ? (float*)ctx->f_spread.p : nullptr;
+  out.layers = fp.want.layers ? (float*)ctx->f_layers.p : nullptr;
+  LAUNCHCHK(ctx, flame_hip::launch_fuse_vote(tab, (long)n, keys, p.rel_tol, p.min_support, out, counts, rs));
+  char* h = ctx->fuse.h.p;
+  HIPCHK(ctx, hipMemcpyAsync(h + fp.at.counts, counts, sizeof(flame_hip::FuseCounts), hipMemcpyDeviceToHost, rs));
+  if (fp.want.copy_out) {
+    if (fp.want.fused) HIPCHK(ctx, hipMemcpyAsync(h + fp.at.fused, out.fused, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    if (fp.want.masks) {
+      HIPCHK(ctx, hipMemcpyAsync(h + fp.at.present, out.present_mask, n, hipMemcpyDeviceToHost, rs));
+      HIPCHK(ctx, hipMemcpyAsync(h + fp.at.inlier, out.inlier_mask, n, hipMemcpyDeviceToHost, rs));
+    }
+    if (fp.want.spread) HIPCHK(ctx, hipMemcpyAsync(h + fp.at.spread, out.spread, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+    if (fp.want.layers) HIPCHK(ctx, hipMemcpyAsync(h + fp.at.layers, out.layers, sizeof(float) * n * (size_t)N, hipMemcpyDeviceToHost, rs));
+  }
+  ctx->fuse_pending = fp;
+  return close_stage(ctx, ctx->fuse);
+}
+
+int flame_nltgv2_fuse_views_end(flame_nltgv2_ctx* ctx, flame_nltgv2_fuse_outputs_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_fuse_views_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::FusePending& fp = ctx->fuse_pending;
+  if (!out || !ctx->fuse.h.p || !ctx->fuse.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  const char* h = ctx->fuse.h.p;
+  const bool host = fp.want.copy_out;
+  out->rows = fp.rows, out->cols = fp.cols, out->n_sources = fp.n_sources;
+  std::memcpy(&out->counts, h + fp.at.counts, sizeof(out->counts));
+  out->device_ms = stage_ms(ctx->fuse);
+  out->fused = host && fp.want.fused ? (const float*)(h + fp.at.fused) : nullptr;
+  out->fused_device = fp.want.fused ? ctx->f_fused.p : nullptr;
+  out->present_mask = host && fp.want.masks ? (const uint8_t*)(h + fp.at.present) : nullptr;
+  out->present_mask_device = fp.want.masks ? ctx->f_pmask.p : nullptr;
+  out->inlier_mask = host && fp.want.masks ? (const uint8_t*)(h + fp.at.inlier) : nullptr;
+  out->inlier_mask_device = fp.want.masks ? ctx->f_imask.p : nullptr;
+  out->spread = host && fp.want.spread ? (const float*)(h + fp.at.spread) : nullptr;
+  out->spread_device = fp.want.spread ? ctx->f_spread.p : nullptr;
+  out->layers = host && fp.want.layers ? (const float*)(h + fp.at.layers) : nullptr;
+  out->layers_device = fp.want.layers ? ctx->f_layers.p : nullptr;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_params* params, int rows, int cols, float* fused_out,
+                            uint8_t* present_mask_out, uint8_t* inlier_mask_out, float* spread_out, float* layers_out,
+                            flame_nltgv2_fuse_counts* counts_out) {
+  flame_nltgv2_fuse_params p;
+  flame_nltgv2_default_fuse_params(&p);
+  if (params) p = *params;
+  p.want_fused = fused_out != nullptr, p.want_masks = present_mask_out != nullptr || inlier_mask_out != nullptr;
+  p.want_spread = spread_out != nullptr, p.want_layers = layers_out != nullptr, p.copy_out = 1;
+  int rc = flame_nltgv2_fuse_views_begin(ctx, params ? &p : nullptr, rows, cols);
+  if (rc) return rc;
+  flame_nltgv2_fuse_outputs_view v;
+  rc = flame_nltgv2_fuse_views_end(ctx, &v);
+  if (rc) return rc;
+  const size_t n = (size_t)v.rows * (size_t)v.cols;
+  if (fused_out) std::memcpy(fused_out, v.fused, sizeof(float) * n);
+  if (present_mask_out) std::memcpy(present_mask_out, v.present_mask, n);
+  if (inlier_mask_out) std::memcpy(inlier_mask_out, v.inlier_mask, n);
+  if (spread_out) std::memcpy(spread_out, v.spread, sizeof(float) * n);
+  if (layers_out) std::memcpy(layers_out, v.layers, sizeof(float) * n * (size_t)v.n_sources);
+  if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
 }
 
 void flame_nltgv2_default_debug_image_params(flame_nltgv2_debug_image_params* p) {

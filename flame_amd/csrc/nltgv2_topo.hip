@@ -271,6 +271,10 @@ __global__ void __launch_bounds__(256) k_topo_rows(const TopoBuild t, const int 
       for (int i = 0; i < d; ++i) {
         const uint32_t h = row[i];
         const int e = (int)(h & ~kRole);
+        // A build that will be declined for kTopoBadEdges (a pair listed twice: deg counted both listings, one edge was added) leaves
+        // row slots that nobody wrote: whatever the allocation held before.  Such a slot names no edge of this build and must not be
+        // followed into src / dst.
+        if ((unsigned)e >= (unsigned)t.dims->n_edges || e >= t.E) continue;
         lo = min(lo, (int)cc_mix((uint32_t)((h & kRole) ? t.src[e] : t.dst[e]), t.cc_bits));
       }
     }

@@ -1,7 +1,7 @@
 // side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
-// images, the wireframe, the metric outputs, the map error, the view renderer), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
+// images, the wireframe, the metric outputs, the map error, the view renderer, the fusion of views), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
 // outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it (MetricLayout:
-// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc).
+// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc; FuseLayout: tests/cpp/fuse_layout_test.cc).
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
@@ -177,6 +177,30 @@ inline ViewLayout view_layout(int rows, int cols, const ViewWants& w) {
   v.tri_index = v.map + up16(w.copy_out && w.map ? sizeof(float) * n : 0);
   v.total = v.tri_index + up16(w.copy_out && w.tri_index ? sizeof(int32_t) * n : 0) + 16;
   return v;
+}
+
+// Which outputs a fusion call asks for (flame_nltgv2_fuse_params), and whether they travel to the host at all.
+struct FuseWants {
+  bool fused, masks, spread, layers, copy_out;
+};
+constexpr size_t kFuseCountBytes = 32 * sizeof(int32_t);  // flame_nltgv2_fuse_counts
+struct FuseLayout {
+  // the counters | rows*cols floats | rows*cols bytes | rows*cols bytes | rows*cols floats | n_sources*rows*cols floats.  The counters
+  // are always there; every other output takes room only if wanted and copy_out.
+  size_t counts, fused, present, inlier, spread, layers, total;
+};
+inline FuseLayout fuse_layout(int rows, int cols, int n_sources, const FuseWants& w) {
+  const size_t n = (size_t)rows * (size_t)cols, f = sizeof(float);
+  const bool out = w.copy_out;
+  FuseLayout l;
+  l.counts = 0;
+  l.fused = up16(kFuseCountBytes);
+  l.present = l.fused + up16(out && w.fused ? f * n : 0);
+  l.inlier = l.present + up16(out && w.masks ? n : 0);
+  l.spread = l.inlier + up16(out && w.masks ? n : 0);
+  l.layers = l.spread + up16(out && w.spread ? f * n : 0);
+  l.total = l.layers + up16(out && w.layers ? f * n * (size_t)n_sources : 0) + 16;
+  return l;
 }
 
 // Every index of T triangles names one of V vertices.

@@ -199,6 +199,61 @@ class _ViewOutputsView(C.Structure):
                 ("map_device", C.c_void_p), ("tri_index", _IP), ("tri_index_device", C.c_void_p)]
 
 
+KEPT_MESHES, FUSE_SOURCES = 16, 8
+
+
+class FuseSource(C.Structure):
+    """== flame_nltgv2_fuse_source (same defaults): slot = a kept slot or -1 for the live resident mesh (then validity 0 / 2 and
+    graph_scale apply), its weight, and its camera into the target: Kinv_src, R (3x3) and t (3) with P_dst = R P_src + t."""
+
+    _fields_ = [("slot", C.c_int32), ("validity", C.c_int32), ("graph_scale", C.c_float), ("weight", C.c_float), ("Kinv_src", C.c_float * 9),
+                ("R", C.c_float * 9), ("t", C.c_float * 3)]
+
+    def __init__(self, slot=-1, Kinv_src=None, R=None, t=None, weight=1.0, graph_scale=1.0, validity=0):
+        super().__init__()
+        eye = np.eye(3, dtype=np.float32)
+        for name, m in (("Kinv_src", Kinv_src), ("R", R)):
+            setattr(self, name, (C.c_float * 9)(*np.ascontiguousarray(eye if m is None else m, np.float32).reshape(9).tolist()))
+        self.t = (C.c_float * 3)(*np.ascontiguousarray(np.zeros(3) if t is None else t, np.float32).reshape(3).tolist())
+        self.slot, self.validity, self.graph_scale, self.weight = int(slot), int(validity), float(graph_scale), float(weight)
+
+
+class FuseParams(C.Structure):
+    """== flame_nltgv2_fuse_params (same defaults): up to FUSE_SOURCES sources, the target's K_dst and near_depth, the vote's rel_tol
+    and min_support, which outputs, and whether they travel to the host."""
+
+    _fields_ = [("n_sources", C.c_int32), ("sources", FuseSource * FUSE_SOURCES), ("K_dst", C.c_float * 9), ("near_depth", C.c_float),
+                ("rel_tol", C.c_float), ("min_support", C.c_int32), ("want_fused", C.c_int32), ("want_masks", C.c_int32),
+                ("want_spread", C.c_int32), ("want_layers", C.c_int32), ("copy_out", C.c_int32)]
+
+    def __init__(self, sources=None, K_dst=None, near_depth=0.0, rel_tol=0.05, min_support=1, want_fused=True, want_masks=True,
+                 want_spread=True, want_layers=False, copy_out=True, n_sources=None):
+        super().__init__()
+        sources = list(sources) if sources is not None else [FuseSource()]
+        for i in range(FUSE_SOURCES):
+            C.memmove(C.byref(self.sources[i]), C.byref(sources[i] if i < len(sources) else FuseSource()), C.sizeof(FuseSource))
+        self.n_sources = len(sources) if n_sources is None else int(n_sources)
+        self.K_dst = (C.c_float * 9)(*np.ascontiguousarray(np.eye(3) if K_dst is None else K_dst, np.float32).reshape(9).tolist())
+        self.near_depth, self.rel_tol, self.min_support = float(near_depth), float(rel_tol), int(min_support)
+        self.want_fused, self.want_masks, self.want_spread, self.want_layers, self.copy_out = (
+            int(bool(v)) for v in (want_fused, want_masks, want_spread, want_layers, copy_out))
+
+
+class FuseCounts(C.Structure):
+    """== flame_nltgv2_fuse_counts: 32 words."""
+
+    _fields_ = [("coverage", C.c_int32), ("support_hist", C.c_int32 * (FUSE_SOURCES + 1)), ("present", C.c_int32 * FUSE_SOURCES),
+                ("inlier", C.c_int32 * FUSE_SOURCES), ("tris_drawn", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+_FUSE_ARRAYS = (("fused", _FP), ("present_mask", C.POINTER(C.c_uint8)), ("inlier_mask", C.POINTER(C.c_uint8)), ("spread", _FP), ("layers", _FP))
+
+
+class _FuseOutputsView(C.Structure):
+    _fields_ = ([("rows", C.c_int32), ("cols", C.c_int32), ("n_sources", C.c_int32), ("device_ms", C.c_float), ("counts", FuseCounts)]
+                + [f for name, typ in _FUSE_ARRAYS for f in ((name, typ), (name + "_device", C.c_void_p))])
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -291,6 +346,8 @@ ABI_SYMBOLS = (
     "flame_nltgv2_default_map_error_params", "flame_nltgv2_map_error_begin", "flame_nltgv2_map_error_end", "flame_nltgv2_map_error",
     "flame_nltgv2_default_view_params", "flame_nltgv2_render_view_begin", "flame_nltgv2_render_view_end", "flame_nltgv2_render_view",
     "flame_nltgv2_render_view_arrays",
+    "flame_nltgv2_keep_mesh", "flame_nltgv2_keep_mesh_arrays", "flame_nltgv2_drop_mesh", "flame_nltgv2_kept_mesh_info", "flame_nltgv2_get_kept_mesh",
+    "flame_nltgv2_default_fuse_params", "flame_nltgv2_fuse_views_begin", "flame_nltgv2_fuse_views_end", "flame_nltgv2_fuse_views",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -389,6 +446,16 @@ def load_library():
                                                C.POINTER(ViewCounts)]),
         "flame_nltgv2_render_view_arrays": (C.c_int, [ctx, C.POINTER(ViewParams), _IP, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p, C.c_int,
                                                       C.c_int, _FP, _IP, C.POINTER(ViewCounts)]),
+        "flame_nltgv2_keep_mesh": (C.c_int, [ctx, C.c_int32, C.c_float, C.c_int32]),
+        "flame_nltgv2_keep_mesh_arrays": (C.c_int, [ctx, C.c_int32, _IP, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
+        "flame_nltgv2_drop_mesh": (C.c_int, [ctx, C.c_int32]),
+        "flame_nltgv2_kept_mesh_info": (C.c_int, [ctx, C.c_int32, _IP, _IP, _IP]),
+        "flame_nltgv2_get_kept_mesh": (C.c_int, [ctx, C.c_int32, _FP, _FP, _IP, C.c_void_p]),
+        "flame_nltgv2_default_fuse_params": (None, [C.POINTER(FuseParams)]),
+        "flame_nltgv2_fuse_views_begin": (C.c_int, [ctx, C.POINTER(FuseParams), C.c_int, C.c_int]),
+        "flame_nltgv2_fuse_views_end": (C.c_int, [ctx, C.POINTER(_FuseOutputsView)]),
+        "flame_nltgv2_fuse_views": (C.c_int, [ctx, C.POINTER(FuseParams), C.c_int, C.c_int, _FP, C.c_void_p, C.c_void_p, _FP, _FP,
+                                              C.POINTER(FuseCounts)]),
         "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
         "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
                                                       C.c_int]),
@@ -884,6 +951,73 @@ class Regularizer:
         out = dict(map=img, tri_index=idx)
         out.update({k: int(getattr(cnt, k)) for k, _ in ViewCounts._fields_})
         return out
+
+    # -- the meshes pose-frames keep, and their fusion in one view (flame_nltgv2_keep_mesh*, flame_nltgv2_fuse_views*) ------------------------
+    def keep_mesh(self, slot, graph_scale=1.0, validity=0):
+        """Snapshots the resident mesh (triangles, pos, x * graph_scale; validity 2: with the filters' validity) into the slot, device
+        to device on the side stream."""
+        self._chk(self._L.flame_nltgv2_keep_mesh(self._ctx, int(slot), C.c_float(graph_scale), int(validity)), "keep_mesh")
+
+    def keep_mesh_arrays(self, slot, triangles, vertices, idepths, tri_valid=None):
+        """Uploads a mesh of the caller's into the slot (a pose-frame's stored triangles, vertices and idepths)."""
+        tr = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        xy = np.ascontiguousarray(vertices, np.float32).reshape(-1, 2)
+        val = _as(idepths, np.float32, xy.shape[0], "idepths")
+        tv = None if tri_valid is None else _as(tri_valid, np.uint8, tr.shape[0], "tri_valid")
+        self._chk(self._L.flame_nltgv2_keep_mesh_arrays(self._ctx, int(slot), tr.ctypes.data_as(_IP), tr.shape[0], xy.ctypes.data_as(_FP),
+                                                        val.ctypes.data_as(_FP), xy.shape[0], None if tv is None else C.c_void_p(tv.ctypes.data)),
+                  "keep_mesh_arrays")
+
+    def drop_mesh(self, slot):
+        self._chk(self._L.flame_nltgv2_drop_mesh(self._ctx, int(slot)), "drop_mesh")
+
+    def kept_mesh_info(self, slot):
+        """-> (V, T, has_validity); (-1, -1, False) for an empty slot."""
+        V, T, hv = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self._L.flame_nltgv2_kept_mesh_info(self._ctx, int(slot), C.byref(V), C.byref(T), C.byref(hv)), "kept_mesh_info")
+        return int(V.value), int(T.value), bool(hv.value)
+
+    def get_kept_mesh(self, slot) -> dict:
+        """Downloads a slot -> dict(vertices (V,2) f32, idepths (V,) f32, triangles (T,3) i32, tri_valid (T,) u8 or None)."""
+        V, T, hv = self.kept_mesh_info(slot)
+        if V < 0:
+            raise NLTGV2Error(-1, "get_kept_mesh: the slot is empty")
+        xy, val, tr = np.empty((V, 2), np.float32), np.empty(V, np.float32), np.empty((T, 3), np.int32)
+        tv = np.empty(T, np.uint8) if hv else None
+        self._chk(self._L.flame_nltgv2_get_kept_mesh(self._ctx, int(slot), xy.ctypes.data_as(_FP), val.ctypes.data_as(_FP), tr.ctypes.data_as(_IP),
+                                                     None if tv is None else C.c_void_p(tv.ctypes.data)), "get_kept_mesh")
+        return dict(vertices=xy, idepths=val, triangles=tr, tri_valid=tv)
+
+    def fuse_views_begin(self, params: FuseParams, rows, cols):
+        """Enqueues the sources of `params` (kept slots, at most one live mesh) rendered into the target camera and the vote per pixel on
+        the side stream and returns.  rows x cols is the target's size."""
+        self._chk(self._L.flame_nltgv2_fuse_views_begin(self._ctx, None if params is None else C.byref(params), rows, cols), "fuse_views_begin")
+
+    def fuse_views_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(rows, cols, n_sources, device_ms, counts (32 i32, as they lie on the device), coverage,
+        support_hist (9), present (8), inlier (8), tris_drawn, device = {name: address} and, as asked for, fused (rows, cols) f32 with
+        NaN on holes, present_mask / inlier_mask (rows, cols) u8, spread (rows, cols) f32, layers (n_sources, rows, cols) f32).
+        copy=False: views of the context's pinned memory, valid until the next begin."""
+        v = _FuseOutputsView()
+        self._chk(self._L.flame_nltgv2_fuse_views_end(self._ctx, C.byref(v)), "fuse_views_end")
+        take = (lambda a: a.copy()) if copy else (lambda a: a)
+        c = v.counts
+        out = dict(rows=int(v.rows), cols=int(v.cols), n_sources=int(v.n_sources), device_ms=float(v.device_ms), device={},
+                   counts=np.frombuffer(bytes(c), np.int32).copy(), coverage=int(c.coverage), support_hist=list(c.support_hist),
+                   present=list(c.present), inlier=list(c.inlier), tris_drawn=int(c.tris_drawn))
+        for name, _ in _FUSE_ARRAYS:
+            dev = getattr(v, name + "_device")
+            if dev:
+                out["device"][name] = int(dev)
+            if getattr(v, name):
+                shape = (v.n_sources, v.rows, v.cols) if name == "layers" else (v.rows, v.cols)
+                out[name] = take(np.ctypeslib.as_array(getattr(v, name), shape=shape))
+        return out
+
+    def fuse_views(self, params: FuseParams, rows, cols) -> dict:
+        """fuse_views_begin; fuse_views_end."""
+        self.fuse_views_begin(params, rows, cols)
+        return self.fuse_views_end()
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

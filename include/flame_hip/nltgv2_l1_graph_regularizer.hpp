@@ -273,6 +273,27 @@ struct RenderedView {
   const int32_t* tri_index = nullptr;  const void* tri_index_device = nullptr;  // [rows * cols]
 };
 
+// The sources of a fusion, the target camera and the vote (flame_nltgv2_fuse_params, constructed with its defaults): sources[s].slot
+// names a kept mesh, or -1 the live one.  The C-ABI struct itself: the header states every rule.
+struct FuseParams : flame_nltgv2_fuse_params {
+  FuseParams() { flame_nltgv2_default_fuse_params(this); }
+};
+
+// Several meshes fused in one view (flame_nltgv2_fuse_outputs_view): the weighted mean of the sources that agree per pixel (NaN where
+// too few do), who was present and who agreed (bit s: source s), the spread of the agreeing values, the layers themselves if asked for,
+// and the counters.  Host pointers into pinned memory of the DeviceGraph and the device pointers of the same arrays; all valid until
+// its next fuseViewsBegin().
+struct FusedView {
+  int rows = 0, cols = 0, num_sources = 0;
+  flame_nltgv2_fuse_counts counts;
+  const float* idepthmap = nullptr;       const void* idepthmap_device = nullptr;     // [rows * cols]
+  const uint8_t* present_mask = nullptr;  const void* present_mask_device = nullptr;  // [rows * cols]
+  const uint8_t* inlier_mask = nullptr;   const void* inlier_mask_device = nullptr;   // [rows * cols]
+  const float* spread = nullptr;          const void* spread_device = nullptr;        // [rows * cols]
+  const float* layers = nullptr;          const void* layers_device = nullptr;        // [num_sources * rows * cols]
+  FusedView() { std::memset(&counts, 0, sizeof(counts)); }
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -502,6 +523,32 @@ class DeviceGraph {
   RenderedView renderView(const ViewParams& params, const uint8_t* tri_validity, int rows, int cols, float graph_scale) {
     renderViewBegin(params, tri_validity, rows, cols, graph_scale);
     return renderViewEnd();
+  }
+
+  // The mesh a pose-frame keeps (flame.cc:417-426, curr_pf_->tris / vtx / vtx_idepths): the resident triangles, positions and
+  // x * graph_scale into `slot` (0 .. FLAME_NLTGV2_KEPT_MESHES - 1), device to device on the side stream; with_validity: with what the
+  // last meshOutputsBegin left of the triangle filters.  dropMesh: prunePoseFrames.  (flame_nltgv2_keep_mesh / _drop_mesh)
+  void keepMesh(int slot, float graph_scale, bool with_validity = false) {
+    check(flame_nltgv2_keep_mesh(ctx_, slot, graph_scale, with_validity ? 2 : 0), "keep_mesh");
+  }
+  void dropMesh(int slot) { check(flame_nltgv2_drop_mesh(ctx_, slot), "drop_mesh"); }
+
+  // Up to FLAME_NLTGV2_FUSE_SOURCES kept meshes (and the live one) rendered into one target camera and voted per pixel, on the side
+  // stream (flame_nltgv2_fuse_views_begin / _end; the rules are stated there).  rows x cols: the target's size.
+  void fuseViewsBegin(const FuseParams& params, int rows, int cols) {
+    check(flame_nltgv2_fuse_views_begin(ctx_, &params, rows, cols), "fuse_views_begin");
+  }
+  FusedView fuseViewsEnd() {
+    flame_nltgv2_fuse_outputs_view v;
+    check(flame_nltgv2_fuse_views_end(ctx_, &v), "fuse_views_end");
+    FusedView r;
+    r.rows = v.rows, r.cols = v.cols, r.num_sources = v.n_sources, r.counts = v.counts;
+    r.idepthmap = v.fused, r.idepthmap_device = v.fused_device;
+    r.present_mask = v.present_mask, r.present_mask_device = v.present_mask_device;
+    r.inlier_mask = v.inlier_mask, r.inlier_mask_device = v.inlier_mask_device;
+    r.spread = v.spread, r.spread_device = v.spread_device;
+    r.layers = v.layers, r.layers_device = v.layers_device;
+    return r;
   }
 
   // drawInverseDepthMap (flame.cc:2699-2719) and interpolateMesh(w1), interpolateMesh(w2), drawNormals (flame.cc:497-506, 2667-2697) over

@@ -661,6 +661,135 @@ int flame_nltgv2_render_view_arrays(flame_nltgv2_ctx* ctx, const flame_nltgv2_vi
                                     const float* vertices_xy, const float* idepths, int32_t V, const uint8_t* tri_valid, int rows,
                                     int cols, float* map_out, int32_t* tri_index_out, flame_nltgv2_view_counts* counts_out);
 
+/* ---- Kept meshes: the mesh a pose-frame keeps (flame.cc:417-426, curr_pf_->tris / vtx / vtx_idepths) -----------------------------------
+ * Slots 0 .. FLAME_NLTGV2_KEPT_MESHES - 1 of the context, each empty or holding on the device V positions (source pixels), V inverse
+ * depths, T triangles and, optionally, T validity bytes.  A kept mesh survives flame_nltgv2_upload_graph, flame_nltgv2_sync_graph /
+ * _sync_commit and any change of topology: that is its purpose.  Slots are written and read on the context's side stream only, so
+ * stream order covers every hazard between a snapshot, a fusion that reads it and the next snapshot into the same slot.
+ *
+ * flame_nltgv2_keep_mesh         snapshots the resident mesh into `slot`, device to device, enqueued on the side stream beside a running
+ *        solver: the resident triangles (of the last flame_nltgv2_interpolate_mesh[_begin] or flame_nltgv2_mesh_outputs_begin), pos, and
+ *        id[v] = x[v] * graph_scale -- one float32 multiply, no FMA -- with pos / x read from the state flame_nltgv2_render_view_begin
+ *        would read (FLAME_NLTGV2_OPT_MESH_STATE decides in the same way).  validity: 0 = none is kept (every triangle is valid), 2 = the
+ *        validity the last flame_nltgv2_mesh_outputs_begin left for the resident triangles.  Rendering the slot later gives the bytes
+ *        flame_nltgv2_render_view_begin on the live mesh would have given at the moment of the snapshot (id * 1.0f == id).
+ *        Errors, reported before anything is enqueued, the slot left as it was: slot out of range; no graph; no resident triangles for
+ *        the current topology; validity not 0 or 2, or 2 without a matching flame_nltgv2_mesh_outputs_begin.  (A failure behind these
+ *        checks -- no memory for a slot that must grow -- leaves the slot empty.)
+ * flame_nltgv2_keep_mesh_arrays  uploads a mesh of the caller's into `slot`: the arguments and their checks are those of
+ *        flame_nltgv2_render_view_arrays (T or V negative, a missing array, an index outside 0 .. V - 1); tri_valid NULL or T bytes.  It
+ *        needs no graph.  The caller's arrays are free when it returns.
+ * flame_nltgv2_drop_mesh         empties a slot (prunePoseFrames); dropping an empty slot is OK.  The memory stays with the context.
+ * flame_nltgv2_kept_mesh_info    *V = *T = -1 and *has_validity = 0 for an empty slot (each pointer may be NULL).
+ * flame_nltgv2_get_kept_mesh     downloads a slot, synchronously (for tests, and for callers that persist meshes): 2V floats, V floats,
+ *        3T int32, T bytes; each pointer may be NULL; an error for an empty slot, and for tri_valid where the slot keeps none. */
+#define FLAME_NLTGV2_KEPT_MESHES 16
+int flame_nltgv2_keep_mesh(flame_nltgv2_ctx* ctx, int32_t slot, float graph_scale, int32_t validity);
+int flame_nltgv2_keep_mesh_arrays(flame_nltgv2_ctx* ctx, int32_t slot, const int32_t* triangles, int32_t T, const float* vertices_xy,
+                                  const float* idepths, int32_t V, const uint8_t* tri_valid);
+int flame_nltgv2_drop_mesh(flame_nltgv2_ctx* ctx, int32_t slot);
+int flame_nltgv2_kept_mesh_info(flame_nltgv2_ctx* ctx, int32_t slot, int32_t* V, int32_t* T, int32_t* has_validity);
+int flame_nltgv2_get_kept_mesh(flame_nltgv2_ctx* ctx, int32_t slot, float* vertices_xy, float* idepths, int32_t* triangles, uint8_t* tri_valid);
+
+/* ---- Several meshes fused in one view --------------------------------------------------------------------------------------------------
+ * Up to FLAME_NLTGV2_FUSE_SOURCES meshes -- kept slots and, optionally, the live resident mesh -- rendered into ONE target camera in a
+ * single batch of launches, then a vote per pixel: where enough pose-frames agree on the surface the pixel gets their weighted mean,
+ * and the masks name who saw it and who disagreed.  Cross-view agreement removes the sliver triangles and mismatched features the
+ * single-view triangle filters only guess at.  The reference has no counterpart, so the rules are stated here in full;
+ * tests/fuse_ref.py restates them in numpy float32 and Python integers over tests/view_ref.py and is the checker: device and checker
+ * agree bit for bit.  All arithmetic is float32 without FMA.
+ *   A layers       layer s is exactly what rules 1 - 5 of flame_nltgv2_render_view_begin give for source s (its mesh, its Kinv_src, R, t)
+ *                  into the target (K_dst, near_depth, rows x cols), the 64-bit key {bits(val) << 32 | t + 1} and its tie rule included;
+ *                  holes are the quiet NaN 0x7fc00000.  A kept slot renders with the validity it keeps, if any; the live mesh as its
+ *                  `validity` says (0 or 2).
+ *   B present      source s is present at a pixel iff layer s is no hole there; n = the number present.
+ *   C reference    the present values ordered ascending by (bits(v_s), s) -- positive floats order as their bits do, equal bit patterns
+ *                  by source index --; m = the value at index n / 2 (integer division): the UPPER median, which of two sources that
+ *                  disagree is the larger inverse depth, the NEARER surface.  For navigation the conservative choice is the nearer one:
+ *                  an obstacle one pose-frame saw must not be voted away by one that saw through it.
+ *   D inliers      a present s is an inlier iff fabsf(v_s - m) <= rel_tol * m (one subtraction, one multiplication, one comparison);
+ *                  support = the number of inliers; the owner of m is always one of them.
+ *   E fused value  the pixel is fused iff support >= min_support; then num = ((v_a * w_a) + v_b * w_b) + ... and den = (w_a + w_b) + ...
+ *                  over the inliers in ascending source index, left to right, and fused = num / den; otherwise the pixel is a hole.
+ *   F outputs      fused: rows * cols floats.  present_mask, inlier_mask: rows * cols uint8, bit s for source s, written for every pixel,
+ *                  fused or not: present & ~inlier names the pose-frames that disagree here.  spread: rows * cols floats, the largest
+ *                  inlier minus the smallest (one subtraction), the quiet NaN where n == 0.  layers: n_sources * rows * cols floats,
+ *                  only with want_layers.  The counters (flame_nltgv2_fuse_counts, 32 int32): coverage = the fused pixels;
+ *                  support_hist[k] = the pixels with support k -- every pixel of the target falls in exactly one bin, n == 0 in bin 0 --;
+ *                  present[s], inlier[s] = the pixels where source s is; tris_drawn summed over the sources; the rest reserved, zero.
+ *   G transfers    with copy_out == 0 only the counters travel (128 bytes); the view carries the device pointers beside the host ones.
+ *                  fused_device serves flame_nltgv2_metric_params.map_device and flame_nltgv2_map_error_params.map_device /
+ *                  truth_device (under the rules stated there), and is what a volumetric integrator would consume.
+ * No floating-point atomics anywhere: two calls give the same bytes.
+ * Not done: clipping at the near plane, anti-aliasing, per-pixel confidence weights, fusing colour or normals. */
+#define FLAME_NLTGV2_FUSE_SOURCES 8
+typedef struct flame_nltgv2_fuse_source {
+  int32_t slot;            /* -1        a kept slot, or -1: the live resident mesh (at most one source of a call) */
+  int32_t validity;        /* 0         the live mesh only: 0 every triangle is valid, 2 the validity of the last mesh_outputs_begin */
+  float   graph_scale;     /* 1.0       the live mesh only: id[v] = x[v] * graph_scale */
+  float   weight;          /* 1.0       finite and > 0 */
+  float   Kinv_src[9];     /* identity  this source's inverse intrinsics */
+  float   R[9];            /* identity  P_dst = R * P_src + t */
+  float   t[3];            /* 0 */
+} flame_nltgv2_fuse_source;
+
+typedef struct flame_nltgv2_fuse_params {
+  int32_t n_sources;       /* 1         1 .. FLAME_NLTGV2_FUSE_SOURCES */
+  flame_nltgv2_fuse_source sources[FLAME_NLTGV2_FUSE_SOURCES];
+  float   K_dst[9];        /* identity  the target camera's intrinsics */
+  float   near_depth;      /* 0.0 */
+  float   rel_tol;         /* 0.05      finite and >= 0 */
+  int32_t min_support;     /* 1         1 .. n_sources */
+  int32_t want_fused;      /* 1 */
+  int32_t want_masks;      /* 1 */
+  int32_t want_spread;     /* 1 */
+  int32_t want_layers;     /* 0 */
+  int32_t copy_out;        /* 1  0: the outputs stay on the device; only the counters travel */
+} flame_nltgv2_fuse_params;
+void flame_nltgv2_default_fuse_params(flame_nltgv2_fuse_params* p);
+
+/* The counters, as they lie on the device and in pinned memory: 32 words. */
+typedef struct flame_nltgv2_fuse_counts {
+  int32_t coverage;
+  int32_t support_hist[FLAME_NLTGV2_FUSE_SOURCES + 1];
+  int32_t present[FLAME_NLTGV2_FUSE_SOURCES];
+  int32_t inlier[FLAME_NLTGV2_FUSE_SOURCES];
+  int32_t tris_drawn;
+  int32_t reserved[5];
+} flame_nltgv2_fuse_counts;
+
+/* Pointers into pinned memory of the context and the device pointers of the same arrays; all valid until the next
+ * flame_nltgv2_fuse_views_begin.  What was not asked for has two NULLs; with copy_out == 0 every host pointer is NULL. */
+typedef struct flame_nltgv2_fuse_outputs_view {
+  int32_t rows, cols, n_sources;
+  float   device_ms;                 /* measurement aid: HIP-event time of what begin enqueued on the side stream, kernels and copies out */
+  flame_nltgv2_fuse_counts counts;
+  const float*   fused;              const void* fused_device;         /* [rows * cols] */
+  const uint8_t* present_mask;       const void* present_mask_device;  /* [rows * cols] */
+  const uint8_t* inlier_mask;        const void* inlier_mask_device;   /* [rows * cols] */
+  const float*   spread;             const void* spread_device;        /* [rows * cols] */
+  const float*   layers;             const void* layers_device;        /* [n_sources * rows * cols] */
+} flame_nltgv2_fuse_outputs_view;
+
+/* begin  checks the arguments -- an error (params NULL; n_sources, rows or cols out of range (rows, cols in 1 .. 32767); a slot out of
+ *        range or empty; two live sources; a live source without a graph, without resident triangles for the current topology, with a
+ *        validity other than 0 or 2, or 2 without a matching flame_nltgv2_mesh_outputs_begin; a weight that is not finite and > 0;
+ *        rel_tol not finite or < 0; min_support outside 1 .. n_sources) is reported before anything is enqueued and leaves the outputs
+ *        of an earlier begin, and its pending _end, as they are --, then enqueues everything on the context's side stream and returns.
+ *        One vertex launch, one count launch, one raster launch and one launch for large boxes serve ALL sources; the vote reads the
+ *        key layers directly.  A live source's pos / x are read as flame_nltgv2_render_view_begin reads them, by the vertex kernel
+ *        alone.  The stage only READS the buffers of the other stages and the kept slots; its key layers, vertices and lists are its
+ *        own, so a pending flame_nltgv2_render_view_end is not disturbed by it, nor the other way round.  The same slot may be named
+ *        twice.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_fuse_views == begin (with copy_out forced to 1 and the want_* flags replaced by: the array is not NULL; the masks are
+ *        made if either is asked for); end; copies into the caller's arrays (each may be NULL). */
+int flame_nltgv2_fuse_views_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_params* params, int rows, int cols);
+int flame_nltgv2_fuse_views_end(flame_nltgv2_ctx* ctx, flame_nltgv2_fuse_outputs_view* out);
+int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_params* params, int rows, int cols, float* fused_out,
+                            uint8_t* present_mask_out, uint8_t* inlier_mask_out, float* spread_out, float* layers_out,
+                            flame_nltgv2_fuse_counts* counts_out);
+
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
  * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
