@@ -6,11 +6,12 @@
 #include <stdint.h>
 
 #include "nltgv2_kernels.h"
+#include "pairwise_sum.hpp"
 
 namespace flame_hip {
 
 constexpr int kMapErrorBins = 256;
-constexpr int kMapErrorChunk = 1024;  // consecutive linear pixel indices per partial of the sum: part of the sum's definition
+constexpr int kMapErrorChunk = kPairwiseChunk;  // 1024 consecutive linear pixel indices per partial of the sum: part of the sum's definition
 constexpr int kMapErrorMaxWin = 31;   // the widest box the tile's LDS holds
 constexpr int kMapErrorTileW = 64, kMapErrorTileH = 16;  // output pixels per workgroup of the box mean
 

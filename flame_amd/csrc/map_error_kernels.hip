@@ -16,6 +16,7 @@
 #include "debug_pixel.hpp"
 #include "map_error_kernels.h"
 #include "nltgv2_device.hpp"
+#include "pairwise_sum.hpp"
 
 namespace flame_hip {
 namespace {
@@ -90,24 +91,6 @@ k_map_error_box(int rows, int cols, int h, const float* __restrict__ err, float*
     }
     out[(long)gr * cols + gc] = o;
   }
-}
-
-// p[t] += p[t + s] for s = 512, 256, ..., 1 over the 1024 values of a workgroup of 1024 threads; the sum is returned to thread 0 (the
-// other threads get a value of no meaning).  The steps down to 64 go through LDS; the last six stay inside wave 0: lane t adds the value
-// of lane t + s, which for t < s is the very p[t + s] of the rule -- the same additions in the same order, without six barriers.
-__device__ __forceinline__ double pairwise_sum(double* p, int t) {
-  __syncthreads();
-  for (int s = kMapErrorChunk / 2; s >= 64; s >>= 1) {
-    if (t < s) p[t] += p[t + s];
-    __syncthreads();
-  }
-  double v = 0.0;
-  if (t < 64) {
-    v = p[t];
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
-  }
-  __syncthreads();  // (p may be rewritten behind this)
-  return v;
 }
 
 // Workgroup b takes the chunks [b * per_group, (b + 1) * per_group): partials[c] is a function of chunk c alone, the histogram is

@@ -21,6 +21,8 @@
 #include "matches_kernels.h"
 #include "input_kernels.h"
 #include "input_params.hpp"
+#include "align_kernels.h"
+#include "align_host.hpp"
 #include "roctx_ranges.hpp"
 
 using namespace flame_hip;
@@ -31,6 +33,8 @@ struct Frame {
   uint8_t* img_pad = nullptr;
   float* gx_pad = nullptr;
   float* gy_pad = nullptr;
+  uint8_t* pyr = nullptr;  // levels >= 1 (align_host.hpp, place_levels), allocated by the first build_pyramid; travels with the set
+  int pyr_levels = 0;      // n_levels of the last build_pyramid; 0: none since the frame was added
 };
 
 }  // namespace
@@ -124,6 +128,11 @@ struct flame_stereo_ctx {
   uint64_t* d_mentries = nullptr;
   size_t mentries_cap = 0;
   size_t match_last_total = 0;
+  // align_linearize / align_frame (align_kernels.hip)
+  double* d_apart = nullptr;  // [kAlignSums][chunks] partials
+  size_t apart_cap = 0;
+  AlignSystem* d_asys = nullptr;
+  AlignSystem* h_asys = nullptr;  // pinned
 };
 
 namespace {
@@ -147,6 +156,7 @@ void free_frame(Frame& f) {
   if (f.img_pad) (void)hipFree(f.img_pad);
   if (f.gx_pad) (void)hipFree(f.gx_pad);
   if (f.gy_pad) (void)hipFree(f.gy_pad);
+  if (f.pyr) (void)hipFree(f.pyr);
   f = Frame{};
 }
 
@@ -162,6 +172,7 @@ void drop_all_frames(flame_stereo_ctx* ctx) {
 // prunes one or two pose-frames every few frames, and bounds the idle memory at 4 x 3 padded planes (72 MB at 1080p).
 constexpr size_t kSpareFrames = 4;
 void release_frame(flame_stereo_ctx* ctx, std::unordered_map<uint32_t, Frame>::iterator it) {
+  it->second.pyr_levels = 0;  // (the levels go with the frame; their buffer stays with the set)
   if (ctx->spare.size() < kSpareFrames) ctx->spare.push_back(it->second); else free_frame(it->second);
   ctx->frames.erase(it);
 }
@@ -188,6 +199,7 @@ int acquire_frame(flame_stereo_ctx* ctx, uint32_t frame_id, Frame** out) {
       return e == hipErrorOutOfMemory ? FLAME_NLTGV2_ERR_OOM : FLAME_NLTGV2_ERR_HIP;
     }
   }
+  f.pyr_levels = 0;  // (a replaced frame's levels describe the old image)
   *out = &f;
   return 0;
 }
@@ -552,11 +564,13 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx) {
   for (void* p : {(void*)ctx->d_res_alt, (void*)ctx->d_proj, (void*)ctx->d_proj_alt, (void*)ctx->d_proj_tmp, (void*)ctx->d_keep,
                   (void*)ctx->d_groups, (void*)ctx->d_ppose, (void*)ctx->d_keep_ids, (void*)ctx->d_cell_key, (void*)ctx->d_blocked, (void*)ctx->d_map, (void*)ctx->d_mask,
                   (void*)ctx->d_fstats, (void*)ctx->d_spose, (void*)ctx->d_sel, (void*)ctx->d_owner, (void*)ctx->d_draw,
-                  (void*)ctx->d_match, (void*)ctx->d_mlist, (void*)ctx->d_mentries, (void*)ctx->d_rawsrc, (void*)ctx->d_istats})
+                  (void*)ctx->d_match, (void*)ctx->d_mlist, (void*)ctx->d_mentries, (void*)ctx->d_rawsrc, (void*)ctx->d_istats,
+                  (void*)ctx->d_apart, (void*)ctx->d_asys})
     if (p) (void)hipFree(p);
   if (ctx->h_fstats) (void)hipHostFree(ctx->h_fstats);
   if (ctx->h_sel) (void)hipHostFree(ctx->h_sel);
   if (ctx->h_istats) (void)hipHostFree(ctx->h_istats);
+  if (ctx->h_asys) (void)hipHostFree(ctx->h_asys);
   if (ctx->d_stats) (void)hipFree(ctx->d_stats);
   if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1220,6 +1234,257 @@ int flame_stereo_select_graph_features_arrays(flame_stereo_ctx* ctx, const flame
     out->error_feature = e, out->num_examined = n;
   }
   return rc;
+}
+
+// ---- pyramid levels and direct alignment (include/flame_stereo.h; align_kernels.hip, align_host.hpp) ----
+
+void flame_stereo_default_align_params(flame_stereo_align_params* p) {
+  if (!p) return;
+  p->border = 2;
+  p->huber_k = 10.0f;
+  p->coarsest_level = 2;
+  p->finest_level = 0;
+  p->max_iters_per_level = 10;
+  p->min_pixels = 100;
+  p->min_step = 1e-5;
+  p->lm_lambda = 0.0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Level `level` of frame f, or false when it is not built.
+bool frame_level(const flame_stereo_ctx* ctx, const Frame& f, int level, AlignLevel* L) {
+  const int w = ctx->cam.width, h = ctx->cam.height, b = ctx->cam.border;
+  if (level == 0) {
+    const int pitch = w + 2 * b;
+    const size_t o = (size_t)b * pitch + b;
+    *L = AlignLevel{f.img_pad + o, f.gx_pad + o, f.gy_pad + o, w, h, pitch};
+    return true;
+  }
+  if (level < 0 || level >= f.pyr_levels || !f.pyr) return false;
+  align::LevelPlace place[align::kMaxLevels];
+  align::place_levels(w, h, f.pyr_levels, place);
+  const align::LevelPlace& pl = place[level];
+  *L = AlignLevel{f.pyr + pl.img, (const float*)(f.pyr + pl.gx), (const float*)(f.pyr + pl.gy), pl.w, pl.h, pl.w};
+  return true;
+}
+
+// What both alignment calls check before anything is enqueued, for the levels [level_lo, level_hi].
+int align_check(flame_stereo_ctx* ctx, const flame_stereo_align_params* P, uint32_t ref_id, uint32_t new_id, int level_lo,
+                int level_hi, const float* map_host, const void* map_device) {
+  if (!P || (map_host != nullptr) == (map_device != nullptr)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  const float* K = ctx->cam.K;
+  if (K[1] != 0.0f || K[3] != 0.0f || K[6] != 0.0f || K[7] != 0.0f || K[8] != 1.0f) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (!(P->huber_k > 0.0f) || !std::isfinite(P->huber_k) || P->border < 1) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  auto fr = ctx->frames.find(ref_id), fn = ctx->frames.find(new_id);
+  if (fr == ctx->frames.end() || fn == ctx->frames.end()) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (level_lo < 0 || level_hi < level_lo || level_hi >= align::kMaxLevels) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  for (int l = level_lo; l <= level_hi; ++l) {
+    AlignLevel a, b;
+    if (!frame_level(ctx, fr->second, l, &a) || !frame_level(ctx, fn->second, l, &b)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+    if (2L * P->border + 2 > std::min(a.w, a.h)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  }
+  return 0;
+}
+
+// Scratch of the linearisation and the map on the device; after this nothing allocates.  *d_map_out: the map to read.
+int align_prepare(flame_stereo_ctx* ctx, const float* map_host, const void* map_device, const float** d_map_out) {
+  const int w = ctx->cam.width, h = ctx->cam.height;
+  const size_t want = (size_t)kAlignSums * (size_t)align_chunks((long)w * h);
+  if (ctx->apart_cap < want || (map_host && ctx->map_cap < (size_t)w * h) || !ctx->d_asys)
+    SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (buffers are about to be reallocated)
+  if (int rc = grow(ctx, &ctx->d_apart, &ctx->apart_cap, want)) return rc;
+  if (!ctx->d_asys) SCHK(ctx, hipMalloc((void**)&ctx->d_asys, sizeof(AlignSystem)));
+  if (!ctx->h_asys) SCHK(ctx, hipHostMalloc((void**)&ctx->h_asys, sizeof(AlignSystem), hipHostMallocDefault));
+  *d_map_out = (const float*)map_device;
+  if (map_host) {
+    if (int rc = grow(ctx, &ctx->d_map, &ctx->map_cap, (size_t)w * h)) return rc;
+    SCHK(ctx, hipMemcpyAsync(ctx->d_map, map_host, (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    SCHK(ctx, hipStreamSynchronize(ctx->stream));  // (`map_host` is pageable memory)
+    *d_map_out = ctx->d_map;
+  }
+  return 0;
+}
+
+// One linearisation at (q, t) on `level`: enqueues, waits once, fills *out from the pinned block.
+int align_eval(flame_stereo_ctx* ctx, const flame_stereo_align_params& P, const Frame& ref, const Frame& cur, int level,
+               const float* d_map, const double q[4], const double t[3], flame_stereo_align_system* out) {
+  AlignArgs a;
+  frame_level(ctx, ref, level, &a.ref);
+  frame_level(ctx, cur, level, &a.cur);
+  a.map = d_map, a.map_w = ctx->cam.width, a.shift = level;
+  a.border = P.border, a.huber_k = P.huber_k;
+  const float scale = (float)(1 << level);
+  a.fx = ctx->cam.K[0] / scale, a.cx = ctx->cam.K[2] / scale, a.fy = ctx->cam.K[4] / scale, a.cy = ctx->cam.K[5] / scale;
+  align::pose_to_float(q, t, a.R, a.t);
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  SCHK(ctx, (hipError_t)launch_align_linearize(a, ctx->d_apart, ctx->d_asys, ctx->stream));
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  SCHK(ctx, hipMemcpyAsync(ctx->h_asys, ctx->d_asys, sizeof(AlignSystem), hipMemcpyDeviceToHost, ctx->stream));
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  static_assert(sizeof(AlignSystem) == sizeof(flame_stereo_align_system), "the device block is the C struct");
+  std::memcpy(out, ctx->h_asys, sizeof *out);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flame_stereo_build_pyramid(flame_stereo_ctx* ctx, uint32_t frame_id, int n_levels) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_build_pyramid");
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  auto it = ctx->frames.find(frame_id);
+  const int w = ctx->cam.width, h = ctx->cam.height;
+  if (it == ctx->frames.end() || !align::levels_valid(w, h, n_levels)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  Frame& f = it->second;
+  if (f.pyr_levels == n_levels) return 0;
+  align::LevelPlace place[align::kMaxLevels];
+  if (!f.pyr && n_levels > 1) {  // (sized for every level the camera could have: one size per camera, so the buffer can be handed on)
+    const size_t bytes = align::place_levels(w, h, align::kMaxLevels, place);
+    SCHK(ctx, hipMalloc((void**)&f.pyr, bytes));
+  }
+  align::place_levels(w, h, n_levels, place);
+  AlignLevel src;
+  frame_level(ctx, f, 0, &src);
+  const uint8_t* s_img = src.img;
+  int sw = src.w, sh = src.h, sp = src.pitch;
+  SCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  for (int l = 1; l < n_levels; ++l) {
+    const align::LevelPlace& pl = place[l];
+    SCHK(ctx, (hipError_t)launch_pyr_down(s_img, sw, sh, sp, f.pyr + pl.img, (float*)(f.pyr + pl.gx), (float*)(f.pyr + pl.gy),
+                                          ctx->stream));
+    s_img = f.pyr + pl.img, sw = pl.w, sh = pl.h, sp = pl.w;
+  }
+  SCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  f.pyr_levels = n_levels;
+  return 0;
+}
+
+int flame_stereo_download_pyramid_level(flame_stereo_ctx* ctx, uint32_t frame_id, int level, uint8_t* img, float* gradx,
+                                        float* grady) {
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->have_camera) return FLAME_NLTGV2_ERR_NO_GRAPH;
+  auto it = ctx->frames.find(frame_id);
+  AlignLevel L;
+  if (it == ctx->frames.end() || !frame_level(ctx, it->second, level, &L)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  SCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (img) SCHK(ctx, hipMemcpy2D(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost));
+  if (gradx)
+    SCHK(ctx, hipMemcpy2D(gradx, (size_t)L.w * 4, L.gx, (size_t)L.pitch * 4, (size_t)L.w * 4, (size_t)L.h, hipMemcpyDeviceToHost));
+  if (grady)
+    SCHK(ctx, hipMemcpy2D(grady, (size_t)L.w * 4, L.gy, (size_t)L.pitch * 4, (size_t)L.w * 4, (size_t)L.h, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int flame_stereo_align_linearize(flame_stereo_ctx* ctx, const flame_stereo_align_params* params, uint32_t ref_frame_id,
+                                 uint32_t new_frame_id, int level, const float* idepthmap_host, const void* idepthmap_device,
+                                 const double q_ref_to_new[4], const double t_ref_to_new[3], flame_stereo_align_system* out) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_align_linearize");
+  if (int rc = enter(ctx)) return rc;
+  if (!q_ref_to_new || !t_ref_to_new || !out) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (int rc = align_check(ctx, params, ref_frame_id, new_frame_id, level, level, idepthmap_host, idepthmap_device)) return rc;
+  if (!align::pose_finite(q_ref_to_new, t_ref_to_new)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const float* d_map = nullptr;
+  if (int rc = align_prepare(ctx, idepthmap_host, idepthmap_device, &d_map)) return rc;
+  return align_eval(ctx, *params, ctx->frames.find(ref_frame_id)->second, ctx->frames.find(new_frame_id)->second, level, d_map,
+                    q_ref_to_new, t_ref_to_new, out);
+}
+
+int flame_stereo_align_frame(flame_stereo_ctx* ctx, const flame_stereo_align_params* params, uint32_t ref_frame_id,
+                             uint32_t new_frame_id, const float* idepthmap_host, const void* idepthmap_device,
+                             const double q_init[4], const double t_init[3], flame_stereo_align_result* out,
+                             flame_stereo_align_trace* trace, int max_trace, int* n_trace) {
+  flame_hip::RoctxRange roctx_range_("flame_stereo_align_frame");
+  if (int rc = enter(ctx)) return rc;
+  if (n_trace) *n_trace = 0;
+  if (!params || !q_init || !t_init || !out || max_trace < 0 || (max_trace > 0 && !trace)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  const flame_stereo_align_params& P = *params;
+  if (P.max_iters_per_level < 1 || P.min_pixels < 1 || !(P.min_step >= 0.0) || !std::isfinite(P.min_step) ||
+      !(P.lm_lambda >= 0.0) || !std::isfinite(P.lm_lambda))
+    return FLAME_NLTGV2_ERR_INVALID_ARG;
+  if (int rc = align_check(ctx, params, ref_frame_id, new_frame_id, P.finest_level, P.coarsest_level, idepthmap_host,
+                           idepthmap_device))
+    return rc;
+  if (!align::pose_finite(q_init, t_init)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  double q[4], t[3] = {t_init[0], t_init[1], t_init[2]};
+  const double qn = std::sqrt(((q_init[0] * q_init[0] + q_init[1] * q_init[1]) + q_init[2] * q_init[2]) + q_init[3] * q_init[3]);
+  if (!(qn > 0.0) || !std::isfinite(qn)) return FLAME_NLTGV2_ERR_INVALID_ARG;
+  for (int k = 0; k < 4; ++k) q[k] = q_init[k] / qn;
+  const float* d_map = nullptr;
+  if (int rc = align_prepare(ctx, idepthmap_host, idepthmap_device, &d_map)) return rc;
+  const Frame& ref = ctx->frames.find(ref_frame_id)->second;
+  const Frame& cur = ctx->frames.find(new_frame_id)->second;
+
+  std::memset(out, 0, sizeof *out);
+  int n_evals = 0;
+  bool have_first = false;
+  flame_stereo_align_system sys;
+  const double zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  auto eval = [&](int level, const double* eq, const double* et, const double* delta, flame_stereo_align_system* s) -> int {
+    if (int rc = align_eval(ctx, P, ref, cur, level, d_map, eq, et, s)) return rc;
+    if (n_evals < max_trace) {
+      flame_stereo_align_trace& e = trace[n_evals];
+      std::memset(&e, 0, sizeof e);
+      e.level = level, e.accepted = 1;
+      std::memcpy(e.q, eq, sizeof e.q);
+      std::memcpy(e.t, et, sizeof e.t);
+      std::memcpy(e.delta, delta, sizeof e.delta);
+      e.sys = *s;
+    }
+    ++n_evals;
+    return 0;
+  };
+  int status = FLAME_STEREO_ALIGN_OK, flags = 0;
+  for (int level = P.coarsest_level; level >= P.finest_level && status == FLAME_STEREO_ALIGN_OK; --level) {
+    if (int rc = eval(level, q, t, zero6, &sys)) return rc;
+    if (!have_first) out->first_mean_cost = sys.cost / (double)sys.n_used, have_first = true;
+    for (int iter = 0;; ++iter) {
+      if (sys.n_used < P.min_pixels) {
+        status = FLAME_STEREO_ALIGN_TOO_FEW;
+        break;
+      }
+      if (iter >= P.max_iters_per_level) {
+        flags |= FLAME_STEREO_ALIGN_FLAG_MAX_ITERS;
+        break;
+      }
+      double delta[6];
+      if (!align::solve(sys.H, sys.b, P.lm_lambda, delta)) {
+        flags |= FLAME_STEREO_ALIGN_FLAG_NOT_PD;
+        break;
+      }
+      double q2[4], t2[3];
+      align::exp_left(delta, q, t, q2, t2);
+      flame_stereo_align_system sys2;
+      const int slot = n_evals;
+      if (int rc = eval(level, q2, t2, delta, &sys2)) return rc;
+      if (!align::accept(sys2.cost, sys2.n_used, sys.cost, sys.n_used)) {
+        if (slot < max_trace) trace[slot].accepted = 0;
+        flags |= FLAME_STEREO_ALIGN_FLAG_REJECTED;
+        break;
+      }
+      std::memcpy(q, q2, sizeof q);
+      std::memcpy(t, t2, sizeof t);
+      sys = sys2;
+      out->iters[level] += 1;
+      if (align::max_abs(delta) < P.min_step) break;
+    }
+  }
+  out->status = status, out->flags = flags;
+  std::memcpy(out->q, q, sizeof q);
+  std::memcpy(out->t, t, sizeof t);
+  for (int k = 0; k < 4; ++k) out->q_f32[k] = (float)q[k];
+  align::pose_to_float(q, t, out->R_f32, out->t_f32);
+  out->last_mean_cost = sys.cost / (double)sys.n_used;
+  out->n_evals = n_evals;
+  if (n_trace) *n_trace = n_evals;
+  return 0;
 }
 
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx) {

@@ -3,7 +3,8 @@
 Mirrors the reference interface of /root/reference/src/flame/flame.cc:1280-1752 (Flame::updateFeatureIDepths,
 Flame::trackFeature), flame.cc:1754-1860 (Flame::projectFeatures), flame.cc:708-773 + 822-1278 (the detection loop
 and Flame::detectFeatures), flame.cc:554-706 (Flame::prunePoseFrames), flame.cc:1954-1980 (the preprocessing of Flame::syncGraph) and src/flame/utils/frame.cc:33-71
-(Frame::create, level 0).  There is no CPU path: every call fails with NLTGV2Error when the HIP library or a gfx950
+(Frame::create, level 0; its further levels through build_pyramid).  The direct alignment (align_linearize, align_frame) has no
+counterpart in the reference: include/flame_stereo.h is its definition.  There is no CPU path: every call fails with NLTGV2Error when the HIP library or a gfx950
 device is missing.
 """
 from __future__ import annotations
@@ -152,6 +153,54 @@ class _MatchesStats(C.Structure):
                 ("lines_skipped", C.c_int32), ("rings_skipped", C.c_int32), ("refilled", C.c_int32), ("entries", C.c_int64)]
 
 
+ALIGN_COUNTS = ("n_used", "n_no_depth", "n_behind", "n_outside", "n_huber")  # flame_stereo_align_system, in order
+ALIGN_OK, ALIGN_TOO_FEW = 0, 1  # flame_stereo_align_result.status
+ALIGN_FLAG_NOT_PD, ALIGN_FLAG_REJECTED, ALIGN_FLAG_MAX_ITERS = 1, 2, 4
+
+
+class AlignParams(C.Structure):
+    """flame_stereo_align_params; the defaults (flame_stereo_default_align_params) are this library's design choices."""
+    _fields_ = [("border", C.c_int32), ("huber_k", C.c_float), ("coarsest_level", C.c_int32), ("finest_level", C.c_int32),
+                ("max_iters_per_level", C.c_int32), ("min_pixels", C.c_int32), ("min_step", C.c_double),
+                ("lm_lambda", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib().flame_stereo_default_align_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown align parameter %r" % k)
+            setattr(self, k, v)
+
+
+class _AlignSystem(C.Structure):
+    _fields_ = [("H", C.c_double * 21), ("b", C.c_double * 6), ("cost", C.c_double)] + \
+               [(n, C.c_int32) for n in ALIGN_COUNTS] + [("reserved_", C.c_int32)]
+
+
+class _AlignTrace(C.Structure):
+    _fields_ = [("level", C.c_int32), ("accepted", C.c_int32), ("q", C.c_double * 4), ("t", C.c_double * 3),
+                ("delta", C.c_double * 6), ("sys", _AlignSystem)]
+
+
+class _AlignResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("q", C.c_double * 4), ("t", C.c_double * 3),
+                ("q_f32", C.c_float * 4), ("t_f32", C.c_float * 3), ("R_f32", C.c_float * 9),
+                ("first_mean_cost", C.c_double), ("last_mean_cost", C.c_double), ("iters", C.c_int32 * 5),
+                ("n_evals", C.c_int32)]
+
+
+assert C.sizeof(AlignParams) == 40 and C.sizeof(_AlignSystem) == 248 and C.sizeof(_AlignTrace) == 360
+assert C.sizeof(_AlignResult) == 168
+
+
+def _system_dict(s):
+    """An _AlignSystem as numpy copies: sums [28] float64 (H's upper triangle row-major, b, cost) and the five counts."""
+    d = {"sums": np.array(list(s.H) + list(s.b) + [s.cost], np.float64)}
+    d.update({n: int(getattr(s, n)) for n in ALIGN_COUNTS})
+    return d
+
+
 STEREO_ABI_SYMBOLS = (
     "flame_stereo_default_params", "flame_stereo_create", "flame_stereo_destroy", "flame_stereo_set_stream",
     "flame_stereo_set_camera", "flame_stereo_add_frame", "flame_stereo_drop_frame", "flame_stereo_frame_count",
@@ -164,7 +213,8 @@ STEREO_ABI_SYMBOLS = (
     "flame_stereo_select_graph_features", "flame_stereo_select_graph_features_arrays",
     "flame_stereo_draw_features", "flame_stereo_frame_image_device", "flame_stereo_draw_matches",
     "flame_stereo_draw_detections", "flame_stereo_default_input_params", "flame_stereo_set_input",
-    "flame_stereo_add_raw_frame",
+    "flame_stereo_add_raw_frame", "flame_stereo_default_align_params", "flame_stereo_build_pyramid",
+    "flame_stereo_download_pyramid_level", "flame_stereo_align_linearize", "flame_stereo_align_frame",
 )
 OPT_LANES_PER_FEATURE = 1
 OPT_GRAPH_COPY = 2
@@ -172,6 +222,7 @@ OPT_RECORD_MATCHES = 3
 
 _READY = False
 _FP = C.POINTER(C.c_float)
+_DP = C.POINTER(C.c_double)
 
 
 def _lib():
@@ -232,6 +283,14 @@ def _lib():
             "flame_stereo_set_input": (C.c_int, [ctx, C.POINTER(InputParams)]),
             "flame_stereo_add_raw_frame": (C.c_int, [ctx, C.c_uint32, C.c_void_p, C.c_int, C.c_int,
                                                      C.POINTER(_InputStats)]),
+            "flame_stereo_default_align_params": (None, [C.POINTER(AlignParams)]),
+            "flame_stereo_build_pyramid": (C.c_int, [ctx, C.c_uint32, C.c_int]),
+            "flame_stereo_download_pyramid_level": (C.c_int, [ctx, C.c_uint32, C.c_int, C.c_void_p, _FP, _FP]),
+            "flame_stereo_align_linearize": (C.c_int, [ctx, C.POINTER(AlignParams), C.c_uint32, C.c_uint32, C.c_int, _FP,
+                                                       C.c_void_p, _DP, _DP, C.POINTER(_AlignSystem)]),
+            "flame_stereo_align_frame": (C.c_int, [ctx, C.POINTER(AlignParams), C.c_uint32, C.c_uint32, _FP, C.c_void_p, _DP,
+                                                   _DP, C.POINTER(_AlignResult), C.POINTER(_AlignTrace), C.c_int,
+                                                   C.POINTER(C.c_int)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -545,6 +604,95 @@ class FeatureTracker:
         if rc != 0:
             raise NLTGV2Error(rc, "detect_features: %s (pixel %d)" % (status_string(rc), stats["error_feature"]))
         return stats["num_features"]
+
+    # ---- refining a frame's pose against a pose-frame's map ----
+    def level_size(self, level: int):
+        """(w_l, h_l) of pyramid level `level`: ((w + 1) // 2, (h + 1) // 2) per level."""
+        w, h = self.width, self.height
+        for _ in range(level):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        return w, h
+
+    def build_pyramid(self, frame_id: int, n_levels: int, raise_on_error: bool = True):
+        """flame_stereo_build_pyramid: levels 1 .. n_levels - 1 of a resident frame (pyrDown in integers + central
+        gradients), enqueue-only.  Returns the status."""
+        rc = self._L.flame_stereo_build_pyramid(self._ctx, frame_id, int(n_levels))
+        if raise_on_error:
+            self._chk(rc, "build_pyramid")
+        return rc
+
+    def download_pyramid_level(self, frame_id: int, level: int, raise_on_error: bool = True):
+        """(img u8, gradx f32, grady f32) of one level, each (h_l, w_l), unpadded; (status, None) on an error when
+        raise_on_error is False."""
+        w, h = self.level_size(level) if 0 <= level < 16 else (1, 1)
+        img, gx, gy = np.empty((h, w), np.uint8), np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+        rc = self._L.flame_stereo_download_pyramid_level(self._ctx, frame_id, int(level), img.ctypes.data,
+                                                         gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP))
+        if not raise_on_error:
+            return rc, ((img, gx, gy) if rc == 0 else None)
+        self._chk(rc, "download_pyramid_level")
+        return img, gx, gy
+
+    def _map_args(self, idepthmap):
+        """(keep-alive, host pointer, device pointer) of an inverse-depth map: a (height, width) float32 host array or an
+        int device address."""
+        if isinstance(idepthmap, (int, np.integer)) and not isinstance(idepthmap, bool):
+            return None, None, C.c_void_p(int(idepthmap))
+        if idepthmap is None:
+            return None, None, None
+        m = np.ascontiguousarray(idepthmap, dtype=np.float32)
+        if m.shape != (self.height, self.width):
+            raise ValueError("idepthmap must be %dx%d" % (self.height, self.width))
+        return m, m.ctypes.data_as(_FP), None
+
+    def align_linearize(self, params: AlignParams, ref_frame_id: int, new_frame_id: int, level: int, idepthmap, q, t,
+                        raise_on_error: bool = True):
+        """flame_stereo_align_linearize: the Gauss-Newton system of the direct alignment of `new_frame_id` against
+        `ref_frame_id` and its map at the pose (q (w x y z), t) = T_ref_to_new, float64.  Returns a dict: sums [28] float64
+        (H's upper triangle row-major, b, cost) and the counts ALIGN_COUNTS; (status, dict) when raise_on_error is False."""
+        q = np.ascontiguousarray(q, np.float64).reshape(4)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        keep, hp, dp = self._map_args(idepthmap)
+        out = _AlignSystem()
+        rc = self._L.flame_stereo_align_linearize(self._ctx, C.byref(params), ref_frame_id, new_frame_id, int(level), hp, dp,
+                                                  q.ctypes.data_as(_DP), t.ctypes.data_as(_DP), C.byref(out))
+        del keep
+        if not raise_on_error:
+            return rc, _system_dict(out)
+        self._chk(rc, "align_linearize")
+        return _system_dict(out)
+
+    def align_frame(self, params: AlignParams, ref_frame_id: int, new_frame_id: int, idepthmap, q_init, t_init,
+                    max_trace: int = 256, raise_on_error: bool = True):
+        """flame_stereo_align_frame: Gauss-Newton over the levels coarsest_level .. finest_level.  Returns a dict: status,
+        flags, q [4] / t [3] float64, q_f32, t_f32, R_f32 [3, 3], first_mean_cost, last_mean_cost, iters [5], n_evals and
+        trace: a list of dicts (level, accepted, q, t, delta, sums, counts), one per evaluation; (status code, dict) when
+        raise_on_error is False."""
+        q = np.ascontiguousarray(q_init, np.float64).reshape(4)
+        t = np.ascontiguousarray(t_init, np.float64).reshape(3)
+        keep, hp, dp = self._map_args(idepthmap)
+        out = _AlignResult()
+        trace = (_AlignTrace * max(max_trace, 1))()
+        n = C.c_int(0)
+        rc = self._L.flame_stereo_align_frame(self._ctx, C.byref(params), ref_frame_id, new_frame_id, hp, dp,
+                                              q.ctypes.data_as(_DP), t.ctypes.data_as(_DP), C.byref(out), trace, int(max_trace),
+                                              C.byref(n))
+        del keep
+        res = {"status": int(out.status), "flags": int(out.flags), "q": np.array(list(out.q), np.float64),
+               "t": np.array(list(out.t), np.float64), "q_f32": np.array(list(out.q_f32), np.float32),
+               "t_f32": np.array(list(out.t_f32), np.float32), "R_f32": np.array(list(out.R_f32), np.float32).reshape(3, 3),
+               "first_mean_cost": float(out.first_mean_cost), "last_mean_cost": float(out.last_mean_cost),
+               "iters": [int(v) for v in out.iters], "n_evals": int(out.n_evals), "trace": []}
+        for k in range(min(int(n.value), max_trace)):
+            e = trace[k]
+            d = _system_dict(e.sys)
+            d.update(level=int(e.level), accepted=int(e.accepted), q=np.array(list(e.q), np.float64),
+                     t=np.array(list(e.t), np.float64), delta=np.array(list(e.delta), np.float64))
+            res["trace"].append(d)
+        if not raise_on_error:
+            return rc, res
+        self._chk(rc, "align_frame")
+        return res
 
     # ---- letting a pose-frame go ----
     @staticmethod

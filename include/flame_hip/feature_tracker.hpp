@@ -197,6 +197,39 @@ class FeatureTracker {
     check(flame_stereo_add_raw_frame(ctx_, frame_id, raw, row_stride_bytes, on_device ? 1 : 0, stats), -1,
           "flame_stereo_add_raw_frame");
   }
+  // Refining a frame's pose against a pose-frame's map (flame_stereo.h, "direct image alignment"): after addFrame / addRawFrame of
+  // the new frame and before updateFeatureIDepths, against curr_pf_ and the dense map that pose-frame kept.  buildPyramid once per
+  // frame (enqueue-only), then alignFrame from the pose the caller has: T_ref_to_new = fnew.pose.inverse() * curr_pf.pose as
+  // (q (w x y z), t) in double.  The refined pose comes back in `out` (double, and as the float32 values flame_stereo_pose takes).
+  // The map is host memory (map_on_device false) or device memory read in place.  `trace` may be NULL.
+  void buildPyramid(uint32_t frame_id, int n_levels) {
+    check(flame_stereo_build_pyramid(ctx_, frame_id, n_levels), -1, "flame_stereo_build_pyramid");
+  }
+  flame_stereo_align_system alignLinearize(const flame_stereo_align_params& params, uint32_t ref_frame_id, uint32_t new_frame_id,
+                                           int level, const float* idepthmap, bool map_on_device, const double q_ref_to_new[4],
+                                           const double t_ref_to_new[3]) {
+    flame_stereo_align_system out;
+    std::memset(&out, 0, sizeof out);
+    check(flame_stereo_align_linearize(ctx_, &params, ref_frame_id, new_frame_id, level, map_on_device ? nullptr : idepthmap,
+                                       map_on_device ? idepthmap : nullptr, q_ref_to_new, t_ref_to_new, &out),
+          -1, "flame_stereo_align_linearize");
+    return out;
+  }
+  flame_stereo_align_result alignFrame(const flame_stereo_align_params& params, uint32_t ref_frame_id, uint32_t new_frame_id,
+                                       const float* idepthmap, bool map_on_device, const double q_init[4], const double t_init[3],
+                                       std::vector<flame_stereo_align_trace>* trace = nullptr, int max_trace = 256) {
+    flame_stereo_align_result out;
+    std::memset(&out, 0, sizeof out);
+    int n = 0;
+    if (trace) trace->resize((size_t)(max_trace > 0 ? max_trace : 0));
+    const int rc = flame_stereo_align_frame(ctx_, &params, ref_frame_id, new_frame_id, map_on_device ? nullptr : idepthmap,
+                                            map_on_device ? idepthmap : nullptr, q_init, t_init, &out,
+                                            trace && max_trace > 0 ? trace->data() : nullptr, trace ? (max_trace > 0 ? max_trace : 0) : 0,
+                                            &n);
+    if (trace) trace->resize((size_t)(rc == 0 ? (n < max_trace ? n : (max_trace > 0 ? max_trace : 0)) : 0));
+    check(rc, -1, "flame_stereo_align_frame");
+    return out;
+  }
   void dropFrame(uint32_t frame_id) { check(flame_stereo_drop_frame(ctx_, frame_id), -1, "flame_stereo_drop_frame"); }
   int frameCount() const { return flame_stereo_frame_count(ctx_); }
 

@@ -574,6 +574,153 @@ int flame_stereo_draw_detections(flame_stereo_ctx* ctx, const flame_stereo_param
                                  const float q_ref_to_prev[4], const float t_ref_to_prev[3], float max_score, int flip,
                                  uint8_t* img_out, flame_stereo_detections_stats* stats);
 
+/* ---- Refining a frame's pose against a pose-frame's map: direct image alignment ---------------------------------------------
+ * Every other stage takes the pose of every frame on trust (flame_stereo_pose, KRKinv / Kt, T_world_cam).  These calls correct
+ * the relative pose T = T_ref_to_new of a new frame against a resident reference frame that has a dense inverse-depth map, by
+ * Gauss-Newton on the photometric error over a few pyramid levels.  UNPINNED: the reference has no direct alignment (it takes
+ * its poses from outside, flame.h:134-140), so everything about the alignment below is this library's own statement;
+ * tests/align_ref.py restates it in numpy and is the checker, bit for bit.  The pyramid follows utils::Frame::create with
+ * num_levels > 1 (frame.cc:33-71): getGaussianPyramid (pyramids.h:42-51: cv::pyrDown per level), getGradientPyramid
+ * (pyramids.h:72-90) and getCentralGradient (image_utils.h:425-474).
+ *
+ * PYRAMID LEVELS.  Level 0 is the resident frame (flame_stereo_add_frame / add_raw_frame) and needs no call.  Level l >= 1 has the
+ * size ((w + 1) / 2, (h + 1) / 2) of level l - 1 (integer division) and is cv::pyrDown's rule stated in integers:
+ *     out(y, x) = (sum_{i, j = -2 .. 2} k_i k_j * src(r(2 y + i), r(2 x + j)) + 128) >> 8,     k = 1 4 6 4 1,
+ * r = the BORDER_REFLECT_101 rule stated at flame_stereo_add_frame, repeated until the coordinate lies inside (a coarse level can
+ * be narrower than 3).  UNPINNED against OpenCV, which is on neither tree: the formula is the definition.  The gradients of
+ * level l >= 1 are getCentralGradient's of that level's image: 0.5f * ((float)right - (float)left) inside, (float)next -
+ * (float)this in the first column / row, (float)this - (float)previous in the last.  Levels >= 1 are stored unpadded, image and
+ * both gradient planes.
+ *   flame_stereo_build_pyramid   builds levels 1 .. n_levels - 1 of resident frame `frame_id`; 1 <= n_levels <= 5 and every level
+ *      must keep w_l, h_l >= 4, else FLAME_NLTGV2_ERR_INVALID_ARG (also for an unknown frame) and nothing changes.  The levels
+ *      belong to the frame: flame_stereo_drop_frame, replacing the frame (add_frame / add_raw_frame with its id), a prune that
+ *      releases it and flame_stereo_set_camera release them; their buffer travels with the frame's other buffers (it waits with them
+ *      for the next add_frame and is reused by the next build_pyramid of that frame).  Building again with the same n_levels is a
+ *      no-op; with another n_levels all levels are rebuilt.  One kernel per level; enqueue-only on the context's stream once the
+ *      frame's buffer exists (the first build of a buffer set allocates).
+ *   flame_stereo_download_pyramid_level  copies level `level` back: w_l x h_l each, unpadded, any pointer may be NULL; for level 0
+ *      the inner width x height of the padded planes.  FLAME_NLTGV2_ERR_INVALID_ARG for an unknown frame or a level not built.
+ *
+ * THE LINEARISATION (flame_stereo_align_linearize): one Gauss-Newton system at the pose (q, t) = T_ref_to_new on level `level`.
+ *   The map      width x height floats at level-0 resolution, in host memory (idepthmap_host) or in device memory
+ *                (idepthmap_device, read in place: the caller orders the work that produces it before the call), exactly one of
+ *                the two.  Level l reads it by decimation: d = map(y * 2^l, x * 2^l).  No map pyramid, nothing is averaged.
+ *   The camera   the context's; K[1] = K[3] = K[6] = K[7] = 0 and K[8] = 1 are required.  fx_l = K[0] / 2^l, cx_l = K[2] / 2^l,
+ *                fy_l = K[4] / 2^l, cy_l = K[5] / 2^l (exact divisions).
+ *   The pose     q = (w, x, y, z) and t in double.  R is formed in double, + - * only, in this association:
+ *                  tx = 2 x, ty = 2 y, tz = 2 z;  twx = tx w, twy = ty w, twz = tz w;  txx = tx x, txy = ty x, txz = tz x;
+ *                  tyy = ty y, tyz = tz y, tzz = tz z;
+ *                  R = [1 - (tyy + tzz), txy - twz, txz + twy;  txy + twz, 1 - (txx + tzz), tyz - twx;
+ *                       txz - twy, tyz + twx, 1 - (txx + tyy)]       (q is not normalised here)
+ *                then R and t are rounded to float32.  The kernel sees only those 12 floats.
+ *   Per level pixel (x, y), linear index y * w_l + x, all in float32, one rounding per operation, in exactly this association:
+ *     1. eligible iff border <= x < w_l - border, the same in y, and d == d && d > 0 && d < inf; a pixel inside the border ring
+ *        whose d fails is counted in n_no_depth.  Pixels of the border ring are counted nowhere.
+ *     2. a = ((float)x - cx_l) / fx_l,  b = ((float)y - cy_l) / fy_l
+ *     3. Xx = ((R0 a + R1 b) + R2) + t0 d,  Xy = ((R3 a + R4 b) + R5) + t1 d,  Xz = ((R6 a + R7 b) + R8) + t2 d;
+ *        !(Xz > 0): counted in n_behind.
+ *     4. xn = Xx / Xz,  yn = Xy / Xz,  rho = d / Xz,  u = fx_l xn + cx_l,  v = fy_l yn + cy_l
+ *     5. inside iff u >= border && v >= border && u < (float)(w_l - 1 - border) && v < (float)(h_l - 1 - border), decided before
+ *        any conversion to an integer (a NaN fails it); else counted in n_outside.  border >= 1.
+ *     6. x0 = (int)u, y0 = (int)v, dx = u - x0, dy = v - y0 and the weights and sum order of flame_stereo_add_raw_frame:
+ *        w11 = dx dy, w01 = dx - w11, w10 = dy - w11, w00 = ((1 - dx) - dy) + w11,
+ *        value = ((w00 g00 + w01 g01) + w10 g10) + w11 g11, on the new frame's level image (I), gradx (gx) and grady (gy).
+ *     7. r = I - (float)I_ref(x, y);  Gx = fx_l gx,  Gy = fy_l gy,  xy = xn yn
+ *        J0 = Gx rho    J1 = Gy rho    J2 = -((Gx xn + Gy yn) rho)
+ *        J3 = -(Gx xy + Gy (1 + yn yn))    J4 = Gx (1 + xn xn) + Gy xy    J5 = Gy xn - Gx yn
+ *        the derivative of r for the left increment T <- exp(xi) T, xi = (v, omega), in the new camera's frame.
+ *     8. ar = |r|,  wgt = ar <= huber_k ? 1 : huber_k / ar; a pixel with wgt < 1 is also counted in n_huber.
+ *   Sums     28 doubles, each term formed in double from the float32 factors: H_ij = ((double)wgt (double)J_i) (double)J_j for
+ *            i <= j, row-major over the upper triangle (21); b_i = ((double)wgt (double)J_i) (double)r (6);
+ *            cost = ((double)wgt (double)r) (double)r.  The order of each sum is the rule of flame_nltgv2_map_error's `sum`
+ *            (flame_nltgv2.h) over the linear level-pixel index, +0.0 from every pixel that contributes nothing: chunks of 1024
+ *            consecutive indices, the last one padded; within a chunk p[t] += p[t + s] for s = 512 .. 1; the chunk partials
+ *            strided (q[t] = b[t] + b[t + 1024] + ... from +0.0), then pairwise.  No floating-point atomics: two calls give
+ *            the same bytes.
+ *   Counts   n_used + n_no_depth + n_behind + n_outside = the pixels inside the border ring; n_huber <= n_used.
+ *   Enqueues on the context's stream and waits once; the result comes through the context's pinned block;
+ *   flame_stereo_last_kernel_ms covers its kernels.  FLAME_NLTGV2_ERR_INVALID_ARG, with nothing changed, for: a NULL params, q, t
+ *   or out; an unknown frame id; a level not built for both frames; border < 1 or 2 border + 2 > min(w_l, h_l); both or neither
+ *   map pointer; huber_k <= 0 or not finite; a non-finite pose; a camera that is not of the form above.
+ *   FLAME_NLTGV2_ERR_NO_GRAPH without a camera.
+ *
+ * THE DRIVER (flame_stereo_align_frame).  State: q (unit, double) and t (double), from q_init (normalised on entry: q / sqrt(((w w +
+ * x x) + y y) + z z)) and t_init.  For level = coarsest_level down to finest_level:
+ *     1. linearise at T (the level's first evaluation; trace: delta = 0, accepted = 1).
+ *     2. n_used < min_pixels: end with status FLAME_STEREO_ALIGN_TOO_FEW and T as it is.
+ *     3. solve (H + lm_lambda diag H) delta = -b by a 6 x 6 Cholesky in double (L L^T, pivots in order, no pivoting); a pivot that
+ *        is not > 0 or a non-finite delta: raise FLAME_STEREO_ALIGN_FLAG_NOT_PD and end the level.
+ *     4. T' = exp(delta) T, delta = (v, o):  th2 = (o0 o0 + o1 o1) + o2 o2.  th2 < 1e-10:  A = 1 - th2 / 6, B = 0.5 - th2 / 24,
+ *        C = 1 / 6 - th2 / 120, Hs = 0.5 - th2 / 48, Hc = 1 - th2 / 8.  Else th = sqrt(th2):  A = sin th / th,
+ *        B = (1 - cos th) / th2, C = (th - sin th) / (th2 th), Hs = sin(0.5 th) / th, Hc = cos(0.5 th).
+ *        t' = ((t + A (o x t)) + B (o x (o x t))) + ((v + B (o x v)) + C (o x (o x v)))   per component,
+ *        (a x b)_0 = a1 b2 - a2 b1 and cyclic;  dq = (Hc, Hs o);  q' = dq (x) q (Hamilton product, each component left to right),
+ *        then q' / sqrt(((w w + x x) + y y) + z z).
+ *     5. linearise at T' (trace: the delta that led to it).  This is also the next iteration's system: one launch per iteration.
+ *     6. accept iff cost' / n_used' < cost / n_used, compared in double (n_used' = 0 is never accepted).  Rejected: keep T, raise
+ *        FLAME_STEREO_ALIGN_FLAG_REJECTED, end the level.
+ *     7. accepted: T = T'; end the level when max |delta_i| < min_step, or after max_iters_per_level iterations (then
+ *        FLAME_STEREO_ALIGN_FLAG_MAX_ITERS is raised).
+ *   Every evaluation appends one trace entry while there is room (max_trace); *n_trace is the number of evaluations made.
+ *   The defaults of flame_stereo_default_align_params are design choices of this library, not the reference's and not test
+ *   thresholds: border 2, huber_k 10 grey levels, coarsest_level 2, finest_level 0, max_iters_per_level 10, min_pixels 100,
+ *   min_step 1e-5, lm_lambda 0.
+ *   FLAME_NLTGV2_ERR_INVALID_ARG as for the linearisation at every level of the range, and for coarsest_level < finest_level,
+ *   finest_level < 0, max_iters_per_level < 1, min_pixels < 1, a negative or non-finite min_step or lm_lambda, a zero q_init,
+ *   max_trace < 0 or a NULL trace with max_trace > 0; nothing is enqueued then. */
+typedef struct flame_stereo_align_params {
+  int32_t border;              /* 2 */
+  float huber_k;               /* 10 */
+  int32_t coarsest_level;      /* 2 */
+  int32_t finest_level;        /* 0 */
+  int32_t max_iters_per_level; /* 10 */
+  int32_t min_pixels;          /* 100 */
+  double min_step;             /* 1e-5 */
+  double lm_lambda;            /* 0 */
+} flame_stereo_align_params;
+void flame_stereo_default_align_params(flame_stereo_align_params* p);
+
+typedef struct flame_stereo_align_system {
+  double H[21];   /* upper triangle, row-major: H00 H01 .. H05 H11 .. H55 */
+  double b[6];
+  double cost;
+  int32_t n_used, n_no_depth, n_behind, n_outside, n_huber;
+  int32_t reserved_;
+} flame_stereo_align_system;
+
+typedef struct flame_stereo_align_trace {
+  int32_t level;
+  int32_t accepted;   /* 1: a level's first evaluation, or an accepted step; 0: rejected */
+  double q[4], t[3];  /* the pose the evaluation was made at */
+  double delta[6];    /* the step that led to it (0 for a level's first evaluation) */
+  flame_stereo_align_system sys;
+} flame_stereo_align_trace;
+
+enum { FLAME_STEREO_ALIGN_OK = 0, FLAME_STEREO_ALIGN_TOO_FEW = 1 };
+enum { FLAME_STEREO_ALIGN_FLAG_NOT_PD = 1, FLAME_STEREO_ALIGN_FLAG_REJECTED = 2, FLAME_STEREO_ALIGN_FLAG_MAX_ITERS = 4 };
+
+typedef struct flame_stereo_align_result {
+  int32_t status;          /* FLAME_STEREO_ALIGN_OK or FLAME_STEREO_ALIGN_TOO_FEW */
+  int32_t flags;           /* FLAME_STEREO_ALIGN_FLAG_* */
+  double q[4], t[3];       /* the final pose */
+  float q_f32[4], t_f32[3], R_f32[9]; /* its roundings: what flame_stereo_pose takes, and the R the kernel saw */
+  double first_mean_cost;  /* cost / n_used of the first evaluation (NaN when n_used = 0) */
+  double last_mean_cost;   /* ... of the evaluation at the final pose */
+  int32_t iters[5];        /* accepted steps per level, by level */
+  int32_t n_evals;         /* linearisations made */
+} flame_stereo_align_result;
+
+int flame_stereo_build_pyramid(flame_stereo_ctx* ctx, uint32_t frame_id, int n_levels);
+int flame_stereo_download_pyramid_level(flame_stereo_ctx* ctx, uint32_t frame_id, int level, uint8_t* img, float* gradx,
+                                        float* grady);
+int flame_stereo_align_linearize(flame_stereo_ctx* ctx, const flame_stereo_align_params* params, uint32_t ref_frame_id,
+                                 uint32_t new_frame_id, int level, const float* idepthmap_host, const void* idepthmap_device,
+                                 const double q_ref_to_new[4], const double t_ref_to_new[3], flame_stereo_align_system* out);
+int flame_stereo_align_frame(flame_stereo_ctx* ctx, const flame_stereo_align_params* params, uint32_t ref_frame_id,
+                             uint32_t new_frame_id, const float* idepthmap_host, const void* idepthmap_device,
+                             const double q_init[4], const double t_init[3], flame_stereo_align_result* out,
+                             flame_stereo_align_trace* trace, int max_trace, int* n_trace);
+
 /* Options.  LANES_PER_FEATURE: 16 (a 16-lane row shares a feature and splits the epipolar walk), 1 (one lane walks the
  * whole per-feature body) or 0 (default: 16 up to 10240 features, 1 above -- whichever is faster on MI355X); same results
  * bit for bit.  GRAPH_COPY: how select_graph_features brings its arrays down: 0 (default) the whole output block in one
@@ -584,8 +731,8 @@ enum { FLAME_STEREO_OPT_LANES_PER_FEATURE = 1, FLAME_STEREO_OPT_GRAPH_COPY = 2, 
 int flame_stereo_set_option(flame_stereo_ctx* ctx, int option, int value);
 
 /* Device time of the last update kernel (or of the kernels of the last project_features / detect_features /
- * prune_pose_frames / prune_features / select_graph_features[_arrays] / draw_matches / draw_detections) in
- * milliseconds (HIP events on the context's stream); < 0 if none. */
+ * prune_pose_frames / prune_features / select_graph_features[_arrays] / draw_matches / draw_detections /
+ * build_pyramid / align_linearize, or of the last linearisation of align_frame) in milliseconds (HIP events on the context's stream); < 0 if none. */
 float flame_stereo_last_kernel_ms(flame_stereo_ctx* ctx);
 int flame_stereo_last_hip_error(const flame_stereo_ctx* ctx);
 
