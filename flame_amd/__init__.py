@@ -14,15 +14,20 @@ from .regularizer import (  # noqa: F401
     FuseCounts,
     FuseParams,
     FuseSource,
+    IntegrateCounts,
+    IntegrateParams,
     MapErrorParams,
     MapErrorStats,
     MeshFilterParams,
     MetricParams,
     NLTGV2Error,
     Params,
+    RaycastCounts,
+    RaycastParams,
     Regularizer,
     ViewCounts,
     ViewParams,
+    VolumeParams,
     WireframeParams,
     delaunay,
     library_path,

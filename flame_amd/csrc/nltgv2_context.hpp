@@ -400,6 +400,22 @@ struct flame_nltgv2_ctx {
     FuseWants want{};
     FuseLayout at{};
   } fuse_pending;
+  // flame_nltgv2_volume_* (volume_kernels.hip): the truncated-signed-distance volume, nx * ny * nz records {tsdf, weight}, written and read
+  // on the side stream only; it belongs to the context, not to a topology.  The two stages have device counters, pinned outputs and
+  // timing events of their own; the raycast's map stays in y_map until the next raycast.  Pinned: integrate_layout / raycast_layout
+  DevBuf vol, vi_counts, y_map, y_counts;
+  bool have_volume = false;
+  flame_nltgv2_volume_params vol_params{};
+  SideStage vint, vray;
+  struct IntegratePending {
+    int rows = 0, cols = 0;
+    VolumeLayout at{};
+  } vint_pending;
+  struct RaycastPending {
+    int rows = 0, cols = 0;
+    bool copy_out = false;
+    VolumeLayout at{};
+  } vray_pending;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

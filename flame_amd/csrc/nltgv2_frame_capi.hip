@@ -8,8 +8,10 @@
 //   the view renderer         render_view_begin / _end, render_view_arrays: the mesh seen from another camera, the nearest surface kept
 //   the kept meshes           keep_mesh, keep_mesh_arrays, drop_mesh, kept_mesh_info, get_kept_mesh: what a pose-frame keeps of its mesh
 //   the fusion of views       fuse_views_begin / _end: up to eight kept or live meshes in one camera, a vote per pixel
+//   the volumetric map        volume_create / _reset / _destroy / _info / _download / _upload; volume_integrate_begin / _end: a depth map folded
+//                             into the truncated-signed-distance volume; volume_raycast_begin / _end: the volume seen from a camera
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
-// The eight begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// The ten begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
 // they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
 // the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
@@ -24,6 +26,7 @@
 #include "metric_kernels.h"
 #include "nltgv2_context.hpp"
 #include "view_kernels.h"
+#include "volume_kernels.h"
 #include "wireframe_kernels.h"
 
 // Which state a mesh stage on the side stream describes (interpolate_mesh_begin, mesh_outputs_begin), and the wait that lets `rs` read
@@ -104,6 +107,12 @@ static_assert(sizeof(flame_hip::ViewCounts) == sizeof(flame_nltgv2_view_counts) 
               "the counters on the device, in the header and in view_layout are one struct");
 static_assert(sizeof(flame_hip::FuseCounts) == sizeof(flame_nltgv2_fuse_counts) && sizeof(flame_nltgv2_fuse_counts) == kFuseCountBytes,
               "the counters on the device, in the header and in fuse_layout are one struct");
+static_assert(sizeof(flame_hip::IntegrateCounts) == sizeof(flame_nltgv2_integrate_counts) && sizeof(flame_nltgv2_integrate_counts) == kIntegrateCountBytes,
+              "the counters on the device, in the header and in integrate_layout are one struct");
+static_assert(sizeof(flame_hip::RaycastCounts) == sizeof(flame_nltgv2_raycast_counts) && sizeof(flame_nltgv2_raycast_counts) == kRaycastCountBytes,
+              "the counters on the device, in the header and in raycast_layout are one struct");
+static_assert(flame_hip::kVolumeCountsBytes == kCountSetsBytes && flame_hip::kVolumeCountSlots == kCountSets &&
+              flame_hip::kVolumeCountSlotWords == kCountSetWords, "the kernels' and the layouts' partial sets of counters");
 static_assert(flame_hip::kFuseSources == FLAME_NLTGV2_FUSE_SOURCES, "the kernels' and the header's number of sources");
 
 extern "C" {
@@ -1204,6 +1213,287 @@ int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_param
   if (inlier_mask_out) std::memcpy(inlier_mask_out, v.inlier_mask, n);
   if (spread_out) std::memcpy(spread_out, v.spread, sizeof(float) * n);
   if (layers_out) std::memcpy(layers_out, v.layers, sizeof(float) * n * (size_t)v.n_sources);
+  if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
+}
+
+// ---- the volumetric map (see flame_nltgv2.h) ---------------------------------------------------------------------------------------------
+void flame_nltgv2_default_volume_params(flame_nltgv2_volume_params* p) {
+  if (!p) return;
+  p->nx = p->ny = p->nz = 64;
+  p->voxel_size = 0.05f;
+  p->origin[0] = p->origin[1] = p->origin[2] = 0.0f;
+  p->trunc = 0.15f;
+  p->max_weight = 64.0f;
+}
+
+void flame_nltgv2_default_integrate_params(flame_nltgv2_integrate_params* p) {
+  if (!p) return;
+  p->weight = 1.0f;
+  p->near_depth = 0.0f;
+  p->min_depth = 0.0f, p->max_depth = HUGE_VALF;
+  p->use_filtered_map = 0, p->reserved = 0;
+  p->map_device = nullptr;
+}
+
+void flame_nltgv2_default_raycast_params(flame_nltgv2_raycast_params* p) {
+  if (!p) return;
+  p->z_near = 0.1f, p->dz = 0.05f;
+  p->n_steps = 64;
+  p->copy_out = 1;
+}
+
+static bool finite_positive(float v) { return std::isfinite(v) && v > 0.0f; }
+
+static flame_hip::VolumeGrid volume_grid(const flame_nltgv2_ctx* ctx) {
+  const flame_nltgv2_volume_params& p = ctx->vol_params;
+  flame_hip::VolumeGrid g;
+  g.nx = p.nx, g.ny = p.ny, g.nz = p.nz;
+  g.voxel_size = p.voxel_size;
+  std::memcpy(g.origin, p.origin, sizeof(g.origin));
+  g.trunc = p.trunc, g.max_weight = p.max_weight;
+  return g;
+}
+static size_t volume_count(const flame_nltgv2_ctx* ctx) {
+  return (size_t)volume_voxels(ctx->vol_params.nx, ctx->vol_params.ny, ctx->vol_params.nz);
+}
+
+// The side stream may still hold an integration that writes the volume or a raycast that reads it: it is waited for, then the memory
+// goes back (hipFree waits for the device: an open run is asked to stop first, as in ensure()).
+static int volume_release(flame_nltgv2_ctx* ctx) {
+  ctx->have_volume = false;
+  if (!ctx->vol.p) return FLAME_NLTGV2_OK;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  request_open_stop(ctx);
+  HIPCHK(ctx, hipFree(ctx->vol.p));
+  ctx->device_bytes -= ctx->vol.cap;
+  ctx->vol.p = nullptr, ctx->vol.cap = 0;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_create(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_params* params) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_create");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!params || volume_voxels(params->nx, params->ny, params->nz) == 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!finite_positive(params->voxel_size) || !finite_positive(params->trunc) || !finite_positive(params->max_weight))
+    return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(params->origin[a])) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  // exactly the bytes of the volume (ensure() would take half as much again: up to a GiB for nothing)
+  const size_t bytes = sizeof(flame_hip::Voxel) * (size_t)volume_voxels(params->nx, params->ny, params->nz);
+  if (ctx->vol.cap != bytes) {
+    rc = volume_release(ctx);
+    if (rc) return rc;
+    const hipError_t e = hipMalloc(&ctx->vol.p, bytes);
+    if (e != hipSuccess) {
+      ctx->last_hip = (int)e;
+      ctx->vol.p = nullptr;
+      return fail(ctx, e == hipErrorOutOfMemory ? FLAME_NLTGV2_ERR_OOM : FLAME_NLTGV2_ERR_HIP);
+    }
+    ctx->vol.cap = bytes;
+    ctx->device_bytes += bytes;
+  }
+  ctx->vol_params = *params;
+  ctx->have_volume = true;
+  LAUNCHCHK(ctx, flame_hip::launch_volume_fill(volume_grid(ctx), (flame_hip::Voxel*)ctx->vol.p, ctx->raster_stream));
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_reset(flame_nltgv2_ctx* ctx) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_reset");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  LAUNCHCHK(ctx, flame_hip::launch_volume_fill(volume_grid(ctx), (flame_hip::Voxel*)ctx->vol.p, ctx->raster_stream));
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_destroy(flame_nltgv2_ctx* ctx) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_destroy");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  return volume_release(ctx);
+}
+
+int flame_nltgv2_volume_info(flame_nltgv2_ctx* ctx, flame_nltgv2_volume_params* params_out, int64_t* device_bytes_out) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (params_out) *params_out = ctx->vol_params;
+  if (device_bytes_out) *device_bytes_out = (int64_t)ctx->vol.cap;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_download(flame_nltgv2_ctx* ctx, float* tsdf_out, float* weight_out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_download");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const size_t n = volume_count(ctx);
+  std::vector<flame_hip::Voxel> h(n);
+  HIPCHK(ctx, hipMemcpyAsync(h.data(), ctx->vol.p, sizeof(flame_hip::Voxel) * n, hipMemcpyDeviceToHost, ctx->raster_stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  for (size_t i = 0; i < n; ++i) {
+    if (tsdf_out) tsdf_out[i] = h[i].tsdf;
+    if (weight_out) weight_out[i] = h[i].weight;
+  }
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_upload(flame_nltgv2_ctx* ctx, const float* tsdf, const float* weight) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_upload");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume || !tsdf || !weight) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const size_t n = volume_count(ctx);
+  std::vector<flame_hip::Voxel> h(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (!(weight[i] >= 0.0f)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+    h[i].tsdf = tsdf[i], h[i].weight = weight[i];
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->vol.p, h.data(), sizeof(flame_hip::Voxel) * n, hipMemcpyHostToDevice, ctx->raster_stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));  // (h leaves scope)
+  return FLAME_NLTGV2_OK;
+}
+
+// The integration on the side stream.  Like the metric stage it reads what the other stages left on the device, in the order of that
+// stream, and nothing of the canonical arrays: no mesh_state_on, no side_kernels_read_last.
+int flame_nltgv2_volume_integrate_begin(flame_nltgv2_ctx* ctx, const float* K, const float* T_cam_world,
+                                        const flame_nltgv2_integrate_params* params, int rows, int cols) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_integrate_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!K || !T_cam_world || !params || rows <= 0 || cols <= 0 || (uint64_t)rows * (uint64_t)cols >= (1ull << 31)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!finite_positive(params->weight)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const float* map = nullptr;
+  if (params->map_device) {
+    map = (const float*)params->map_device;
+  } else {
+    if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+    if (params->use_filtered_map) {
+      if (ctx->fmap_rows != rows || ctx->fmap_cols != cols || !ctx->m_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      map = (const float*)ctx->m_img.p;
+    } else {
+      if (ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+      map = (const float*)ctx->r_img.p;
+    }
+  }
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::IntegratePending ip;
+  ip.rows = rows, ip.cols = cols;
+  ip.at = integrate_layout();
+  rc = open_stage(ctx, ctx->vint, ip.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->vi_counts, kCountSetsBytes);
+  if (rc) return rc;
+  ctx->vint.active = false;  // (from here on the pinned outputs are being rewritten)
+  flame_hip::IntegrateArgs a;
+  std::memcpy(a.K, K, sizeof(a.K));
+  std::memcpy(a.pose, T_cam_world, sizeof(a.pose));
+  a.rows = rows, a.cols = cols;
+  a.weight = params->weight, a.near_depth = params->near_depth, a.min_depth = params->min_depth, a.max_depth = params->max_depth;
+  int* counts = (int*)ctx->vi_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->vint.ev0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_volume_integrate(volume_grid(ctx), a, map, (flame_hip::Voxel*)ctx->vol.p, counts, rs));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->vint.h.p + ip.at.counts, counts, kCountSetsBytes, hipMemcpyDeviceToHost, rs));
+  ctx->vint_pending = ip;
+  return close_stage(ctx, ctx->vint);
+}
+
+int flame_nltgv2_volume_integrate_end(flame_nltgv2_ctx* ctx, flame_nltgv2_integrate_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_integrate_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::IntegratePending& ip = ctx->vint_pending;
+  if (!out || !ctx->vint.h.p || !ctx->vint.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  out->rows = ip.rows, out->cols = ip.cols;
+  out->device_ms = stage_ms(ctx->vint);
+  out->reserved = 0;
+  sum_count_slots((const int32_t*)(ctx->vint.h.p + ip.at.counts), (int)(sizeof(out->counts) / sizeof(int32_t)), (int32_t*)&out->counts);
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_integrate(flame_nltgv2_ctx* ctx, const float* K, const float* T_cam_world,
+                                  const flame_nltgv2_integrate_params* params, int rows, int cols, flame_nltgv2_integrate_counts* counts_out) {
+  int rc = flame_nltgv2_volume_integrate_begin(ctx, K, T_cam_world, params, rows, cols);
+  if (rc) return rc;
+  flame_nltgv2_integrate_view v;
+  rc = flame_nltgv2_volume_integrate_end(ctx, &v);
+  if (rc) return rc;
+  if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
+}
+
+// The raycast on the side stream: it reads the volume alone.
+int flame_nltgv2_volume_raycast_begin(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                      const flame_nltgv2_raycast_params* params, int rows, int cols) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_raycast_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!Kinv || !T_world_cam || !params || !view_size_ok(rows, cols)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (!std::isfinite(params->z_near) || !finite_positive(params->dz) || params->n_steps < 1 || params->n_steps > 4096)
+    return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const size_t n = (size_t)rows * (size_t)cols;
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::RaycastPending rp;
+  rp.rows = rows, rp.cols = cols, rp.copy_out = params->copy_out != 0;
+  rp.at = raycast_layout(rows, cols, rp.copy_out);
+  rc = open_stage(ctx, ctx->vray, rp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->y_map, sizeof(float) * n);
+  if (!rc) rc = ensure(ctx, ctx->y_counts, kCountSetsBytes);
+  if (rc) return rc;
+  ctx->vray.active = false;  // (from here on the pinned outputs are being rewritten)
+  flame_hip::RaycastArgs a;
+  std::memcpy(a.Kinv, Kinv, sizeof(a.Kinv));
+  std::memcpy(a.pose, T_world_cam, sizeof(a.pose));
+  a.rows = rows, a.cols = cols;
+  a.z_near = params->z_near, a.dz = params->dz, a.n_steps = params->n_steps;
+  int* counts = (int*)ctx->y_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->vray.ev0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_volume_raycast(volume_grid(ctx), a, (const flame_hip::Voxel*)ctx->vol.p, (float*)ctx->y_map.p, counts, rs));
+  char* h = ctx->vray.h.p;
+  HIPCHK(ctx, hipMemcpyAsync(h + rp.at.counts, counts, kCountSetsBytes, hipMemcpyDeviceToHost, rs));
+  if (rp.copy_out) HIPCHK(ctx, hipMemcpyAsync(h + rp.at.map, ctx->y_map.p, sizeof(float) * n, hipMemcpyDeviceToHost, rs));
+  ctx->vray_pending = rp;
+  return close_stage(ctx, ctx->vray);
+}
+
+int flame_nltgv2_volume_raycast_end(flame_nltgv2_ctx* ctx, flame_nltgv2_raycast_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_raycast_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::RaycastPending& rp = ctx->vray_pending;
+  if (!out || !ctx->vray.h.p || !ctx->vray.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  const char* h = ctx->vray.h.p;
+  out->rows = rp.rows, out->cols = rp.cols;
+  out->device_ms = stage_ms(ctx->vray);
+  out->reserved = 0;
+  sum_count_slots((const int32_t*)(h + rp.at.counts), (int)(sizeof(out->counts) / sizeof(int32_t)), (int32_t*)&out->counts);
+  out->map = rp.copy_out ? (const float*)(h + rp.at.map) : nullptr;
+  out->map_device = ctx->y_map.p;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                const flame_nltgv2_raycast_params* params, int rows, int cols, float* map_out,
+                                flame_nltgv2_raycast_counts* counts_out) {
+  flame_nltgv2_raycast_params p;
+  flame_nltgv2_default_raycast_params(&p);
+  if (params) p = *params;
+  p.copy_out = 1;
+  int rc = flame_nltgv2_volume_raycast_begin(ctx, Kinv, T_world_cam, params ? &p : nullptr, rows, cols);
+  if (rc) return rc;
+  flame_nltgv2_raycast_view v;
+  rc = flame_nltgv2_volume_raycast_end(ctx, &v);
+  if (rc) return rc;
+  if (map_out) std::memcpy(map_out, v.map, sizeof(float) * (size_t)v.rows * (size_t)v.cols);
   if (counts_out) *counts_out = v.counts;
   return FLAME_NLTGV2_OK;
 }

@@ -1,7 +1,7 @@
 // side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
 // images, the wireframe, the metric outputs, the map error, the view renderer, the fusion of views), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
 // outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it (MetricLayout:
-// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc; FuseLayout: tests/cpp/fuse_layout_test.cc).
+// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc; FuseLayout: tests/cpp/fuse_layout_test.cc; VolumeLayout: tests/cpp/volume_layout_test.cc).
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
@@ -201,6 +201,48 @@ inline FuseLayout fuse_layout(int rows, int cols, int n_sources, const FuseWants
   l.layers = l.spread + up16(out && w.spread ? f * n : 0);
   l.total = l.layers + up16(out && w.layers ? f * n * (size_t)n_sources : 0) + 16;
   return l;
+}
+
+// The volume's two stages (flame_nltgv2_volume_integrate_begin, flame_nltgv2_volume_raycast_begin), each with a pinned buffer of its own.
+constexpr size_t kIntegrateCountBytes = 8 * sizeof(int32_t);  // flame_nltgv2_integrate_counts
+constexpr size_t kRaycastCountBytes = 4 * sizeof(int32_t);    // flame_nltgv2_raycast_counts
+// The counters come down as the kernels keep them: kCountSets partial sets, one 128-byte line apart (volume_kernels.h), which _end sums.
+constexpr int kCountSets = 16, kCountSetWords = 32;
+constexpr size_t kCountSetsBytes = sizeof(int32_t) * kCountSets * kCountSetWords;
+constexpr int kVolumeMaxAxis = 1024;
+constexpr uint64_t kVolumeMaxVoxels = 1ull << 28;
+struct VolumeLayout {
+  // the counters' partial sets | rows*cols floats.  The counters are always there; an integration has no map, a raycast's takes room only
+  // with copy_out.
+  size_t counts, map, total;
+};
+inline VolumeLayout integrate_layout() {
+  VolumeLayout v;
+  v.counts = 0;
+  v.map = up16(kCountSetsBytes);
+  v.total = v.map + 16;
+  return v;
+}
+inline VolumeLayout raycast_layout(int rows, int cols, bool copy_out) {
+  VolumeLayout v;
+  v.counts = 0;
+  v.map = up16(kCountSetsBytes);
+  v.total = v.map + up16(copy_out ? sizeof(float) * (size_t)rows * (size_t)cols : 0) + 16;
+  return v;
+}
+// out[c] = the sum over the partial sets of their word c, for the n_words counters of a stage.
+inline void sum_count_slots(const int32_t* slots, int n_words, int32_t* out) {
+  for (int c = 0; c < n_words; ++c) {
+    int32_t sum = 0;
+    for (int s = 0; s < kCountSets; ++s) sum += slots[s * kCountSetWords + c];
+    out[c] = sum;
+  }
+}
+// Voxels of an nx x ny x nz volume; 0 for dimensions flame_nltgv2_volume_create refuses.
+inline uint64_t volume_voxels(int nx, int ny, int nz) {
+  if (nx < 1 || ny < 1 || nz < 1 || nx > kVolumeMaxAxis || ny > kVolumeMaxAxis || nz > kVolumeMaxAxis) return 0;
+  const uint64_t n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+  return n <= kVolumeMaxVoxels ? n : 0;
 }
 
 // Every index of T triangles names one of V vertices.

@@ -254,6 +254,61 @@ class _FuseOutputsView(C.Structure):
                 + [f for name, typ in _FUSE_ARRAYS for f in ((name, typ), (name + "_device", C.c_void_p))])
 
 
+class VolumeParams(C.Structure):
+    """== flame_nltgv2_volume_params (same defaults): nx, ny, nz voxels of voxel_size metres, origin = the world position of the centre
+    of voxel (0, 0, 0), the truncation distance and the weight at which a voxel saturates."""
+
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
+                ("trunc", C.c_float), ("max_weight", C.c_float)]
+
+    def __init__(self, nx=64, ny=64, nz=64, voxel_size=0.05, origin=(0.0, 0.0, 0.0), trunc=0.15, max_weight=64.0):
+        super().__init__(int(nx), int(ny), int(nz), float(voxel_size),
+                         (C.c_float * 3)(*np.asarray(origin, np.float32).reshape(3).tolist()), float(trunc), float(max_weight))
+
+
+class IntegrateParams(C.Structure):
+    """== flame_nltgv2_integrate_params (same defaults): the call's weight, the near plane, the depth window (exclusive, metres) and
+    which map, under the rules of MetricParams: the resident unfiltered one, the filtered one, or map_device."""
+
+    _fields_ = [("weight", C.c_float), ("near_depth", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("use_filtered_map", C.c_int32), ("reserved", C.c_int32), ("map_device", C.c_void_p)]
+
+    def __init__(self, weight=1.0, near_depth=0.0, min_depth=0.0, max_depth=float("inf"), use_filtered_map=False, map_device=None):
+        super().__init__(weight, near_depth, min_depth, max_depth, int(bool(use_filtered_map)), 0, int(map_device) if map_device else None)
+
+
+class IntegrateCounts(C.Structure):
+    """== flame_nltgv2_integrate_counts: 8 words."""
+
+    _fields_ = [("front", C.c_int32), ("in_image", C.c_int32), ("valid", C.c_int32), ("behind", C.c_int32), ("updated", C.c_int32),
+                ("saturated", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class _IntegrateView(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("device_ms", C.c_float), ("reserved", C.c_int32), ("counts", IntegrateCounts)]
+
+
+class RaycastParams(C.Structure):
+    """== flame_nltgv2_raycast_params (same defaults): the first sample's depth, the step, the number of steps, and whether the map
+    travels to the host."""
+
+    _fields_ = [("z_near", C.c_float), ("dz", C.c_float), ("n_steps", C.c_int32), ("copy_out", C.c_int32)]
+
+    def __init__(self, z_near=0.1, dz=0.05, n_steps=64, copy_out=True):
+        super().__init__(z_near, dz, int(n_steps), int(bool(copy_out)))
+
+
+class RaycastCounts(C.Structure):
+    """== flame_nltgv2_raycast_counts."""
+
+    _fields_ = [("hits", C.c_int32), ("back", C.c_int32), ("empty", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _RaycastView(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("device_ms", C.c_float), ("reserved", C.c_int32), ("counts", RaycastCounts),
+                ("map", _FP), ("map_device", C.c_void_p)]
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -348,6 +403,10 @@ ABI_SYMBOLS = (
     "flame_nltgv2_render_view_arrays",
     "flame_nltgv2_keep_mesh", "flame_nltgv2_keep_mesh_arrays", "flame_nltgv2_drop_mesh", "flame_nltgv2_kept_mesh_info", "flame_nltgv2_get_kept_mesh",
     "flame_nltgv2_default_fuse_params", "flame_nltgv2_fuse_views_begin", "flame_nltgv2_fuse_views_end", "flame_nltgv2_fuse_views",
+    "flame_nltgv2_default_volume_params", "flame_nltgv2_default_integrate_params", "flame_nltgv2_default_raycast_params",
+    "flame_nltgv2_volume_create", "flame_nltgv2_volume_reset", "flame_nltgv2_volume_destroy", "flame_nltgv2_volume_info",
+    "flame_nltgv2_volume_download", "flame_nltgv2_volume_upload", "flame_nltgv2_volume_integrate_begin", "flame_nltgv2_volume_integrate_end",
+    "flame_nltgv2_volume_integrate", "flame_nltgv2_volume_raycast_begin", "flame_nltgv2_volume_raycast_end", "flame_nltgv2_volume_raycast",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -456,6 +515,21 @@ def load_library():
         "flame_nltgv2_fuse_views_end": (C.c_int, [ctx, C.POINTER(_FuseOutputsView)]),
         "flame_nltgv2_fuse_views": (C.c_int, [ctx, C.POINTER(FuseParams), C.c_int, C.c_int, _FP, C.c_void_p, C.c_void_p, _FP, _FP,
                                               C.POINTER(FuseCounts)]),
+        "flame_nltgv2_default_volume_params": (None, [C.POINTER(VolumeParams)]),
+        "flame_nltgv2_default_integrate_params": (None, [C.POINTER(IntegrateParams)]),
+        "flame_nltgv2_default_raycast_params": (None, [C.POINTER(RaycastParams)]),
+        "flame_nltgv2_volume_create": (C.c_int, [ctx, C.POINTER(VolumeParams)]),
+        "flame_nltgv2_volume_reset": (C.c_int, [ctx]),
+        "flame_nltgv2_volume_destroy": (C.c_int, [ctx]),
+        "flame_nltgv2_volume_info": (C.c_int, [ctx, C.POINTER(VolumeParams), C.POINTER(C.c_int64)]),
+        "flame_nltgv2_volume_download": (C.c_int, [ctx, _FP, _FP]),
+        "flame_nltgv2_volume_upload": (C.c_int, [ctx, _FP, _FP]),
+        "flame_nltgv2_volume_integrate_begin": (C.c_int, [ctx, _FP, _FP, C.POINTER(IntegrateParams), C.c_int, C.c_int]),
+        "flame_nltgv2_volume_integrate_end": (C.c_int, [ctx, C.POINTER(_IntegrateView)]),
+        "flame_nltgv2_volume_integrate": (C.c_int, [ctx, _FP, _FP, C.POINTER(IntegrateParams), C.c_int, C.c_int, C.POINTER(IntegrateCounts)]),
+        "flame_nltgv2_volume_raycast_begin": (C.c_int, [ctx, _FP, _FP, C.POINTER(RaycastParams), C.c_int, C.c_int]),
+        "flame_nltgv2_volume_raycast_end": (C.c_int, [ctx, C.POINTER(_RaycastView)]),
+        "flame_nltgv2_volume_raycast": (C.c_int, [ctx, _FP, _FP, C.POINTER(RaycastParams), C.c_int, C.c_int, _FP, C.POINTER(RaycastCounts)]),
         "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
         "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
                                                       C.c_int]),
@@ -1018,6 +1092,99 @@ class Regularizer:
         """fuse_views_begin; fuse_views_end."""
         self.fuse_views_begin(params, rows, cols)
         return self.fuse_views_end()
+
+    # -- the volumetric map: integrate depth maps, raycast a view (flame_nltgv2_volume_*) ---------------------------------------------------
+    def volume_create(self, params: VolumeParams = None):
+        """Makes the context's truncated-signed-distance volume, every voxel {tsdf 1, weight 0}; replaces an existing one."""
+        p = params if params is not None else VolumeParams()
+        self._chk(self._L.flame_nltgv2_volume_create(self._ctx, C.byref(p)), "volume_create")
+
+    def volume_reset(self):
+        self._chk(self._L.flame_nltgv2_volume_reset(self._ctx), "volume_reset")
+
+    def volume_destroy(self):
+        self._chk(self._L.flame_nltgv2_volume_destroy(self._ctx), "volume_destroy")
+
+    def volume_info(self) -> dict:
+        """-> dict(nx, ny, nz, voxel_size, origin (3,), trunc, max_weight, device_bytes)."""
+        p, b = VolumeParams(), C.c_int64()
+        self._chk(self._L.flame_nltgv2_volume_info(self._ctx, C.byref(p), C.byref(b)), "volume_info")
+        return dict(nx=int(p.nx), ny=int(p.ny), nz=int(p.nz), voxel_size=float(p.voxel_size), origin=np.array(list(p.origin), np.float32),
+                    trunc=float(p.trunc), max_weight=float(p.max_weight), device_bytes=int(b.value))
+
+    def volume_download(self) -> dict:
+        """-> dict(tsdf, weight), each (nz, ny, nx) f32: voxel (i, j, k) is [k, j, i]."""
+        i = self.volume_info()
+        shape = (i["nz"], i["ny"], i["nx"])
+        tsdf, weight = np.empty(shape, np.float32), np.empty(shape, np.float32)
+        self._chk(self._L.flame_nltgv2_volume_download(self._ctx, tsdf.ctypes.data_as(_FP), weight.ctypes.data_as(_FP)), "volume_download")
+        return dict(tsdf=tsdf, weight=weight)
+
+    def volume_upload(self, tsdf, weight):
+        """Replaces every voxel (for tests of the raycast); both arrays hold nx * ny * nz floats, voxel (i, j, k) at [k, j, i]."""
+        i = self.volume_info()
+        n = i["nx"] * i["ny"] * i["nz"]
+        t, w = _as(tsdf, np.float32, n, "tsdf"), _as(weight, np.float32, n, "weight")
+        self._chk(self._L.flame_nltgv2_volume_upload(self._ctx, t.ctypes.data_as(_FP), w.ctypes.data_as(_FP)), "volume_upload")
+
+    @staticmethod
+    def _pose12(pose, name):
+        t = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1)[:12])
+        if t.size != 12:
+            raise ValueError(f"{name}: expected 12 floats, row-major [R | t]")
+        return t
+
+    def volume_integrate_begin(self, K, T_cam_world, rows, cols, params: IntegrateParams = None):
+        """Enqueues the integration of one (rows, cols) inverse-depth map seen from T_cam_world (12 floats, row-major [R | t]) on the
+        side stream and returns.  The map is the resident one, the filtered one or params.map_device."""
+        k = np.ascontiguousarray(K, np.float32).reshape(9)
+        t = self._pose12(T_cam_world, "T_cam_world")
+        p = params if params is not None else IntegrateParams()
+        self._chk(self._L.flame_nltgv2_volume_integrate_begin(self._ctx, k.ctypes.data_as(_FP), t.ctypes.data_as(_FP), C.byref(p), rows, cols),
+                  "volume_integrate_begin")
+
+    def volume_integrate_end(self) -> dict:
+        """Waits for the side stream; dict(rows, cols, device_ms, counts (8 i32, as they lie on the device), front, in_image, valid,
+        behind, updated, saturated)."""
+        v = _IntegrateView()
+        self._chk(self._L.flame_nltgv2_volume_integrate_end(self._ctx, C.byref(v)), "volume_integrate_end")
+        out = dict(rows=int(v.rows), cols=int(v.cols), device_ms=float(v.device_ms), counts=np.frombuffer(bytes(v.counts), np.int32).copy())
+        out.update({k: int(getattr(v.counts, k)) for k, _ in IntegrateCounts._fields_ if k != "reserved"})
+        return out
+
+    def volume_integrate(self, K, T_cam_world, rows, cols, params: IntegrateParams = None) -> dict:
+        """volume_integrate_begin; volume_integrate_end."""
+        self.volume_integrate_begin(K, T_cam_world, rows, cols, params)
+        return self.volume_integrate_end()
+
+    def volume_raycast_begin(self, Kinv, T_world_cam, rows, cols, params: RaycastParams = None):
+        """Enqueues the volume seen from T_world_cam (12 floats, row-major [R | t]) through Kinv as a (rows, cols) inverse-depth map on
+        the side stream and returns."""
+        k = np.ascontiguousarray(Kinv, np.float32).reshape(9)
+        t = self._pose12(T_world_cam, "T_world_cam")
+        p = params if params is not None else RaycastParams()
+        self._chk(self._L.flame_nltgv2_volume_raycast_begin(self._ctx, k.ctypes.data_as(_FP), t.ctypes.data_as(_FP), C.byref(p), rows, cols),
+                  "volume_raycast_begin")
+
+    def volume_raycast_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(rows, cols, device_ms, counts (4 i32), hits, back, empty, device = {"map": address} and,
+        with copy_out, map (rows, cols) f32 with NaN on holes).  copy=False: a view of the context's pinned memory, valid until the
+        next begin."""
+        v = _RaycastView()
+        self._chk(self._L.flame_nltgv2_volume_raycast_end(self._ctx, C.byref(v)), "volume_raycast_end")
+        out = dict(rows=int(v.rows), cols=int(v.cols), device_ms=float(v.device_ms), counts=np.frombuffer(bytes(v.counts), np.int32).copy(),
+                   hits=int(v.counts.hits), back=int(v.counts.back), empty=int(v.counts.empty), device={})
+        if v.map_device:
+            out["device"]["map"] = int(v.map_device)
+        if v.map:
+            a = np.ctypeslib.as_array(v.map, shape=(v.rows, v.cols))
+            out["map"] = a.copy() if copy else a
+        return out
+
+    def volume_raycast(self, Kinv, T_world_cam, rows, cols, params: RaycastParams = None) -> dict:
+        """volume_raycast_begin; volume_raycast_end."""
+        self.volume_raycast_begin(Kinv, T_world_cam, rows, cols, params)
+        return self.volume_raycast_end()
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

@@ -294,6 +294,34 @@ struct FusedView {
   FusedView() { std::memset(&counts, 0, sizeof(counts)); }
 };
 
+// The volumetric map's parameters (flame_nltgv2_volume_params, flame_nltgv2_integrate_params, flame_nltgv2_raycast_params, each
+// constructed with its defaults).  The C-ABI structs themselves: the header states every rule.
+struct VolumeParams : flame_nltgv2_volume_params {
+  VolumeParams() { flame_nltgv2_default_volume_params(this); }
+};
+struct IntegrateParams : flame_nltgv2_integrate_params {
+  IntegrateParams() { flame_nltgv2_default_integrate_params(this); }
+};
+struct RaycastParams : flame_nltgv2_raycast_params {
+  RaycastParams() { flame_nltgv2_default_raycast_params(this); }
+};
+
+// What one integration did (flame_nltgv2_integrate_view): the six counters.
+struct IntegratedMap {
+  int rows = 0, cols = 0;
+  flame_nltgv2_integrate_counts counts;
+  IntegratedMap() { std::memset(&counts, 0, sizeof(counts)); }
+};
+
+// The volume seen from a camera (flame_nltgv2_raycast_view): the inverse depth of the surface per pixel (NaN on holes) and the counters.
+// The host pointer into pinned memory of the DeviceGraph (nullptr with copy_out == 0) and the device pointer of the same array; both
+// valid until its next volumeRaycastBegin().
+struct RaycastView {
+  int rows = 0, cols = 0;
+  flame_nltgv2_raycast_counts counts = {0, 0, 0, 0};
+  const float* idepthmap = nullptr;    const void* idepthmap_device = nullptr;  // [rows * cols]
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -548,6 +576,43 @@ class DeviceGraph {
     r.inlier_mask = v.inlier_mask, r.inlier_mask_device = v.inlier_mask_device;
     r.spread = v.spread, r.spread_device = v.spread_device;
     r.layers = v.layers, r.layers_device = v.layers_device;
+    return r;
+  }
+
+  // The volumetric map of the context (flame_nltgv2_volume_*; the rules are stated there): one truncated-signed-distance volume that
+  // outlives every upload() and sync(), a depth map folded into it from a pose, and the volume seen from any camera -- all on the side
+  // stream.  volumeIntegrateBegin reads the resident map of the last interpolateMesh[Begin], the filtered one or params.map_device
+  // (e.g. FusedView::idepthmap_device); RaycastView::idepthmap_device serves FeatureTracker::alignFrame, MapErrorParams::truth_device and
+  // MetricParams::map_device.  K, Kinv: 9 floats row-major; T_cam_world, T_world_cam: 12 floats, row-major [R | t].
+  void volumeCreate(const VolumeParams& params) { check(flame_nltgv2_volume_create(ctx_, &params), "volume_create"); }
+  void volumeReset() { check(flame_nltgv2_volume_reset(ctx_), "volume_reset"); }
+  void volumeDestroy() { check(flame_nltgv2_volume_destroy(ctx_), "volume_destroy"); }
+  VolumeParams volumeInfo(int64_t* device_bytes = nullptr) {
+    VolumeParams p;
+    check(flame_nltgv2_volume_info(ctx_, &p, device_bytes), "volume_info");
+    return p;
+  }
+  void volumeDownload(float* tsdf, float* weight) { check(flame_nltgv2_volume_download(ctx_, tsdf, weight), "volume_download"); }
+  void volumeUpload(const float* tsdf, const float* weight) { check(flame_nltgv2_volume_upload(ctx_, tsdf, weight), "volume_upload"); }
+  void volumeIntegrateBegin(const float K[9], const float T_cam_world[12], const IntegrateParams& params, int rows, int cols) {
+    check(flame_nltgv2_volume_integrate_begin(ctx_, K, T_cam_world, &params, rows, cols), "volume_integrate_begin");
+  }
+  IntegratedMap volumeIntegrateEnd() {
+    flame_nltgv2_integrate_view v;
+    check(flame_nltgv2_volume_integrate_end(ctx_, &v), "volume_integrate_end");
+    IntegratedMap r;
+    r.rows = v.rows, r.cols = v.cols, r.counts = v.counts;
+    return r;
+  }
+  void volumeRaycastBegin(const float Kinv[9], const float T_world_cam[12], const RaycastParams& params, int rows, int cols) {
+    check(flame_nltgv2_volume_raycast_begin(ctx_, Kinv, T_world_cam, &params, rows, cols), "volume_raycast_begin");
+  }
+  RaycastView volumeRaycastEnd() {
+    flame_nltgv2_raycast_view v;
+    check(flame_nltgv2_volume_raycast_end(ctx_, &v), "volume_raycast_end");
+    RaycastView r;
+    r.rows = v.rows, r.cols = v.cols, r.counts = v.counts;
+    r.idepthmap = v.map, r.idepthmap_device = v.map_device;
     return r;
   }
 

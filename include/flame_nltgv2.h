@@ -790,6 +790,152 @@ int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_param
                             uint8_t* present_mask_out, uint8_t* inlier_mask_out, float* spread_out, float* layers_out,
                             flame_nltgv2_fuse_counts* counts_out);
 
+/* ---- Volumetric map: integrate depth maps, raycast a view -------------------------------------------------------------------------------
+ * One truncated-signed-distance volume per context, resident on the device: the map that keeps what pruned pose-frames saw.  Two stages
+ * on the side stream work on it beside a running solver: flame_nltgv2_volume_integrate_begin folds one inverse-depth map, seen from one
+ * pose, into it; flame_nltgv2_volume_raycast_begin renders it into any pinhole camera as a dense inverse-depth map on the device, which
+ * serves flame_stereo_align_frame as idepthmap_device (frame-to-model tracking), flame_nltgv2_map_error_params.truth_device (consistency
+ * against everything seen so far) and flame_nltgv2_metric_params.map_device.  The reference has no counterpart, so the rules are stated
+ * here in full (UNPINNED); tests/volume_ref.py restates them in numpy float32 and is the checker: device and checker agree bit for bit.
+ * All arithmetic is float32 without FMA, every sum of three products left to right, divisions correctly rounded.
+ *
+ * THE STORE.  nx, ny, nz each in 1 .. 1024 with nx * ny * nz <= 2^28; voxel_size, trunc, max_weight finite and > 0; origin (finite) is
+ *   the world position of the CENTRE of voxel (0, 0, 0).  A voxel is the record {float tsdf; float weight} at linear index
+ *   (k * ny + j) * nx + i, x fastest; a fresh or reset voxel is {1.0f, 0.0f}.  The volume survives flame_nltgv2_upload_graph,
+ *   flame_nltgv2_sync_graph / _sync_commit and every change of topology, as the kept meshes do; it is written and read on the context's
+ *   side stream only, so stream order covers every hazard between the calls below.
+ *   flame_nltgv2_volume_create    makes the volume, every voxel {1, 0}; on a context that already has one it replaces it.  An error in
+ *                                 the parameters leaves an existing volume as it is.
+ *   flame_nltgv2_volume_reset     every voxel {1, 0} again.
+ *   flame_nltgv2_volume_destroy   frees it (flame_nltgv2_destroy does too).
+ *   flame_nltgv2_volume_info      the parameters it was created with and the bytes it takes on the device (each pointer may be NULL).
+ *   flame_nltgv2_volume_download  synchronous: nx * ny * nz floats each, in the linear order above (each pointer may be NULL).
+ *   flame_nltgv2_volume_upload    synchronous, both arrays required: it exists so that a raycast can be tested on voxel values an
+ *                                 integration would never produce, and checks weight >= 0 for every voxel (a NaN is not) and nothing else.
+ *   Every call but create on a context without a volume answers FLAME_NLTGV2_ERR_INVALID_ARG.
+ *
+ * INTEGRATION, per voxel (i, j, k), with K (9 floats row-major) and T_cam_world (12 floats, row-major [R | t]):
+ *   1 centre     p = origin + (float)index * voxel_size, per axis; P = ((r0 * p.x + r1 * p.y) + r2 * p.z) + t, row by row.
+ *   2 front      the voxel is skipped unless P.z > near_depth.                                               counter `front`
+ *   3 projection q = K * P, the full 3x3 product; u = q.x / q.z, v = q.y / q.z.
+ *   4 in image   iff u >= -0.5f && u < (float)cols - 0.5f && v >= -0.5f && v < (float)rows - 0.5f.  The test comes first, so that no
+ *                NaN or huge value reaches a conversion.                                                     counter `in_image`
+ *   5 pixel      col = (int)floorf(u + 0.5f), row = (int)floorf(v + 0.5f), both clamped to the image: the NEAREST pixel, no
+ *                interpolation -- a hole must not bleed.
+ *   6 validity   d = map[row * cols + col]; zm = 1.0f / d; valid iff d > 0.0f && zm > min_depth && zm < max_depth: the rule of the
+ *                metric outputs, so a NaN, zero, negative or infinite d is a hole.                           counter `valid`
+ *   7 distance   sdf = zm - P.z: projective, along the optical axis.  A voxel with sdf < -trunc is left alone.   counter `behind`
+ *   8 truncation s = fminf(sdf / trunc, 1.0f).
+ *   9 update     W = w_old + weight; tsdf = ((tsdf_old * w_old) + (s * weight)) / W; w = fminf(W, max_weight).  counter `updated`;
+ *                `saturated` counts the updated voxels with W > max_weight.
+ *   The counters nest: updated = valid - behind <= valid <= in_image <= front.  A voxel that is not updated is not written, and its
+ *   record is not loaded either: the tests of 2 - 7 come before the load.  Each voxel has one owner; there are no floating-point
+ *   atomics: the same calls in the same order give the same bytes.  Integration is not commutative in float32: the order of the
+ *   calls is part of the result.  Only the counters come down (2 KiB: sixteen partial sets, which _end sums).
+ *   WHICH MAP: exactly as flame_nltgv2_metric_params: map_device (rows * cols floats on the context's device, taken on trust; read on
+ *   the side stream, which waits for no stream of the caller's: its writer must have completed before begin, and it must stay allocated
+ *   and unchanged until _end has returned), else use_filtered_map != 0: the filtered map of the last
+ *   flame_nltgv2_mesh_outputs_begin(want_filtered_map != 0), else the resident unfiltered map of the last
+ *   flame_nltgv2_interpolate_mesh[_begin]; a resident map must have the size rows x cols.  Unlike the metric stage a graph is needed
+ *   only when a resident map is read (FLAME_NLTGV2_ERR_NO_GRAPH).
+ *
+ * RAYCAST, per pixel (row, col), with Kinv (9 floats) and T_world_cam (12 floats); rows, cols in 1 .. 32767; z_near, dz finite, dz > 0;
+ * n_steps in 1 .. 4096:
+ *   q = Kinv * (col, row, 1), as in the metric outputs.  For n = 0 .. n_steps - 1:
+ *     z_n = z_near + (float)n * dz: a product, not a running sum;  Pc = q * z_n, componentwise;  p = T_world_cam applied as in rule 1;
+ *     g = (p - origin) / voxel_size, per axis;
+ *     the sample is VALID iff every g lies in [0, n_axis - 1] and all eight voxels around it have weight > 0; an axis with
+ *     n_axis == 1 has no valid sample;
+ *     i0 = min((int)floorf(g), n_axis - 2), f = g - (float)i0, so g == n_axis - 1 gives f == 1;
+ *     the value is trilinear with lerp(a, b, t) = a + t * (b - a), along x, then y, then z.
+ *   The ray ENDS at the first valid sample with value <= 0.  It is a HIT iff the sample of step n - 1 was valid and > 0: then
+ *   z* = z_{n-1} + dz * (f_prev / (f_prev - f_cur)) with the two values, and the pixel is 1.0f / (z* * q.z).  Otherwise the surface was
+ *   met from inside or behind: the pixel is a hole, counted in `back`.  A ray that never ends is a hole, counted in `empty` if it had
+ *   no valid sample at all.  Holes are the quiet NaN 0x7fc00000.
+ *   The view follows the other stages: the host pointer, the device pointer beside it, device_ms; all valid until the next
+ *   flame_nltgv2_volume_raycast_begin.  With copy_out == 0 only the counters travel (2 KiB, as above) and the host pointer is NULL.
+ *
+ * begin  (both stages) checks the arguments -- an error (no volume; a NULL matrix or params; rows / cols out of range; integration:
+ *        weight not finite or <= 0, no map of the kind asked for or one of another size; raycast: z_near or dz not finite, dz <= 0,
+ *        n_steps out of range) is reported before anything is enqueued and leaves the volume, the outputs of an earlier begin and its
+ *        pending _end as they are --, then enqueues everything on the context's side stream and returns.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_volume_integrate / flame_nltgv2_volume_raycast == begin (the raycast with copy_out forced to 1); end; copies into the
+ *        caller's arrays (each may be NULL).
+ * Not done: normals, colour, surface extraction, a sparse or hashed volume, a volume that moves with the camera. */
+typedef struct flame_nltgv2_volume_params {
+  int32_t nx, ny, nz;      /* 64, 64, 64 */
+  float   voxel_size;      /* 0.05       metres */
+  float   origin[3];       /* 0          the world position of the centre of voxel (0, 0, 0) */
+  float   trunc;           /* 0.15       metres */
+  float   max_weight;      /* 64.0 */
+} flame_nltgv2_volume_params;
+void flame_nltgv2_default_volume_params(flame_nltgv2_volume_params* p);
+
+typedef struct flame_nltgv2_integrate_params {
+  float   weight;            /* 1.0        finite and > 0 */
+  float   near_depth;        /* 0.0        metres, exclusive */
+  float   min_depth;         /* 0.0        metres, exclusive */
+  float   max_depth;         /* +infinity  metres, exclusive */
+  int32_t use_filtered_map;  /* 0 */
+  int32_t reserved;          /* 0 */
+  const void* map_device;    /* NULL       a caller's own device map: see WHICH MAP above for its rules */
+} flame_nltgv2_integrate_params;
+void flame_nltgv2_default_integrate_params(flame_nltgv2_integrate_params* p);
+
+/* The counters, as they lie on the device and in pinned memory: 8 words. */
+typedef struct flame_nltgv2_integrate_counts {
+  int32_t front, in_image, valid, behind, updated, saturated;
+  int32_t reserved[2];
+} flame_nltgv2_integrate_counts;
+
+typedef struct flame_nltgv2_integrate_view {
+  int32_t rows, cols;
+  float   device_ms;       /* measurement aid: HIP-event time of what begin enqueued on the side stream */
+  int32_t reserved;
+  flame_nltgv2_integrate_counts counts;
+} flame_nltgv2_integrate_view;
+
+typedef struct flame_nltgv2_raycast_params {
+  float   z_near;          /* 0.1        metres: the depth of the first sample along the optical axis */
+  float   dz;              /* 0.05       metres, > 0 */
+  int32_t n_steps;         /* 64         1 .. 4096 */
+  int32_t copy_out;        /* 1  0: the map stays on the device; only the counters travel */
+} flame_nltgv2_raycast_params;
+void flame_nltgv2_default_raycast_params(flame_nltgv2_raycast_params* p);
+
+typedef struct flame_nltgv2_raycast_counts {
+  int32_t hits, back, empty, reserved;
+} flame_nltgv2_raycast_counts;
+
+/* map: pinned memory of the context (NULL with copy_out == 0); map_device: the same array on the device; both valid until the next
+ * flame_nltgv2_volume_raycast_begin. */
+typedef struct flame_nltgv2_raycast_view {
+  int32_t rows, cols;
+  float   device_ms;       /* measurement aid: HIP-event time of what begin enqueued on the side stream, kernel and copies out */
+  int32_t reserved;
+  flame_nltgv2_raycast_counts counts;
+  const float* map;        const void* map_device;   /* [rows * cols] inverse depths */
+} flame_nltgv2_raycast_view;
+
+int flame_nltgv2_volume_create(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_params* params);
+int flame_nltgv2_volume_reset(flame_nltgv2_ctx* ctx);
+int flame_nltgv2_volume_destroy(flame_nltgv2_ctx* ctx);
+int flame_nltgv2_volume_info(flame_nltgv2_ctx* ctx, flame_nltgv2_volume_params* params_out, int64_t* device_bytes_out);
+int flame_nltgv2_volume_download(flame_nltgv2_ctx* ctx, float* tsdf_out, float* weight_out);
+int flame_nltgv2_volume_upload(flame_nltgv2_ctx* ctx, const float* tsdf, const float* weight);
+int flame_nltgv2_volume_integrate_begin(flame_nltgv2_ctx* ctx, const float* K, const float* T_cam_world,
+                                        const flame_nltgv2_integrate_params* params, int rows, int cols);
+int flame_nltgv2_volume_integrate_end(flame_nltgv2_ctx* ctx, flame_nltgv2_integrate_view* out);
+int flame_nltgv2_volume_integrate(flame_nltgv2_ctx* ctx, const float* K, const float* T_cam_world,
+                                  const flame_nltgv2_integrate_params* params, int rows, int cols, flame_nltgv2_integrate_counts* counts_out);
+int flame_nltgv2_volume_raycast_begin(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                      const flame_nltgv2_raycast_params* params, int rows, int cols);
+int flame_nltgv2_volume_raycast_end(flame_nltgv2_ctx* ctx, flame_nltgv2_raycast_view* out);
+int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
+                                const flame_nltgv2_raycast_params* params, int rows, int cols, float* map_out,
+                                flame_nltgv2_raycast_counts* counts_out);
+
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
  * the rasteriser's key image, the canonical w1 / w2 and the frame's grey image.  (getDebugImageFeatures: flame_stereo_draw_features,
