@@ -91,6 +91,7 @@ class Volume:
         self.tsdf = np.where(updated, tsdf, self.tsdf).astype(F)
         self.weight = np.where(updated, w, self.weight).astype(F)
         flags = (front, in_image, valid, behind, updated, saturated)
+        self.flags = dict(zip(INTEGRATE_COUNTERS, flags))  # the last call's classes per voxel, (nz, ny, nx) bool: for tests that ask where
         return {k: int(np.count_nonzero(f)) for k, f in zip(INTEGRATE_COUNTERS, flags)}
 
     # -- the raycast --------------------------------------------------------------------------------------------------------------------
