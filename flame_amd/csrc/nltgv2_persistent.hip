@@ -57,8 +57,10 @@ namespace {
 //              all tags are the step's.  A poll that finds an old record only rewrites the slot with the bytes it already
 //              holds: a producer cannot publish step s+2 into that parity before this patch has published s+1, i.e.
 //              consumed s.  A vertex is published to memory only if another patch reads it.
-//   step       Straight-line code: the per-role selects of the dual update are folded into signed per-lane constants
-//              (exact: IEEE negation, a*(-b) == -(a*b)), the w1/w2 halves run as packed-f32 pairs.  The ordered
+//   step       Straight-line code: the per-role selects of the primal contributions are folded into signed per-lane constants
+//              (exact: IEEE negation, a*(-b) == -(a*b)); the dual update's (source - target) is sg * own - sg * neighbour in one
+//              rounding (an fma with sg = +-1: own - neighbour negated afterwards differs where the difference is a zero); the
+//              w1/w2 halves run as packed-f32 pairs.  The ordered
 //              accumulation (cc:120-142: ascending edge id) runs across the lanes of a vertex towards its first lane, which
 //              alone holds its state (patches are row-packed: a vertex's lanes inside one 16-lane row): shift j adds the
 //              contribution of lane first + j with the DPP row shift of a plain add, EXEC masks (moved in by the scalar
@@ -182,8 +184,13 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
   const float beta = q.w;
   float q1 = q.x;
   v2f_t q23 = {q.y, q.z};
-  // signed per-lane constants: the per-role selects of the dual update folded in ("step" above)
-  const float as = is_target ? -alpha : alpha, bs = is_target ? -beta : beta, ac = is_target ? alpha : -alpha;
+  // signed per-lane constants: the per-role selects of the primal contributions folded in ("step" above)
+  const float ac = is_target ? alpha : -alpha;
+  // the dual update takes (source - target) of the edge: this lane's own record enters it with the sign sg, the neighbour's with -sg
+  // (one rounding: sg * own is exact).  NOT (own - neighbour) times a negated weight: the same value except where it is a zero --
+  // x - x is +0.0 in either order and its negation is not, which a dual that is -0.0 would keep (tests/solver_special_cases.py).
+  const float sg = is_target ? -1.0f : 1.0f;
+  const v2f_t sg2 = {sg, sg};
   const v2f_t P12 = {alpha * dx, alpha * dy};
   // (a lane without a half-edge has all-zero constants and q = +0 for good: its (cx, a, b) come out as (-0, a, -0) with
   //  a = (-0) * C2 -- C2 = +0 there makes that -0 as well, so the head of an isolated vertex adds exactly nothing to its own state)
@@ -398,14 +405,14 @@ k_persistent_pv(const int wg_begin, const int n_wgs, const int wgs_per_xcd, cons
     xb = own.x, wb12 = v2f_t{own.y, own.z};
     // ---- dual update of this half-edge's private q copy (cc:99-110) ------------------------------
     const v2f_t nbw = {nbv.y, nbv.z};
-    const float d0 = xb - nbv.x;
-    const v2f_t d12 = wb12 - nbw;
+    const float d0 = __builtin_fmaf(nbv.x, -sg, sg * xb);                // x_bar: source - target
+    const v2f_t d12 = __builtin_elementwise_fma(nbw, -sg2, sg2 * wb12);   // (w1_bar, w2_bar): source - target
     const v2f_t wbi = is_target ? nbw : wb12;  // the SOURCE vertex's (w1_bar, w2_bar)
-    float K1 = as * d0;
+    float K1 = alpha * d0;
     const v2f_t m12 = P12 * wbi;
     K1 -= m12.x;
     K1 -= m12.y;
-    const v2f_t K23 = bs * d12;
+    const v2f_t K23 = beta * d12;
     const float q1r = q1 + p.step_q * K1;
     const v2f_t q23r = q23 + p.step_q * K23;
     q1 = __builtin_fminf(__builtin_fmaxf(q1r, -1.0f), 1.0f);

@@ -6,7 +6,8 @@
 // do (register copies that line up packed pairs, moves that assemble the record, pads, EXEC bookkeeping, a taken branch over the code
 // of larger degrees).  The compiler cannot be steered there (profiles/r06_hot_path_ab.txt), so ONE statement holds the step from its
 // first poll to the record in LDS, written by hand with fixed temporaries: the same IEEE operations in the same order as the general
-// kernel's (no FMA, the compare-and-select clamps of x, nothing re-associated), which is what keeps the result bit-identical.
+// kernel's (no contraction -- the one fma is the exact (source - target) of the dual update, as there --, the compare-and-select clamps
+// of x, nothing re-associated), which is what keeps the result bit-identical.
 // Compiled with -ffp-contract=off like the other kernels; counts of both kernels as built: profiles/pv_lean_path.txt.
 // NOT EXERCISED: the wait's bounded fallback (64 rounds without all tags: abort flag, spin budget, report_expired) is the general
 // kernel's logic written once more inside the statement, and no test reaches it -- the fault-injection hook, which is how the suite
@@ -122,12 +123,13 @@ k_persistent_pv_lean(const int wg_begin, const int n_wgs, const int wgs_per_xcd,
   const float beta = q.w;
   float q1 = q.x;
   v2f_t q23 = {q.y, q.z};
-  // signed per-lane constants: the per-role selects of the dual update folded in (nltgv2_persistent.hip, "step")
-  const float as = is_target ? -alpha : alpha, bs = is_target ? -beta : beta, ac = is_target ? alpha : -alpha;
+  // signed per-lane constants: the per-role selects of the primal contributions folded in (nltgv2_persistent.hip, "step")
+  const float ac = is_target ? alpha : -alpha;
+  const float sg = is_target ? -1.0f : 1.0f;  // the dual update takes (source - target): this lane's own record enters with this sign
   const v2f_t P12 = {alpha * dx, alpha * dy};
   const v2f_t C2 = !active ? v2f_t{0.0f, 0.0f} : is_target ? v2f_t{beta, beta} : v2f_t{-dx, -dy};
   const float nbeta = -beta;
-  const v2f_t bs2 = {bs, bs}, nbeta2 = {nbeta, nbeta};
+  const v2f_t beta2 = {beta, beta}, nbeta2 = {nbeta, nbeta}, sg2 = {sg, sg};
 
   float4 st = make_float4(0.f, 0.f, 0.f, 0.f), bs4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float2 aux = make_float2(0.f, 0.f);
@@ -309,13 +311,18 @@ k_persistent_pv_lean(const int wg_begin, const int n_wgs, const int wgs_per_xcd,
                    "2:\n\t"
                    "s_setprio 3\n\t"
                    // ---- dual update of this half-edge's private q copy (cc:99-110) ----
-                   "v_sub_f32 v76, v67, v66\n\t"
-                   "v_pk_add_f32 v[72:73], v[70:71], v[68:69] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+                   // (source - target) of the EDGE, whichever end this lane is: sg * own - sg * neighbour in one rounding (sg = +-1: the
+                   // product is exact).  own - neighbour times a negated weight is the same value except where it is a zero: x - x is +0.0
+                   // for either order, and its negation is not.
+                   "v_mul_f32 v76, %[sg], v67\n\t"
+                   "v_pk_mul_f32 v[72:73], %[sg2], v[70:71]\n\t"
+                   "v_fma_f32 v76, v66, -%[sg], v76\n\t"
+                   "v_pk_fma_f32 v[72:73], v[68:69], %[sg2], v[72:73] neg_lo:[0,1,0] neg_hi:[0,1,0]\n\t"
                    "v_cndmask_b32_e64 v75, v71, v69, %[itm]\n\t"
                    "v_cndmask_b32_e64 v74, v70, v68, %[itm]\n\t"
-                   "v_mul_f32 v76, %[as], v76\n\t"
+                   "v_mul_f32 v76, %[al], v76\n\t"
                    "v_pk_mul_f32 v[74:75], %[P12], v[74:75]\n\t"
-                   "v_pk_mul_f32 v[72:73], %[bs2], v[72:73]\n\t"
+                   "v_pk_mul_f32 v[72:73], %[be2], v[72:73]\n\t"
                    "v_sub_f32 v76, v76, v74\n\t"
                    "v_sub_f32 v76, v76, v75\n\t"
                    "v_mul_f32 v76, %[sq], v76\n\t"
@@ -395,7 +402,7 @@ k_persistent_pv_lean(const int wg_begin, const int n_wgs, const int wgs_per_xcd,
                      [xp] "+v"(x_prev), [wp] "+v"(w_prev)
                    : [src] "v"(src), [dst] "s"(dst), [ra] "v"(rd_nbr), [fa] "v"(own_slot), [ro] "v"(rd_own), [wo] "v"(wr_own), [pr] "v"(pub_r),
                      [pl2] "v"(pub_l), [tag] "s"(s), [tagn] "s"(s_next), [fm] "s"(fetch_mask), [itm] "s"(it_mask), [pubm] "s"(pub_mask),
-                     [recm] "s"(rec_mask), [as] "v"(as), [P12] "v"(P12), [bs2] "v"(bs2), [ac] "v"(ac), [C2] "v"(C2), [nb2] "v"(nbeta2),
+                     [recm] "s"(rec_mask), [al] "v"(alpha), [sg] "v"(sg), [sg2] "v"(sg2), [P12] "v"(P12), [be2] "v"(beta2), [ac] "v"(ac), [C2] "v"(C2), [nb2] "v"(nbeta2),
                      [nz] "v"(neg_zero), [dat] "v"(data), [thr] "v"(thr), [xmnv] "v"(x_min_v), [xmxv] "v"(x_max_v), [sq] "s"(p.step_q),
                      [sq2] "s"(sq2), [sx] "s"(p.step_x), [sx2] "s"(sx2), [th] "s"(p.theta), [th2] "s"(th2), [xmn] "s"(p.x_min), [xmx] "s"(p.x_max),
                      [fmx] "s"(3.402823466e+38f), [abp] "s"(abort_flag), [omax] "s"(max_spins >> 4), [md] "s"(stride), [m1] "s"(rm1), [m2] "s"(rm2), [m3] "s"(rm3), [m4] "s"(rm4), [m5] "s"(rm5),
@@ -469,7 +476,7 @@ unsigned pv_lean_lds_bytes(int lcap, int slab_slots) { return 16u * (unsigned)(2
 // kernel runs in has at most kPvPaceAbovePerCu = 13 patches per CU, four waves per SIMD hold them (tests/test_pv_lean.py re-derives the
 // figure from the compiler's resource report).
 int pv_lean_real_waves_per_simd() {
-  // {VGPRs, SGPRs} -> waves: {<= 104, <= 96} -> min(4, 7)
+  // {VGPRs, SGPRs} -> waves: {<= 128, <= 96} -> min(4, 7)  (105 / 95 as built)
   return 4;
 }
 

@@ -11,10 +11,12 @@ namespace flame_hip {
 
 namespace {
 
-// The per-half-edge constants of one slot (see k_persistent_pv: the role selects folded into signed constants)
+// The per-half-edge constants of one slot (see k_persistent_pv: the role selects folded into signed constants; as = alpha at the edge's
+// source, -alpha at its target: its magnitude is the weight, its sign the one this lane's own record takes in the dual update's
+// (source - target) -- taken from it in the step, since this kernel has no register to spare for a constant of its own)
 struct SlotConst {
   bool active, is_target;
-  float as, bs, ac, nbeta, beta;
+  float as, ac, nbeta, beta;
   v2f_t P12, C2;
 };
 
@@ -82,7 +84,7 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
     c.beta = q.w;
     q1 = q.x;
     q23 = v2f_t{q.y, q.z};
-    c.as = c.is_target ? -alpha : alpha, c.bs = c.is_target ? -c.beta : c.beta, c.ac = c.is_target ? alpha : -alpha;
+    c.as = c.is_target ? -alpha : alpha, c.ac = c.is_target ? alpha : -alpha;
     c.P12 = v2f_t{alpha * dx, alpha * dy};
     c.C2 = !active ? v2f_t{0.0f, 0.0f} : c.is_target ? v2f_t{c.beta, c.beta} : v2f_t{-dx, -dy};
     c.nbeta = -c.beta;
@@ -267,14 +269,17 @@ k_persistent_pv2(const int wg_begin, const int n_wgs, const int wgs_per_xcd, con
     v2f_t a0, b0, a1, b1, q23r0, q23r1;
     auto edge = [&](const SlotConst& c, const v4f_t nbv, float& q1, v2f_t& q23, float& cx, v2f_t& a12, v2f_t& b12, float& q1r, v2f_t& q23r) {
       const v2f_t nbw = {nbv.y, nbv.z};
-      const float d0 = xb - nbv.x;
-      const v2f_t d12 = wb12 - nbw;
+      // (source - target) in one rounding, sg * own exact: not (own - neighbour) negated, which differs where it is a zero (k_persistent_pv)
+      const float sg = __builtin_copysignf(1.0f, c.as);
+      const v2f_t sg2 = {sg, sg};
+      const float d0 = __builtin_fmaf(nbv.x, -sg, sg * xb);
+      const v2f_t d12 = __builtin_elementwise_fma(nbw, -sg2, sg2 * wb12);
       const v2f_t wbi = c.is_target ? nbw : wb12;
-      float K1 = c.as * d0;
+      float K1 = __builtin_fabsf(c.as) * d0;
       const v2f_t m12 = c.P12 * wbi;
       K1 -= m12.x;
       K1 -= m12.y;
-      const v2f_t K23 = c.bs * d12;
+      const v2f_t K23 = c.beta * d12;
       q1r = q1 + p.step_q * K1;
       q23r = q23 + p.step_q * K23;
       q1 = __builtin_fminf(__builtin_fmaxf(q1r, -1.0f), 1.0f);

@@ -19,7 +19,8 @@ def _prox_conj(q):
     return (q / np.where(absq > 1, absq, F(1))).astype(F)
 
 
-def step(g: dict, p: dict) -> None:
+def step(g: dict, p: dict) -> bool:
+    """One step in place.  Returns whether a new dual came out NaN: the reference's FLAME_ASSERT(!isnan(new_q)), h:174."""
     sx, sq, th, lam = F(p["step_x"]), F(p["step_q"]), F(p["theta"]), F(p["data_factor"])
     xmin, xmax = F(p["x_min"]), F(p["x_max"])
     i, j = g["src"], g["dst"]
@@ -39,6 +40,7 @@ def step(g: dict, p: dict) -> None:
     g["q1"][:] = _prox_conj(g["q1"] + sq * K1)
     g["q2"][:] = _prox_conj(g["q2"] + sq * (be * (w1b[i] - w1b[j])))
     g["q3"][:] = _prox_conj(g["q3"] + sq * (be * (w2b[i] - w2b[j])))
+    bad = bool(np.isnan(g["q1"]).any() or np.isnan(g["q2"]).any() or np.isnan(g["q3"]).any())
 
     # primalStep cc:116-154: per-edge sequence of in-place updates, kept in order
     t1 = (g["q1"] * sx) * al
@@ -73,8 +75,11 @@ def step(g: dict, p: dict) -> None:
     g["x_bar"][:] = nb
     g["w1_bar"][:] = g["w1"] + th * (g["w1"] - g["w1_prev"])
     g["w2_bar"][:] = g["w2"] + th * (g["w2"] - g["w2_prev"])
+    return bad
 
 
-def run(g: dict, n_iters: int, p: dict) -> None:
+def run(g: dict, n_iters: int, p: dict) -> bool:
+    bad = False
     for _ in range(n_iters):
-        step(g, p)
+        bad = step(g, p) or bad
+    return bad

@@ -29,6 +29,34 @@ def assert_state_equal(a: dict, b: dict, keys=OUT_KEYS, what=""):
                                  f"{int((d > 0).sum())}/{d.size} elements")
 
 
+ALL_STATE_KEYS = OUT_KEYS + ("x_prev", "w1_prev", "w2_prev")
+CANONICAL_NAN = 0x7FC00000
+
+
+def float_bits(a):
+    """The float32 bit patterns of `a`, every NaN mapped to one pattern: IEEE 754 leaves the sign and payload of a NaN that an
+    operation GENERATES to the implementation (x86 SSE makes 0xFFC00000, gfx950 0x7FC00000) and the reference never reads
+    them; tests/test_mesh_outputs.py::bits does the same for the mesh outputs.  Where a NaN stands is compared, and every
+    bit of every other value: signed zeros, subnormals and infinities included."""
+    f = np.ascontiguousarray(a, np.float32)
+    u = f.view(np.uint32).copy()
+    u[np.isnan(f)] = CANONICAL_NAN
+    return u
+
+
+def assert_state_bits_equal(a: dict, b: dict, keys=ALL_STATE_KEYS, what=""):
+    """assert_state_equal on the bit patterns: -0.0 is not +0.0 here, and a NaN equals any other NaN."""
+    for k in keys:
+        ua, ub = float_bits(a[k]), float_bits(b[k])
+        if ua.shape != ub.shape:
+            raise AssertionError(f"{what}: {k} has shape {ua.shape} against {ub.shape}")
+        diff = np.flatnonzero(ua != ub)
+        if diff.size:
+            i = int(diff[0])
+            raise AssertionError(f"{what}: {k} differs in its bits, first at [{i}]: 0x{int(ua[i]):08X} against 0x{int(ub[i]):08X}, "
+                                 f"{diff.size}/{ua.size} elements")
+
+
 def rms(a, b):
     d = a.astype(np.float64) - b.astype(np.float64)
     return float(np.sqrt(np.mean(d * d))) if d.size else 0.0
