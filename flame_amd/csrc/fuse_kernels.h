@@ -18,18 +18,8 @@ struct FuseCounts {
 constexpr int kFuseCountWords = 32;
 static_assert(sizeof(FuseCounts) == kFuseCountWords * sizeof(int32_t), "the counters are 32 words");
 
-// One source of a batch: its camera into the target, its mesh on the device, and where its vertices and triangles start in the batch's
-// concatenated numbering (prefix sums of V and T).
-struct FuseSource {
-  ViewCamera cam;
-  const float2* pos;
-  const float* values;
-  const int32_t* tris;
-  const uint8_t* tri_valid;  // NULL: every triangle is valid
-  float value_scale, weight;
-  int32_t v0, t0;
-};
-// The table travels by value in the kernel arguments (under 2 KB).  v_end / t_end: the sums over all sources.
+// The sources of a batch (FuseSource: view_kernels.h).  The table travels by value in the kernel arguments (under 2 KB).  v_end /
+// t_end: the sums of V and T over all sources.
 struct FuseTable {
   FuseSource s[kFuseSources];
   int32_t n, v_end, t_end;

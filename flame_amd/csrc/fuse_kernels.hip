@@ -11,19 +11,21 @@
 //               over a compile-time 8 (or 1, 2, 4 where fewer sources are named) with presence predicates -- no array is indexed by a
 //               run-time value, nothing goes to scratch (profiles/fuse_views.txt has the compiler's resource report); inliers, the weighted mean left to right, masks, spread;
 //               the counters through ballot + popcount per wave, LDS per workgroup, one global atomic per non-zero counter
+// clear, vertices and the three triangle kernels are thin instances of the bodies in view_project.hpp, which view_kernels.hip
+// instantiates for its one source: here the sources are the FuseTable, and of rule 2's classes the drawn one alone is published (word
+// 26 of FuseCounts).  keep and vote are this file's own.
 // The source table travels by value in the kernel arguments.  No floating-point atomics: two calls give the same bytes.  Built with
 // -ffp-contract=off (no FMA); division is correctly rounded.
 #include <hip/hip_runtime.h>
 
 #include "fuse_kernels.h"
-#include "view_device.hpp"
+#include "view_project.hpp"
 
 namespace flame_hip {
 namespace {
 
-using namespace view_device;  // rules 1 - 5, shared with view_kernels.hip
+using namespace view_project;  // the five bodies, shared with view_kernels.hip; FuseTable is this file's model of the sources
 
-constexpr int kPerThread = kViewResolveTile / 256;
 constexpr unsigned kHoleBits = 0x7fc00000u;
 // words of FuseCounts
 constexpr int kWordCoverage = 0, kWordHist = 1, kWordPresent = kWordHist + kFuseSources + 1, kWordInlier = kWordPresent + kFuseSources,
@@ -45,103 +47,26 @@ k_fuse_clear(long n, unsigned long long* __restrict__ keys, int* __restrict__ co
     if (threadIdx.x < kFuseCountWords) counts[threadIdx.x] = 0;
     if (threadIdx.x == 0) big[0] = 0;
   }
-  const long base = (long)blockIdx.x * kViewResolveTile + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < kPerThread; ++j) {
-    const long i = base + (long)j * 256;
-    if (i < n) keys[i] = 0ull;
-  }
-}
-
-// The source that vertex v (by v0) or triangle t (by t0) of the concatenated numbering belongs to: the last one that starts at or
-// before it.  Empty sources share their start with the next one and are passed over.
-__device__ __forceinline__ int source_of_vertex(const FuseTable& tab, int v) {
-  int k = 0;
-#pragma unroll
-  for (int j = 1; j < kFuseSources; ++j) k += (j < tab.n && v >= tab.s[j].v0) ? 1 : 0;
-  return k;
-}
-__device__ __forceinline__ int source_of_triangle(const FuseTable& tab, int t) {
-  int k = 0;
-#pragma unroll
-  for (int j = 1; j < kFuseSources; ++j) k += (j < tab.n && t >= tab.s[j].t0) ? 1 : 0;
-  return k;
+  clear_tile(n, keys);
 }
 
 __global__ void __launch_bounds__(256)
-k_fuse_vertices(FuseTable tab, ViewVertex* __restrict__ out) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= tab.v_end) return;
-  const FuseSource& S = tab.s[source_of_vertex(tab, v)];
-  const int local = v - S.v0;
-  out[v] = view_vertex(S.pos[local], S.values[local] * S.value_scale, S.cam);
-}
+k_fuse_vertices(FuseTable tab, ViewVertex* __restrict__ out) { project_vertices(tab, out); }
 
-struct FuseTriangle {
-  ViewVertex a, b, c;
-};
-__device__ __forceinline__ FuseTriangle load_triangle(const FuseSource& S, int local, const ViewVertex* __restrict__ vtx) {
-  const int32_t* tri = S.tris + 3 * (size_t)local;
-  return FuseTriangle{vtx[S.v0 + tri[0]], vtx[S.v0 + tri[1]], vtx[S.v0 + tri[2]]};
-}
-
-// One lane per triangle of any source: drawn ones counted (one atomic per workgroup), large boxes listed as big[2 + 2 i] = source,
-// big[3 + 2 i] = the triangle's index in its source; big[0] counts them.
 __global__ void __launch_bounds__(256)
 k_fuse_count(FuseTable tab, const ViewVertex* __restrict__ vtx, int* __restrict__ counts, int* __restrict__ big, int rows, int cols) {
-  __shared__ int s_drawn;
-  if (threadIdx.x == 0) s_drawn = 0;
-  __syncthreads();
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  bool drawn = false;
-  if (t < tab.t_end) {
-    const int k = source_of_triangle(tab, t);
-    const FuseSource& S = tab.s[k];
-    const int local = t - S.t0;
-    const FuseTriangle tr = load_triangle(S, local, vtx);
-    long long A = 0;
-    drawn = classify(local, S.tri_valid, tr.a, tr.b, tr.c, &A) == kDraw;
-    if (drawn && bounding_box(tr.a, tr.b, tr.c, rows, cols).n > (unsigned)kViewWavePixels) {
-      const int at = atomicAdd(&big[0], 1);
-      big[2 + 2 * at] = k, big[3 + 2 * at] = local;
-    }
-  }
-  const int n = __popcll(__ballot(drawn));
-  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&s_drawn, n);
-  __syncthreads();
-  if (threadIdx.x == 0 && s_drawn) atomicAdd(&counts[kWordDrawn], s_drawn);
+  count_triangles(tab, vtx, big, rows, cols, [=](const int* n) { if (n[kDraw]) atomicAdd(&counts[kWordDrawn], n[kDraw]); });
 }
 
-// One wavefront per triangle whose box holds at most kViewWavePixels pixels: the others are k_fuse_raster_big's.
 __global__ void __launch_bounds__(64)
 k_fuse_raster(FuseTable tab, const ViewVertex* __restrict__ vtx, unsigned long long* __restrict__ keys, int rows, int cols) {
-  const int t = blockIdx.x;
-  if (t >= tab.t_end) return;
-  const int k = source_of_triangle(tab, t);
-  const FuseSource& S = tab.s[k];
-  const int local = t - S.t0;
-  const FuseTriangle tr = load_triangle(S, local, vtx);
-  long long A = 0;
-  if (classify(local, S.tri_valid, tr.a, tr.b, tr.c, &A) != kDraw) return;
-  const ViewBox box = bounding_box(tr.a, tr.b, tr.c, rows, cols);
-  if (box.n > (unsigned)kViewWavePixels) return;
-  raster_pixels(local, A, tr.a, tr.b, tr.c, box, threadIdx.x, 64u, keys + (size_t)k * (size_t)rows * (size_t)cols, cols);
+  raster_triangle(tab, vtx, keys, rows, cols);
 }
 
-// The listed triangles: kViewBigWaves wavefronts share one triangle's box (blockIdx.x: which of them), blockIdx.y walks the list.
 __global__ void __launch_bounds__(64)
 k_fuse_raster_big(FuseTable tab, const ViewVertex* __restrict__ vtx, const int* __restrict__ big, unsigned long long* __restrict__ keys,
                   int rows, int cols) {
-  const int n_big = big[0];
-  for (int item = blockIdx.y; item < n_big; item += gridDim.y) {
-    const int k = big[2 + 2 * item], local = big[3 + 2 * item];
-    const FuseSource& S = tab.s[k];
-    const FuseTriangle tr = load_triangle(S, local, vtx);
-    long long A = 0;
-    (void)classify(local, nullptr, tr.a, tr.b, tr.c, &A);  // (listed: drawn)
-    raster_pixels(local, A, tr.a, tr.b, tr.c, bounding_box(tr.a, tr.b, tr.c, rows, cols), blockIdx.x * 64u + threadIdx.x, 64u * kViewBigWaves,
-                  keys + (size_t)k * (size_t)rows * (size_t)cols, cols);
-  }
+  raster_listed(tab, vtx, big, keys, rows, cols);
 }
 
 struct FuseVote {
@@ -247,8 +172,6 @@ k_fuse_vote(FuseVote p, long n, const unsigned long long* __restrict__ keys, Fus
   __syncthreads();
   if (threadIdx.x < kWordDrawn && s_n[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_n[threadIdx.x]);
 }
-
-inline dim3 tiles(long n) { return dim3((unsigned)((n + kViewResolveTile - 1) / kViewResolveTile)); }
 
 }  // namespace
 

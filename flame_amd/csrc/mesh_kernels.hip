@@ -17,6 +17,7 @@
 // list alone.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.hpp"
 #include "mesh_kernels.h"
 
 namespace flame_hip {
@@ -120,30 +121,13 @@ k_mesh_triangles(int T, const int32_t* __restrict__ tris, const float2* __restri
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(n_valid, n);
 }
 
-// Exclusive scan of the V + 1 counts in place, one workgroup: a chunk per thread, the chunk totals through LDS.
-constexpr int kScanThreads = 1024;
+// Exclusive scan of the V + 1 counts in place, one workgroup (block_scan.hpp).
 __global__ void __launch_bounds__(kScanThreads)
 k_mesh_scan(int n, int* __restrict__ offset, int* __restrict__ cursor) {
-  __shared__ int s_sum[kScanThreads];
-  const int chunk = (n + kScanThreads - 1) / kScanThreads;
-  const int lo = min((int)threadIdx.x * chunk, n), hi = min(lo + chunk, n);
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += offset[i];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kScanThreads; d <<= 1) {  // inclusive scan of the chunk totals
-    const int add = threadIdx.x >= (unsigned)d ? s_sum[threadIdx.x - d] : 0;
-    __syncthreads();
-    s_sum[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int run = s_sum[threadIdx.x] - sum;
-  for (int i = lo; i < hi; ++i) {
-    const int c = offset[i];
+  block_exclusive_scan(n, offset, [=](int i, int run) {
     offset[i] = run;
     if (i < n - 1) cursor[i] = run;  // (entry n - 1 is the total: it has no list)
-    run += c;
-  }
+  });
 }
 
 __global__ void __launch_bounds__(256)

@@ -17,6 +17,7 @@
 // consecutive bytes, was measured and was 4-11 % SLOWER (profiles/metric_outputs.txt): it is not done.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.hpp"
 #include "metric_kernels.h"
 
 namespace flame_hip {
@@ -90,31 +91,11 @@ k_metric_pixels(MetricArgs a, const float* __restrict__ map, float* __restrict__
   }
 }
 
-// Exclusive scan of n counts in place, their sum to *total; one workgroup: a chunk per thread, the chunk totals through LDS.
-constexpr int kScanThreads = 1024;
+// Exclusive scan of n counts in place, their sum to *total; one workgroup (block_scan.hpp).
 __global__ void __launch_bounds__(kScanThreads)
 k_metric_scan(int n, int* __restrict__ count, int* __restrict__ total) {
-  __shared__ int s_sum[kScanThreads];
-  const int chunk = (n + kScanThreads - 1) / kScanThreads;
-  const long lo_l = (long)threadIdx.x * chunk;
-  const int lo = (int)(lo_l < n ? lo_l : n), hi = (int)(lo_l + chunk < n ? lo_l + chunk : n);
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += count[i];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kScanThreads; d <<= 1) {  // inclusive scan of the chunk totals
-    const int add = threadIdx.x >= (unsigned)d ? s_sum[threadIdx.x - d] : 0;
-    __syncthreads();
-    s_sum[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int run = s_sum[threadIdx.x] - sum;
-  for (int i = lo; i < hi; ++i) {
-    const int c = count[i];
-    count[i] = run;
-    run += c;
-  }
-  if (threadIdx.x == kScanThreads - 1) *total = s_sum[kScanThreads - 1];
+  const int sum = block_exclusive_scan(n, count, [=](int i, int run) { count[i] = run; });
+  if (threadIdx.x == kScanThreads - 1) *total = sum;
 }
 
 __global__ void __launch_bounds__(kMetricBlock)

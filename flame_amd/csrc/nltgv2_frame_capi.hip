@@ -81,6 +81,60 @@ static float stage_ms(const SideStage& st) {
   return ms;
 }
 
+// The dense inverse-depth map a stage reads: the caller's device map, else the filtered map of mesh_outputs_begin, else the resident map
+// of interpolate_mesh -- either of the graph's own must have been made at rows x cols.
+static int resident_map(flame_nltgv2_ctx* ctx, const void* map_device, int use_filtered, int rows, int cols, const float** map) {
+  *map = (const float*)map_device;
+  if (map_device) return FLAME_NLTGV2_OK;
+  const bool f = use_filtered != 0;
+  if ((f ? ctx->fmap_rows : ctx->map_rows) != rows || (f ? ctx->fmap_cols : ctx->map_cols) != cols) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  *map = (const float*)(f ? ctx->m_img.p : ctx->r_img.p);
+  return *map ? FLAME_NLTGV2_OK : fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+}
+
+// What the view renderer and the fusion of views share: a camera, the three kinds of source, the projection's enqueue.
+static flame_hip::ViewCamera view_camera(const float* Kinv_src, const float* K_dst, const float* R, const float* t, float near_depth) {
+  flame_hip::ViewCamera cam;
+  std::memcpy(cam.Kinv_src, Kinv_src, sizeof(cam.Kinv_src));
+  std::memcpy(cam.K_dst, K_dst, sizeof(cam.K_dst));
+  std::memcpy(cam.R, R, sizeof(cam.R));
+  std::memcpy(cam.t, t, sizeof(cam.t));
+  cam.near_depth = near_depth;
+  return cam;
+}
+static flame_hip::FuseSource mesh_source(const void* pos, const void* values, float value_scale, const void* tris, const void* tri_valid) {
+  flame_hip::FuseSource o{};  // (the camera, and weight / v0 / t0 where there is a batch: the caller's)
+  o.pos = (const float2*)pos, o.values = (const float*)values, o.value_scale = value_scale;
+  o.tris = (const int32_t*)tris, o.tri_valid = (const uint8_t*)tri_valid;
+  return o;
+}
+// The graph's live mesh: the resident triangles over the canonical pos / x * graph_scale; validity 2: the filters' validity.
+static flame_hip::FuseSource live_source(const flame_nltgv2_ctx* ctx, int validity, float graph_scale) {
+  return mesh_source(ctx->c.pos, ctx->c.x, graph_scale, ctx->r_tris.p, validity == 2 ? ctx->m_tvalid.p : nullptr);
+}
+static flame_hip::FuseSource kept_source(const flame_nltgv2_ctx::KeptMesh& k) {
+  return mesh_source(k.pos.p, k.id.p, 1.0f, k.tris.p, k.has_valid ? k.valid.p : nullptr);  // (id * 1.0f == id: what the snapshot stored)
+}
+static flame_hip::FuseSource arrays_source(const flame_nltgv2_ctx* ctx) {  // what render_view_arrays puts into the view stage's own buffers
+  return mesh_source(ctx->v_apos.p, ctx->v_aid.p, 1.0f, ctx->v_atris.p, nullptr);
+}
+
+// Rules 1 - 5 of a stage on the side stream, from its ev0 on: vertices(), clear() and raster() launch the stage's kernels.  live: a
+// source is the graph's mesh, whose canonical pos / x the vertex kernel reads, and nothing after it.
+template <class Vertices, class Clear, class Raster>
+static int enqueue_projection(flame_nltgv2_ctx* ctx, SideStage& st, bool live, Vertices vertices, Clear clear, Raster raster) {
+  hipStream_t rs = ctx->raster_stream;
+  int rc = live ? mesh_state_on(ctx, rs) : FLAME_NLTGV2_OK;
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(st.ev0, rs));
+  LAUNCHCHK(ctx, vertices());
+  rc = live ? side_kernels_read_last(ctx) : FLAME_NLTGV2_OK;
+  if (rc) return rc;
+  LAUNCHCHK(ctx, clear());
+  LAUNCHCHK(ctx, raster());
+  return FLAME_NLTGV2_OK;
+}
+
 // The grey image a stage draws over.  A host image goes through pinned memory (`staging`, rows packed) into `d`, so the caller's buffer
 // is free again when this returns; a device image is read where it lies.
 static int stage_gray(flame_nltgv2_ctx* ctx, const uint8_t* img_host, const void* img_device, int step_bytes, int rows, int cols,
@@ -449,17 +503,8 @@ int flame_nltgv2_metric_outputs_begin(flame_nltgv2_ctx* ctx, const float* Kinv, 
   const bool want_pixels = w.depth || w.depth_mm || w.organized || w.cloud;
   if (!want_pixels && !w.mesh) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const float* map = nullptr;
-  if (want_pixels) {
-    if (params->map_device) {
-      map = (const float*)params->map_device;
-    } else if (params->use_filtered_map) {
-      if (ctx->fmap_rows != rows || ctx->fmap_cols != cols || !ctx->m_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-      map = (const float*)ctx->m_img.p;
-    } else {
-      if (ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-      map = (const float*)ctx->r_img.p;
-    }
-  }
+  rc = want_pixels ? resident_map(ctx, params->map_device, params->use_filtered_map, rows, cols, &map) : FLAME_NLTGV2_OK;
+  if (rc) return rc;
   if (w.mesh && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const int32_t V = w.mesh ? ctx->L.V : 0, T = w.mesh ? ctx->tris.T() : 0;
   const size_t n = (size_t)rows * (size_t)cols, f = sizeof(float);
@@ -626,15 +671,8 @@ int flame_nltgv2_map_error_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_map_e
   w.host_gray = !photo && w.image && p.gray_host != nullptr;
   if (!w.stats && !w.error_map && !w.image) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const float* map = nullptr;
-  if (p.map_device) {
-    map = (const float*)p.map_device;
-  } else if (p.use_filtered_map) {
-    if (ctx->fmap_rows != rows || ctx->fmap_cols != cols || !ctx->m_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-    map = (const float*)ctx->m_img.p;
-  } else {
-    if (ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-    map = (const float*)ctx->r_img.p;
-  }
+  rc = resident_map(ctx, p.map_device, p.use_filtered_map, rows, cols, &map);
+  if (rc) return rc;
   flame_hip::MapErrorPhoto ph{};
   bool ctx_images = false;
   if (photo) {
@@ -765,24 +803,14 @@ void flame_nltgv2_default_view_params(flame_nltgv2_view_params* p) {
   p->want_map = p->want_tri_index = p->copy_out = 1;
 }
 
-// The mesh a view-renderer call draws, on the device.  Of the graph: the resident triangles and the canonical pos / x; of the caller:
-// host arrays that go up into buffers of the stage.
-struct ViewMesh {
-  int32_t T = 0, V = 0;
-  bool own = false;                    // the _arrays form: the three host arrays
-  const int32_t* host_tris = nullptr;
-  const float* host_xy = nullptr;
-  const float* host_id = nullptr;
-  const uint8_t* host_valid = nullptr;    // validity == 1
-  const uint8_t* device_valid = nullptr;  // validity == 2
-  float value_scale = 1.0f;
-};
+// The three host arrays of the _arrays form, which go up into buffers of the stage.
+struct ViewMesh { const int32_t* host_tris; const float *host_xy, *host_id; };
 
 // What begin and the _arrays form share, behind their argument checks: open_stage, the stage's buffers, everything enqueued on the
-// side stream, close_stage.
-static int view_enqueue(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params& p, const ViewMesh& m, int rows, int cols) {
-  const bool own = m.own;
-  const int32_t T = m.T, V = m.V;
+// side stream, close_stage.  The mesh of V vertices and T triangles: own's arrays, or (own == NULL) the graph's live mesh at graph_scale
+// with p.validity 0 or 2; host_valid: the validity array of validity == 1.
+static int view_enqueue(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params& p, int32_t V, int32_t T, float graph_scale, const uint8_t* host_valid,
+                        const ViewMesh* own, int rows, int cols) {
   const size_t n = (size_t)rows * (size_t)cols;
   hipStream_t rs = ctx->raster_stream;
   flame_nltgv2_ctx::ViewPending vp;
@@ -794,54 +822,36 @@ static int view_enqueue(flame_nltgv2_ctx* ctx, const flame_nltgv2_view_params& p
   rc = ensure(ctx, ctx->v_vtx, sizeof(flame_hip::ViewVertex) * (size_t)V + 16);
   if (!rc) rc = ensure(ctx, ctx->v_keys, sizeof(unsigned long long) * n);
   if (!rc) rc = ensure(ctx, ctx->v_counts, sizeof(flame_hip::ViewCounts));
-  if (!rc) rc = ensure(ctx, ctx->v_big, sizeof(int) * ((size_t)T + 1));
+  if (!rc) rc = ensure(ctx, ctx->v_big, sizeof(int) * (2 * (size_t)T + 2));
   if (!rc && vp.want.map) rc = ensure(ctx, ctx->v_map, sizeof(float) * n);
   if (!rc && vp.want.tri_index) rc = ensure(ctx, ctx->v_tri, sizeof(int32_t) * n);
-  if (!rc && m.host_valid) rc = ensure(ctx, ctx->v_tvalid, (size_t)T + 16);
-  if (!rc && own) {
-    rc = ensure(ctx, ctx->v_atris, sizeof(int32_t) * 3 * (size_t)T + 16);
-    if (!rc) rc = ensure(ctx, ctx->v_apos, sizeof(float) * 2 * (size_t)V + 16);
-    if (!rc) rc = ensure(ctx, ctx->v_aid, sizeof(float) * (size_t)V + 16);
-  }
+  if (!rc && host_valid) rc = ensure(ctx, ctx->v_tvalid, (size_t)T + 16);
+  if (!rc && own) rc = ensure(ctx, ctx->v_atris, sizeof(int32_t) * 3 * (size_t)T + 16);
+  if (!rc && own) rc = ensure(ctx, ctx->v_apos, sizeof(float) * 2 * (size_t)V + 16);
+  if (!rc && own) rc = ensure(ctx, ctx->v_aid, sizeof(float) * (size_t)V + 16);
   if (rc) return rc;
   ctx->view.active = false;  // (from here on the pinned outputs are being rewritten)
+  flame_hip::FuseSource src = own ? arrays_source(ctx) : live_source(ctx, p.validity, graph_scale);
+  src.cam = view_camera(p.Kinv_src, p.K_dst, p.R, p.t, p.near_depth);
   // (pageable memory: each copy holds the host until the bytes have left the caller's array)
-  const uint8_t* d_tv = m.device_valid;
-  if (m.host_valid && T > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->v_tvalid.p, m.host_valid, (size_t)T, hipMemcpyHostToDevice, rs));
-    d_tv = (const uint8_t*)ctx->v_tvalid.p;
+  if (host_valid && T > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->v_tvalid.p, host_valid, (size_t)T, hipMemcpyHostToDevice, rs));
+    src.tri_valid = (const uint8_t*)ctx->v_tvalid.p;
   }
-  const int32_t* d_tris = (const int32_t*)ctx->r_tris.p;
-  const float2* d_pos = ctx->c.pos;
-  const float* d_val = ctx->c.x;
-  if (own) {
-    if (T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->v_atris.p, m.host_tris, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
-    if (V > 0) {
-      HIPCHK(ctx, hipMemcpyAsync(ctx->v_apos.p, m.host_xy, sizeof(float) * 2 * (size_t)V, hipMemcpyHostToDevice, rs));
-      HIPCHK(ctx, hipMemcpyAsync(ctx->v_aid.p, m.host_id, sizeof(float) * (size_t)V, hipMemcpyHostToDevice, rs));
-    }
-    d_tris = (const int32_t*)ctx->v_atris.p, d_pos = (const float2*)ctx->v_apos.p, d_val = (const float*)ctx->v_aid.p;
-  } else {
-    rc = mesh_state_on(ctx, rs);
-    if (rc) return rc;
+  if (own && T > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->v_atris.p, own->host_tris, sizeof(int32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, rs));
+  if (own && V > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->v_apos.p, own->host_xy, sizeof(float) * 2 * (size_t)V, hipMemcpyHostToDevice, rs));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->v_aid.p, own->host_id, sizeof(float) * (size_t)V, hipMemcpyHostToDevice, rs));
   }
-  flame_hip::ViewCamera cam;
-  std::memcpy(cam.Kinv_src, p.Kinv_src, sizeof(cam.Kinv_src));
-  std::memcpy(cam.K_dst, p.K_dst, sizeof(cam.K_dst));
-  std::memcpy(cam.R, p.R, sizeof(cam.R));
-  std::memcpy(cam.t, p.t, sizeof(cam.t));
-  cam.near_depth = p.near_depth;
   flame_hip::ViewVertex* vtx = (flame_hip::ViewVertex*)ctx->v_vtx.p;
   unsigned long long* keys = (unsigned long long*)ctx->v_keys.p;
   flame_hip::ViewCounts* counts = (flame_hip::ViewCounts*)ctx->v_counts.p;
-  HIPCHK(ctx, hipEventRecord(ctx->view.ev0, rs));
-  LAUNCHCHK(ctx, flame_hip::launch_view_vertices(V, d_pos, d_val, m.value_scale, cam, vtx, rs));
-  if (!own) {  // the vertex kernel is the last reader of the canonical pos / x
-    rc = side_kernels_read_last(ctx);
-    if (rc) return rc;
-  }
-  LAUNCHCHK(ctx, flame_hip::launch_view_clear((long)n, keys, counts, (int*)ctx->v_big.p, rs));
-  LAUNCHCHK(ctx, flame_hip::launch_view_raster(T, d_tris, d_tv, vtx, keys, counts, (int*)ctx->v_big.p, rows, cols, rs));
+  int* big = (int*)ctx->v_big.p;
+  rc = enqueue_projection(ctx, ctx->view, !own,
+                          [&] { return flame_hip::launch_view_vertices(src, V, vtx, rs); },
+                          [&] { return flame_hip::launch_view_clear((long)n, keys, counts, big, rs); },
+                          [&] { return flame_hip::launch_view_raster(src, T, vtx, keys, counts, big, rows, cols, rs); });
+  if (rc) return rc;
   LAUNCHCHK(ctx, flame_hip::launch_view_resolve((long)n, keys, vp.want.map ? (float*)ctx->v_map.p : nullptr,
                                                 vp.want.tri_index ? (int32_t*)ctx->v_tri.p : nullptr, counts, rs));
   char* h = ctx->view.h.p;
@@ -867,12 +877,7 @@ int flame_nltgv2_render_view_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_vie
   if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (params->validity < 0 || params->validity > 2 || (tri_valid != nullptr) != (params->validity == 1)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (params->validity == 2 && !ctx->tris.validity_current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-  ViewMesh m;
-  m.T = ctx->tris.T(), m.V = ctx->L.V;
-  m.host_valid = tri_valid;
-  if (params->validity == 2) m.device_valid = (const uint8_t*)ctx->m_tvalid.p;
-  m.value_scale = graph_scale;
-  return view_enqueue(ctx, *params, m, rows, cols);
+  return view_enqueue(ctx, *params, ctx->L.V, ctx->tris.T(), graph_scale, tri_valid, nullptr, rows, cols);
 }
 
 int flame_nltgv2_render_view_end(flame_nltgv2_ctx* ctx, flame_nltgv2_view_outputs_view* out) {
@@ -929,11 +934,8 @@ int flame_nltgv2_render_view_arrays(flame_nltgv2_ctx* ctx, const flame_nltgv2_vi
   if (!triangles_in_range(triangles, T, V)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   flame_nltgv2_view_params p = *params;
   p.want_map = map_out != nullptr, p.want_tri_index = tri_index_out != nullptr, p.copy_out = 1;
-  ViewMesh m;
-  m.T = T, m.V = V, m.own = true;
-  m.host_tris = triangles, m.host_xy = vertices_xy, m.host_id = idepths;
-  m.host_valid = tri_valid;
-  rc = view_enqueue(ctx, p, m, rows, cols);
+  const ViewMesh own{triangles, vertices_xy, idepths};
+  rc = view_enqueue(ctx, p, V, T, 1.0f, tri_valid, &own, rows, cols);
   if (rc) return rc;
   return view_finish(ctx, map_out, tri_index_out, counts_out);
 }
@@ -1086,27 +1088,11 @@ int flame_nltgv2_fuse_views_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse
   for (int s = 0; s < N; ++s) {
     const flame_nltgv2_fuse_source& src = p.sources[s];
     flame_hip::FuseSource& o = tab.s[s];
-    std::memcpy(o.cam.Kinv_src, src.Kinv_src, sizeof(o.cam.Kinv_src));
-    std::memcpy(o.cam.K_dst, p.K_dst, sizeof(o.cam.K_dst));
-    std::memcpy(o.cam.R, src.R, sizeof(o.cam.R));
-    std::memcpy(o.cam.t, src.t, sizeof(o.cam.t));
-    o.cam.near_depth = p.near_depth;
+    o = s == live ? live_source(ctx, src.validity, src.graph_scale) : kept_source(ctx->kept[src.slot]);
+    o.cam = view_camera(src.Kinv_src, p.K_dst, src.R, src.t, p.near_depth);
     o.weight = src.weight;
-    int32_t V, T;
-    if (s == live) {
-      V = ctx->L.V, T = ctx->tris.T();
-      o.pos = ctx->c.pos, o.values = ctx->c.x, o.tris = (const int32_t*)ctx->r_tris.p;
-      o.tri_valid = src.validity == 2 ? (const uint8_t*)ctx->m_tvalid.p : nullptr;
-      o.value_scale = src.graph_scale;
-    } else {
-      const flame_nltgv2_ctx::KeptMesh& k = ctx->kept[src.slot];
-      V = k.V, T = k.T;
-      o.pos = (const float2*)k.pos.p, o.values = (const float*)k.id.p, o.tris = (const int32_t*)k.tris.p;
-      o.tri_valid = k.has_valid ? (const uint8_t*)k.valid.p : nullptr;
-      o.value_scale = 1.0f;  // (id * 1.0f == id: what the snapshot stored)
-    }
     o.v0 = (int32_t)v_sum, o.t0 = (int32_t)t_sum;
-    v_sum += V, t_sum += T;
+    v_sum += s == live ? ctx->L.V : ctx->kept[src.slot].V, t_sum += s == live ? ctx->tris.T() : ctx->kept[src.slot].T;
     if (v_sum > INT32_MAX / 4 || t_sum > INT32_MAX / 4) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);  // (3 t and 2 + 2 t stay ints)
   }
   tab.v_end = (int32_t)v_sum, tab.t_end = (int32_t)t_sum;
@@ -1131,22 +1117,15 @@ int flame_nltgv2_fuse_views_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse
   if (!rc && fp.want.layers) rc = ensure(ctx, ctx->f_layers, sizeof(float) * n * (size_t)N);
   if (rc) return rc;
   ctx->fuse.active = false;  // (from here on the pinned outputs are being rewritten)
-  if (live >= 0) {
-    rc = mesh_state_on(ctx, rs);
-    if (rc) return rc;
-  }
   flame_hip::ViewVertex* vtx = (flame_hip::ViewVertex*)ctx->f_vtx.p;
   unsigned long long* keys = (unsigned long long*)ctx->f_keys.p;
   flame_hip::FuseCounts* counts = (flame_hip::FuseCounts*)ctx->f_counts.p;
   int* big = (int*)ctx->f_big.p;
-  HIPCHK(ctx, hipEventRecord(ctx->fuse.ev0, rs));
-  LAUNCHCHK(ctx, flame_hip::launch_fuse_vertices(tab, vtx, rs));
-  if (live >= 0) {  // the vertex kernel is the last reader of the canonical pos / x
-    rc = side_kernels_read_last(ctx);
-    if (rc) return rc;
-  }
-  LAUNCHCHK(ctx, flame_hip::launch_fuse_clear((long)(n * (size_t)N), keys, counts, big, rs));
-  LAUNCHCHK(ctx, flame_hip::launch_fuse_raster(tab, vtx, keys, counts, big, rows, cols, rs));
+  rc = enqueue_projection(ctx, ctx->fuse, live >= 0,
+                          [&] { return flame_hip::launch_fuse_vertices(tab, vtx, rs); },
+                          [&] { return flame_hip::launch_fuse_clear((long)(n * (size_t)N), keys, counts, big, rs); },
+                          [&] { return flame_hip::launch_fuse_raster(tab, vtx, keys, counts, big, rows, cols, rs); });
+  if (rc) return rc;
   flame_hip::FuseOutputs out;
   out.fused = fp.want.fused ? (float*)ctx->f_fused.p : nullptr;
   out.present_mask = fp.want.masks ? (uint8_t*)ctx->f_pmask.p : nullptr;
@@ -1369,18 +1348,9 @@ int flame_nltgv2_volume_integrate_begin(flame_nltgv2_ctx* ctx, const float* K, c
   if (!K || !T_cam_world || !params || rows <= 0 || cols <= 0 || (uint64_t)rows * (uint64_t)cols >= (1ull << 31)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (!finite_positive(params->weight)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const float* map = nullptr;
-  if (params->map_device) {
-    map = (const float*)params->map_device;
-  } else {
-    if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
-    if (params->use_filtered_map) {
-      if (ctx->fmap_rows != rows || ctx->fmap_cols != cols || !ctx->m_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-      map = (const float*)ctx->m_img.p;
-    } else {
-      if (ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
-      map = (const float*)ctx->r_img.p;
-    }
-  }
+  if (!params->map_device && !ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
+  rc = resident_map(ctx, params->map_device, params->use_filtered_map, rows, cols, &map);
+  if (rc) return rc;
   hipStream_t rs = ctx->raster_stream;
   flame_nltgv2_ctx::IntegratePending ip;
   ip.rows = rows, ip.cols = cols;
@@ -1513,7 +1483,10 @@ int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_ho
   int rc = enter(ctx);
   if (rc) return rc;
   if (!ctx->have_graph) return fail(ctx, FLAME_NLTGV2_ERR_NO_GRAPH);
-  if (rows <= 0 || cols <= 0 || ctx->map_rows != rows || ctx->map_cols != cols || !ctx->r_img.p) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (rows <= 0 || cols <= 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const float* map = nullptr;
+  rc = resident_map(ctx, nullptr, 0, rows, cols, &map);
+  if (rc) return rc;
   if (!ctx->tris.current(ctx->topo)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if ((img_host != nullptr) == (img_device != nullptr) || step_bytes < cols || !K || !params) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   const int32_t T = ctx->tris.T();
@@ -1564,7 +1537,7 @@ int flame_nltgv2_debug_images_begin(flame_nltgv2_ctx* ctx, const uint8_t* img_ho
     rc = side_kernels_read_last(ctx);  // (of the canonical pos / w1 / w2)
     if (rc) return rc;
   }
-  LAUNCHCHK(ctx, flame_hip::launch_debug_images(a, (const float*)ctx->r_img.p, (const float*)ctx->d_w1map.p, (const float*)ctx->d_w2map.p,
+  LAUNCHCHK(ctx, flame_hip::launch_debug_images(a, map, (const float*)ctx->d_w1map.p, (const float*)ctx->d_w2map.p,
                                                 want_id ? (uint8_t*)ctx->d_idimg.p : nullptr, want_n ? (uint8_t*)ctx->d_nimg.p : nullptr, rs));
   if (want_id) HIPCHK(ctx, hipMemcpyAsync(h + dp.at.idimg, ctx->d_idimg.p, 3 * n, hipMemcpyDeviceToHost, rs));
   if (want_n) {

@@ -30,15 +30,26 @@ struct ViewCamera {
   float near_depth;
 };
 
-// keys[0 .. n) = 0, *counts = 0 and big[0] = 0.  big: [1 + T] ints of scratch, the list of the triangles with large boxes.
+// A mesh on the device and its camera into the target: the view renderer draws one, the fusion (fuse_kernels.h) a table of them, where
+// weight is the vote's and v0, t0 the prefix sums of V and T over the sources before this one.  The view renderer leaves the three 0.
+struct FuseSource {
+  ViewCamera cam;
+  const float2* pos;
+  const float* values;       // the inverse depth of vertex v: values[v] * value_scale
+  const int32_t* tris;
+  const uint8_t* tri_valid;  // NULL: every triangle is valid
+  float value_scale, weight;
+  int32_t v0, t0;
+};
+
+// keys[0 .. n) = 0, *counts = 0 and big[0] = 0.  big: [2 + 2 * T] ints of scratch, the list of the triangles with large boxes.
 int launch_view_clear(long n, unsigned long long* keys, ViewCounts* counts, int* big, hipStream_t s);
-// out[v] for the V vertices pos[v] with inverse depth values[v] * value_scale: one lane per vertex.  The only reader of pos / values.
-int launch_view_vertices(int V, const float2* pos, const float* values, float value_scale, const ViewCamera& cam, ViewVertex* out, hipStream_t s);
-// Rule 2 per triangle into counts (one atomic per workgroup and counter), then rules 3 - 5 into keys: one wavefront per triangle over
-// its pixel bounding box clipped to rows x cols, kViewBigWaves of them where the box holds more than kViewWavePixels pixels (big, as
-// launch_view_clear left it).  tri_valid: NULL = every triangle is valid.
-int launch_view_raster(int T, const int32_t* tris, const uint8_t* tri_valid, const ViewVertex* vtx, unsigned long long* keys, ViewCounts* counts,
-                       int* big, int rows, int cols, hipStream_t s);
+// out[v] for the V vertices of the mesh: one lane per vertex.  The only reader of pos / values.
+int launch_view_vertices(const FuseSource& mesh, int V, ViewVertex* out, hipStream_t s);
+// Rule 2 per triangle of the mesh into counts (one atomic per workgroup and counter), then rules 3 - 5 into keys of rows x cols: one
+// wavefront per triangle, kViewBigWaves of them where its clipped box holds more than kViewWavePixels pixels (big: as launch_view_clear left it).
+int launch_view_raster(const FuseSource& mesh, int T, const ViewVertex* vtx, unsigned long long* keys, ViewCounts* counts, int* big, int rows,
+                       int cols, hipStream_t s);
 // Rule 6: map / tri_index (each may be NULL) from keys, the coverage into counts with one atomic per workgroup.
 int launch_view_resolve(long n, const unsigned long long* keys, float* map, int32_t* tri_index, ViewCounts* counts, hipStream_t s);
 

@@ -10,95 +10,48 @@
 //               coefficients: w = e0 + row * dy + col * dx in int64 is the rule's value exactly (|X|, |Y| <= 2^20: |w| < 2^44).  The
 //               nearest surface wins through a 64-bit atomicMax on {bits(val), t + 1}: val > 0, so its bits order as the floats do
 //   resolve     keys -> map, owner index, coverage (one atomic per workgroup: the lesson of k_raster_resolve)
-// The device functions of rules 1 - 5 are in view_device.hpp, shared with fuse_kernels.hip.
+// clear, vertices and the three triangle kernels are thin instances of the bodies in view_project.hpp, which fuse_kernels.hip
+// instantiates too: this file draws ONE source (view_project::OneSource -- no table is searched, the listed boxes are (0, triangle)
+// pairs) and publishes all three counted classes of rule 2.  The resolve is this file's own.  Rules 1 - 5: view_device.hpp.
 // No floating-point atomics: the key image does not depend on scheduling.  Built with -ffp-contract=off (no FMA); division and the
 // int64 -> float conversions are correctly rounded.
 #include <hip/hip_runtime.h>
 
-#include "view_device.hpp"
 #include "view_kernels.h"
+#include "view_project.hpp"
 
 namespace flame_hip {
 namespace {
 
-using namespace view_device;  // rules 1 - 5, shared with fuse_kernels.hip
-
-constexpr int kPerThread = kViewResolveTile / 256;
+using namespace view_project;  // the five bodies, shared with fuse_kernels.hip; OneSource: this file's model of the sources
 
 __global__ void __launch_bounds__(256)
 k_view_clear(long n, unsigned long long* __restrict__ keys, ViewCounts* __restrict__ counts, int* __restrict__ big) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *counts = ViewCounts{0, 0, 0, 0}, big[0] = 0;
-  const long base = (long)blockIdx.x * kViewResolveTile + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < kPerThread; ++j) {
-    const long i = base + (long)j * 256;
-    if (i < n) keys[i] = 0ull;
-  }
+  clear_tile(n, keys);
 }
 
 __global__ void __launch_bounds__(256)
-k_view_vertices(int V, const float2* __restrict__ pos, const float* __restrict__ values, float value_scale, ViewCamera cam,
-                ViewVertex* __restrict__ out) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  out[v] = view_vertex(pos[v], values[v] * value_scale, cam);
-}
+k_view_vertices(OneSource m, ViewVertex* __restrict__ out) { project_vertices(m, out); }
 
-// One lane per triangle: what rule 2 makes of it, counted with one atomic per workgroup and counter; a drawn triangle whose box holds
-// more than kViewWavePixels pixels goes on the list big[1 ..], big[0] counting them (few: a triangle stretched across a depth edge).
 __global__ void __launch_bounds__(256)
-k_view_count(int T, const int32_t* __restrict__ tris, const uint8_t* __restrict__ tri_valid, const ViewVertex* __restrict__ vtx,
-             ViewCounts* __restrict__ counts, int* __restrict__ big, int rows, int cols) {
-  __shared__ int s_n[4];
-  if (threadIdx.x < 4) s_n[threadIdx.x] = 0;
-  __syncthreads();
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  int cls = kInvalid;
-  if (t < T) {
-    long long A = 0;
-    const ViewVertex a = vtx[tris[3 * t]], b = vtx[tris[3 * t + 1]], c = vtx[tris[3 * t + 2]];
-    cls = classify(t, tri_valid, a, b, c, &A);
-    if (cls == kDraw && bounding_box(a, b, c, rows, cols).n > (unsigned)kViewWavePixels) big[1 + atomicAdd(&big[0], 1)] = t;
-  }
-  for (int k = kDraw; k <= kCulledFacing; ++k) {
-    if (k == kInvalid) continue;
-    const int n = __popcll(__ballot(cls == k));
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&s_n[k], n);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_n[kDraw]) atomicAdd(&counts->tris_drawn, s_n[kDraw]);
-    if (s_n[kCulledVertex]) atomicAdd(&counts->tris_culled_vertex, s_n[kCulledVertex]);
-    if (s_n[kCulledFacing]) atomicAdd(&counts->tris_culled_facing, s_n[kCulledFacing]);
-  }
+k_view_count(OneSource m, const ViewVertex* __restrict__ vtx, ViewCounts* __restrict__ counts, int* __restrict__ big, int rows, int cols) {
+  count_triangles(m, vtx, big, rows, cols, [=](const int* n) {
+    if (n[kDraw]) atomicAdd(&counts->tris_drawn, n[kDraw]);
+    if (n[kCulledVertex]) atomicAdd(&counts->tris_culled_vertex, n[kCulledVertex]);
+    if (n[kCulledFacing]) atomicAdd(&counts->tris_culled_facing, n[kCulledFacing]);
+  });
 }
 
-// One wavefront per triangle whose box holds at most kViewWavePixels pixels: the others are k_view_raster_big's.
 __global__ void __launch_bounds__(64)
-k_view_raster(int T, const int32_t* __restrict__ tris, const uint8_t* __restrict__ tri_valid, const ViewVertex* __restrict__ vtx,
-              unsigned long long* __restrict__ keys, int rows, int cols) {
-  const int t = blockIdx.x;
-  if (t >= T) return;
-  const ViewVertex a = vtx[tris[3 * t]], b = vtx[tris[3 * t + 1]], c = vtx[tris[3 * t + 2]];
-  long long A = 0;
-  if (classify(t, tri_valid, a, b, c, &A) != kDraw) return;
-  const ViewBox box = bounding_box(a, b, c, rows, cols);
-  if (box.n > (unsigned)kViewWavePixels) return;
-  raster_pixels(t, A, a, b, c, box, threadIdx.x, 64u, keys, cols);
+k_view_raster(OneSource m, const ViewVertex* __restrict__ vtx, unsigned long long* __restrict__ keys, int rows, int cols) {
+  raster_triangle(m, vtx, keys, rows, cols);
 }
 
-// The listed triangles: kViewBigWaves wavefronts share one triangle's box (blockIdx.x: which of them), blockIdx.y walks the list.
 __global__ void __launch_bounds__(64)
-k_view_raster_big(const int32_t* __restrict__ tris, const ViewVertex* __restrict__ vtx, const int* __restrict__ big,
-                  unsigned long long* __restrict__ keys, int rows, int cols) {
-  const int n_big = big[0];
-  for (int item = blockIdx.y; item < n_big; item += gridDim.y) {
-    const int t = big[1 + item];
-    const ViewVertex a = vtx[tris[3 * t]], b = vtx[tris[3 * t + 1]], c = vtx[tris[3 * t + 2]];
-    long long A = 0;
-    (void)classify(t, nullptr, a, b, c, &A);  // (listed: drawn)
-    raster_pixels(t, A, a, b, c, bounding_box(a, b, c, rows, cols), blockIdx.x * 64u + threadIdx.x, 64u * kViewBigWaves, keys, cols);
-  }
+k_view_raster_big(OneSource m, const ViewVertex* __restrict__ vtx, const int* __restrict__ big, unsigned long long* __restrict__ keys, int rows,
+                  int cols) {
+  raster_listed(m, vtx, big, keys, rows, cols);
 }
 
 __global__ void __launch_bounds__(256)
@@ -127,8 +80,6 @@ k_view_resolve(long n, const unsigned long long* __restrict__ keys, float* __res
   if (threadIdx.x == 0 && s_count) atomicAdd(&counts->coverage, s_count);
 }
 
-inline dim3 tiles(long n) { return dim3((unsigned)((n + kViewResolveTile - 1) / kViewResolveTile)); }
-
 }  // namespace
 
 int launch_view_clear(long n, unsigned long long* keys, ViewCounts* counts, int* big, hipStream_t s) {
@@ -136,18 +87,19 @@ int launch_view_clear(long n, unsigned long long* keys, ViewCounts* counts, int*
   return (int)hipGetLastError();
 }
 
-int launch_view_vertices(int V, const float2* pos, const float* values, float value_scale, const ViewCamera& cam, ViewVertex* out, hipStream_t s) {
+int launch_view_vertices(const FuseSource& mesh, int V, ViewVertex* out, hipStream_t s) {
   if (V <= 0) return 0;
-  hipLaunchKernelGGL(k_view_vertices, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s, V, pos, values, value_scale, cam, out);
+  hipLaunchKernelGGL(k_view_vertices, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s, OneSource{mesh, V, 0}, out);
   return (int)hipGetLastError();
 }
 
-int launch_view_raster(int T, const int32_t* tris, const uint8_t* tri_valid, const ViewVertex* vtx, unsigned long long* keys, ViewCounts* counts,
-                       int* big, int rows, int cols, hipStream_t s) {
+int launch_view_raster(const FuseSource& mesh, int T, const ViewVertex* vtx, unsigned long long* keys, ViewCounts* counts, int* big, int rows,
+                       int cols, hipStream_t s) {
   if (T <= 0) return 0;
-  hipLaunchKernelGGL(k_view_count, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, T, tris, tri_valid, vtx, counts, big, rows, cols);
-  hipLaunchKernelGGL(k_view_raster, dim3((unsigned)T), dim3(64), 0, s, T, tris, tri_valid, vtx, keys, rows, cols);
-  hipLaunchKernelGGL(k_view_raster_big, dim3(kViewBigWaves, kViewBigRows), dim3(64), 0, s, tris, vtx, big, keys, rows, cols);
+  const OneSource m{mesh, 0, T};
+  hipLaunchKernelGGL(k_view_count, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, m, vtx, counts, big, rows, cols);
+  hipLaunchKernelGGL(k_view_raster, dim3((unsigned)T), dim3(64), 0, s, m, vtx, keys, rows, cols);
+  hipLaunchKernelGGL(k_view_raster_big, dim3(kViewBigWaves, kViewBigRows), dim3(64), 0, s, m, vtx, big, keys, rows, cols);
   return (int)hipGetLastError();
 }
 

@@ -299,6 +299,43 @@ def test_gpu_more_large_boxes_than_list_rows_over_three_sources(gpu, reg):
     assert len(np.unique(vr.bits(got["layers"][0]))) > 1000 and 0 < want["coverage"]
 
 
+# ---- the two stages are one projection -----------------------------------------------------------------------------------------------------
+def one_projection_cases():
+    grid = tg.mesh_case(14, step=3, rows=30, cols=40, R=tg.cases.rotation_y(-5.0), t=np.array([0.3, 0.1, 0], F))
+    large = dict(tris=np.array([[0, 1, 2]], np.int32), pos=np.array([[-100, -100], [300, -100], [-100, 300]], F), idepth=np.array([0.4, 1.1, 2.3], F),
+                 Kinv_src=KINV, K_dst=K, t=np.array([0.05, 0, 0], F), rows=60, cols=80)
+    return {"630_triangles_30x40": grid, "one_large_box_60x80": large, "no_triangles": dict(grid, tris=np.zeros((0, 3), np.int32))}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(one_projection_cases()))
+def test_gpu_render_view_is_the_fusion_of_one_live_source(gpu, reg, name):
+    """render_view and fuse_views with one live source run the same projection (view_project.hpp): one camera, validity 0 and 2 --
+    the map is layer 0 bit for bit, and coverage and tris_drawn are the same numbers."""
+    c = one_projection_cases()[name]
+    rows, cols, T = c["rows"], c["cols"], len(c["tris"])
+    tg.make_resident(reg, c["pos"], c["idepth"], c["tris"])
+    mo = reg.mesh_outputs(None, KINV, *SRC, filter=gpu.MeshFilterParams(do_oblique_triangle_filter=False, do_edge_length_filter=False, min_triangle_idepth=0.6))
+    n_valid = int(np.asarray(mo["tri_valid"], np.uint8).sum())
+    drawn = {}
+    for validity in (0, 2):
+        view = reg.render_view(tg.view_params(gpu, c, validity=validity), rows, cols)
+        p = gpu.FuseParams(sources=[fuse_source(gpu, -1, c, validity=validity)], K_dst=c["K_dst"], near_depth=c.get("near_depth", 0.0), want_layers=True)
+        fused = reg.fuse_views(p, rows, cols)
+        print("%s, validity %d: coverage %d / %d, tris_drawn %d / %d" % (name, validity, view["coverage"], fused["coverage"], view["tris_drawn"], fused["tris_drawn"]))
+        assert view["map"].shape == fused["layers"][0].shape == (rows, cols)
+        assert vr.bits(view["map"]).tobytes() == vr.bits(fused["layers"][0]).tobytes(), validity
+        assert np.uint32(view["coverage"]) == np.uint32(fused["coverage"]) and np.uint32(view["tris_drawn"]) == np.uint32(fused["tris_drawn"]), validity
+        drawn[validity] = view["tris_drawn"]
+    # nothing passes by being empty, and each mesh takes the path it is here for
+    if name == "630_triangles_30x40":
+        assert T >= 600 and 0 < n_valid < T and 0 < drawn[2] < drawn[0] and view["coverage"] > 0
+    elif name == "one_large_box_60x80":
+        assert rows * cols > 2048 and view["coverage"] == rows * cols and drawn == {0: 1, 2: 1}  # (the one box is the whole target: listed)
+    else:
+        assert T == 0 and drawn == {0: 0, 2: 0} and (vr.bits(view["map"]) == vr.HOLE).all()
+
+
 # ---- repeats, transfers, errors ----------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_gpu_two_calls_give_the_same_bytes_and_outputs_may_stay_on_the_device(gpu, reg):
