@@ -27,6 +27,8 @@ from .regularizer import (  # noqa: F401
     Regularizer,
     ViewCounts,
     ViewParams,
+    VolumeMeshCounts,
+    VolumeMeshParams,
     VolumeParams,
     WireframeParams,
     delaunay,

@@ -416,6 +416,17 @@ struct flame_nltgv2_ctx {
     bool copy_out = false;
     VolumeLayout at{};
   } vray_pending;
+  // flame_nltgv2_volume_mesh_* (volume_mesh_kernels.hip): the passes' scratch (6 bytes per voxel of the box, 8 per workgroup), the cube
+  // counters and the scan's totals, and the mesh, which stays in z_verts / z_norms / z_tris until the next call.  Pinned:
+  // volume_mesh_layout; z_pass: the events between the four passes.
+  DevBuf z_cls, z_emask, z_vloc, z_tloc, z_bv, z_bt, z_counts, z_totals, z_verts, z_norms, z_tris;
+  SideStage vmesh;
+  hipEvent_t z_pass[3] = {nullptr, nullptr, nullptr};
+  struct VolumeMeshPending {
+    bool want_normals = false, copy_out = false, fetched = false;
+    int32_t v_room = 0, t_room = 0;  // the capacities the emit pass compared the counts with
+    VolumeMeshLayout at{};
+  } vmesh_pending;
   hipStream_t topo_stream = nullptr;  // the side stream of a prepared sync
   hipEvent_t ev_topo_ready = nullptr; // recorded on the context's stream when a topology stands (upload, commit): the next builder waits for it
   struct PreparedSync {

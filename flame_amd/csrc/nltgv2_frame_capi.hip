@@ -9,9 +9,10 @@
 //   the kept meshes           keep_mesh, keep_mesh_arrays, drop_mesh, kept_mesh_info, get_kept_mesh: what a pose-frame keeps of its mesh
 //   the fusion of views       fuse_views_begin / _end: up to eight kept or live meshes in one camera, a vote per pixel
 //   the volumetric map        volume_create / _reset / _destroy / _info / _download / _upload; volume_integrate_begin / _end: a depth map folded
-//                             into the truncated-signed-distance volume; volume_raycast_begin / _end: the volume seen from a camera
+//                             into the truncated-signed-distance volume; volume_raycast_begin / _end: the volume seen from a camera;
+//                             volume_mesh_begin / _end: its surface as a triangle mesh with normals
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
-// The ten begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
+// The eleven begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
 // they are; open_stage; the stage's device buffers; its work between ev0 and ev1 with side_kernels_read_last behind the last reader of
 // the canonical arrays; the copies out; close_stage.  What is a function of sizes and of the calls so far (the pinned layouts, the
@@ -27,6 +28,7 @@
 #include "nltgv2_context.hpp"
 #include "view_kernels.h"
 #include "volume_kernels.h"
+#include "volume_mesh_kernels.h"
 #include "wireframe_kernels.h"
 
 // Which state a mesh stage on the side stream describes (interpolate_mesh_begin, mesh_outputs_begin), and the wait that lets `rs` read
@@ -167,6 +169,9 @@ static_assert(sizeof(flame_hip::RaycastCounts) == sizeof(flame_nltgv2_raycast_co
               "the counters on the device, in the header and in raycast_layout are one struct");
 static_assert(flame_hip::kVolumeCountsBytes == kCountSetsBytes && flame_hip::kVolumeCountSlots == kCountSets &&
               flame_hip::kVolumeCountSlotWords == kCountSetWords, "the kernels' and the layouts' partial sets of counters");
+static_assert(sizeof(flame_nltgv2_volume_mesh_counts) == kMeshCountBytes && sizeof(flame_hip::MeshTotals) == kMeshTotalsBytes,
+              "the counters in the header and the scan's totals on the device and in volume_mesh_layout");
+static_assert(flame_hip::kMeshPasses == 4 && sizeof(((flame_nltgv2_volume_mesh_view*)nullptr)->pass_ms) == 4 * sizeof(float), "one time per pass");
 static_assert(flame_hip::kFuseSources == FLAME_NLTGV2_FUSE_SOURCES, "the kernels' and the header's number of sources");
 
 extern "C" {
@@ -1465,6 +1470,123 @@ int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const 
   if (rc) return rc;
   if (map_out) std::memcpy(map_out, v.map, sizeof(float) * (size_t)v.rows * (size_t)v.cols);
   if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
+}
+
+void flame_nltgv2_default_volume_mesh_params(flame_nltgv2_volume_mesh_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->want_normals = p->copy_out = 1;
+}
+
+// The surface extraction on the side stream: it reads the volume alone.  The counts are known only on the device when the emit pass
+// runs, so the arrays have room for the caller's capacities (capped by what the box can give) and _end fetches what was written.
+int flame_nltgv2_volume_mesh_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_mesh_params* params) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_mesh_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume || !params) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  if (params->max_vertices < 0 || params->max_triangles < 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t dims[3] = {ctx->vol_params.nx, ctx->vol_params.ny, ctx->vol_params.nz};
+  flame_hip::MeshBox box;
+  const uint64_t n_box = mesh_box_voxels(dims, params->lo, params->hi, box.lo, box.n);
+  if (n_box == 0) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const size_t v_room = (size_t)mesh_vertex_room(n_box, params->max_vertices), t_room = (size_t)mesh_triangle_room(n_box, params->max_triangles);
+  const size_t blocks = (size_t)flame_hip::mesh_blocks((long)n_box);
+  hipStream_t rs = ctx->raster_stream;
+  flame_nltgv2_ctx::VolumeMeshPending mp;
+  mp.want_normals = params->want_normals != 0, mp.copy_out = params->copy_out != 0;
+  mp.v_room = (int32_t)v_room, mp.t_room = (int32_t)t_room;
+  mp.at = volume_mesh_layout((int64_t)v_room, (int64_t)t_room, mp.want_normals, mp.copy_out);
+  rc = open_stage(ctx, ctx->vmesh, mp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->z_cls, n_box);
+  if (!rc) rc = ensure(ctx, ctx->z_emask, n_box);
+  if (!rc) rc = ensure(ctx, ctx->z_vloc, sizeof(uint16_t) * n_box);
+  if (!rc) rc = ensure(ctx, ctx->z_tloc, sizeof(uint16_t) * n_box);
+  if (!rc) rc = ensure(ctx, ctx->z_bv, sizeof(int) * blocks);
+  if (!rc) rc = ensure(ctx, ctx->z_bt, sizeof(int) * blocks);
+  if (!rc) rc = ensure(ctx, ctx->z_counts, kCountSetsBytes);
+  if (!rc) rc = ensure(ctx, ctx->z_totals, kMeshTotalsBytes);
+  if (!rc) rc = ensure(ctx, ctx->z_verts, 3 * sizeof(float) * v_room);
+  if (!rc && mp.want_normals) rc = ensure(ctx, ctx->z_norms, 3 * sizeof(float) * v_room);
+  if (!rc) rc = ensure(ctx, ctx->z_tris, 3 * sizeof(int32_t) * t_room);
+  if (rc) return rc;
+  ctx->vmesh.active = false;  // (from here on the pinned outputs are being rewritten)
+  flame_hip::MeshScratch sc;
+  sc.cls = (uint8_t*)ctx->z_cls.p, sc.emask = (uint8_t*)ctx->z_emask.p;
+  sc.vloc = (uint16_t*)ctx->z_vloc.p, sc.tloc = (uint16_t*)ctx->z_tloc.p;
+  sc.block_v = (int*)ctx->z_bv.p, sc.block_t = (int*)ctx->z_bt.p;
+  flame_hip::MeshOut mo;
+  mo.vertices = (float*)ctx->z_verts.p, mo.normals = mp.want_normals ? (float*)ctx->z_norms.p : nullptr, mo.triangles = (int32_t*)ctx->z_tris.p;
+  int* counts = (int*)ctx->z_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->vmesh.ev0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_volume_mesh(volume_grid(ctx), box, (const flame_hip::Voxel*)ctx->vol.p, sc, counts, (flame_hip::MeshTotals*)ctx->z_totals.p,
+                                               (int)v_room, (int)t_room, mo, ctx->z_pass, rs));
+  char* h = ctx->vmesh.h.p;
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.at.counts, counts, kCountSetsBytes, hipMemcpyDeviceToHost, rs));
+  HIPCHK(ctx, hipMemcpyAsync(h + mp.at.totals, ctx->z_totals.p, kMeshTotalsBytes, hipMemcpyDeviceToHost, rs));
+  ctx->vmesh_pending = mp;
+  return close_stage(ctx, ctx->vmesh);
+}
+
+int flame_nltgv2_volume_mesh_end(flame_nltgv2_ctx* ctx, flame_nltgv2_volume_mesh_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_mesh_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  flame_nltgv2_ctx::VolumeMeshPending& mp = ctx->vmesh_pending;
+  if (!out || !ctx->vmesh.h.p || !ctx->vmesh.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  hipStream_t rs = ctx->raster_stream;
+  HIPCHK(ctx, hipStreamSynchronize(rs));
+  char* h = ctx->vmesh.h.p;
+  flame_hip::MeshTotals tot;
+  std::memcpy(&tot, h + mp.at.totals, sizeof(tot));
+  int32_t cubes[flame_hip::kMeshCubeCounters];
+  sum_count_slots((const int32_t*)(h + mp.at.counts), flame_hip::kMeshCubeCounters, cubes);
+  const bool overflow = tot.n_vertices > mp.v_room || tot.n_triangles > mp.t_room;  // (the emit pass's own test)
+  const bool host = mp.copy_out && !overflow;
+  if (host && !mp.fetched) {  // exactly what was written, as metric_outputs_end fetches the dense cloud
+    const size_t vb = 3 * sizeof(float) * (size_t)tot.n_vertices, tb = 3 * sizeof(int32_t) * (size_t)tot.n_triangles;
+    if (vb) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.vertices, ctx->z_verts.p, vb, hipMemcpyDeviceToHost, rs));
+    if (vb && mp.want_normals) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.normals, ctx->z_norms.p, vb, hipMemcpyDeviceToHost, rs));
+    if (tb) HIPCHK(ctx, hipMemcpyAsync(h + mp.at.triangles, ctx->z_tris.p, tb, hipMemcpyDeviceToHost, rs));
+    if (vb || tb) HIPCHK(ctx, hipStreamSynchronize(rs));
+    mp.fetched = true;
+  }
+  std::memset(out, 0, sizeof(*out));
+  out->counts.n_vertices = tot.n_vertices, out->counts.n_triangles = tot.n_triangles;
+  out->counts.live_cubes = cubes[0], out->counts.surface_cubes = cubes[1];
+  out->counts.overflow = overflow ? 1 : 0;
+  out->device_ms = stage_ms(ctx->vmesh);
+  const hipEvent_t marks[flame_hip::kMeshPasses + 1] = {ctx->vmesh.ev0, ctx->z_pass[0], ctx->z_pass[1], ctx->z_pass[2], ctx->vmesh.ev1};
+  for (int p = 0; p < flame_hip::kMeshPasses; ++p)
+    if (hipEventElapsedTime(&out->pass_ms[p], marks[p], marks[p + 1]) != hipSuccess) (void)hipGetLastError(), out->pass_ms[p] = 0.0f;
+  out->vertices = host ? (const float*)(h + mp.at.vertices) : nullptr;
+  out->normals = host && mp.want_normals ? (const float*)(h + mp.at.normals) : nullptr;
+  out->triangles = host ? (const int32_t*)(h + mp.at.triangles) : nullptr;
+  out->vertices_device = ctx->z_verts.p;
+  out->normals_device = mp.want_normals ? ctx->z_norms.p : nullptr;
+  out->triangles_device = ctx->z_tris.p;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_mesh(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_mesh_params* params, float* vertices_out, float* normals_out,
+                             int32_t* triangles_out, flame_nltgv2_volume_mesh_counts* counts_out) {
+  flame_nltgv2_volume_mesh_params p;
+  flame_nltgv2_default_volume_mesh_params(&p);
+  if (params) p = *params;
+  p.copy_out = 1, p.want_normals = normals_out != nullptr;
+  int rc = flame_nltgv2_volume_mesh_begin(ctx, params ? &p : nullptr);
+  if (rc) return rc;
+  flame_nltgv2_volume_mesh_view v;
+  rc = flame_nltgv2_volume_mesh_end(ctx, &v);
+  if (rc) return rc;
+  if (counts_out) *counts_out = v.counts;
+  if (v.counts.overflow) return FLAME_NLTGV2_OK;
+  const size_t vb = 3 * sizeof(float) * (size_t)v.counts.n_vertices;
+  if (vertices_out && vb) std::memcpy(vertices_out, v.vertices, vb);
+  if (normals_out && vb) std::memcpy(normals_out, v.normals, vb);
+  if (triangles_out && v.counts.n_triangles) std::memcpy(triangles_out, v.triangles, 3 * sizeof(int32_t) * (size_t)v.counts.n_triangles);
   return FLAME_NLTGV2_OK;
 }
 

@@ -1,7 +1,7 @@
 // side_stage.hpp -- the pure part of the stages on the side stream (nltgv2_frame_capi.hip: the dense map, the mesh outputs, the debug
 // images, the wireframe, the metric outputs, the map error, the view renderer, the fusion of views), no HIP and no context: what the context knows about the triangles resident in r_tris, where each stage's
 // outputs lie in its pinned buffer, and the triangle index check.  tests/cpp/side_stage_test.cc walks all of it (MetricLayout:
-// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc; FuseLayout: tests/cpp/fuse_layout_test.cc; VolumeLayout: tests/cpp/volume_layout_test.cc).
+// tests/cpp/metric_layout_test.cc; MapErrorLayout: tests/cpp/map_error_layout_test.cc; ViewLayout: tests/cpp/view_layout_test.cc; FuseLayout: tests/cpp/fuse_layout_test.cc; VolumeLayout: tests/cpp/volume_layout_test.cc; VolumeMeshLayout and the box check: tests/cpp/volume_mesh_layout_test.cc).
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
@@ -243,6 +243,49 @@ inline uint64_t volume_voxels(int nx, int ny, int nz) {
   if (nx < 1 || ny < 1 || nz < 1 || nx > kVolumeMaxAxis || ny > kVolumeMaxAxis || nz > kVolumeMaxAxis) return 0;
   const uint64_t n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
   return n <= kVolumeMaxVoxels ? n : 0;
+}
+
+// The volume's surface extraction (flame_nltgv2_volume_mesh_begin).
+constexpr size_t kMeshCountBytes = 8 * sizeof(int32_t);   // flame_nltgv2_volume_mesh_counts
+constexpr size_t kMeshTotalsBytes = 4 * sizeof(int32_t);  // what the scan leaves: n_vertices, n_triangles, 0, 0
+constexpr uint64_t kMeshMaxBoxVoxels = 1ull << 26;        // 7 vertices and 12 triangles per voxel stay below 2^31
+// The box lo <= index < hi of a volume of dims voxels (all-zero hi: the whole volume): its voxels, its lower corner and its extent; 0 for
+// a box that is out of range, empty or over kMeshMaxBoxVoxels.
+inline uint64_t mesh_box_voxels(const int32_t dims[3], const int32_t lo[3], const int32_t hi[3], int32_t lo_out[3], int32_t n_out[3]) {
+  const bool whole = hi[0] == 0 && hi[1] == 0 && hi[2] == 0;
+  uint64_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    const int32_t h = whole ? dims[a] : hi[a];
+    if (lo[a] < 0 || lo[a] >= h || h > dims[a]) return 0;
+    lo_out[a] = lo[a], n_out[a] = h - lo[a];
+    n *= (uint64_t)(h - lo[a]);
+  }
+  return n <= kMeshMaxBoxVoxels ? n : 0;
+}
+// The elements the device arrays (and with copy_out the pinned ones) hold: the caller's capacity, but no more than the box can give.
+inline int64_t mesh_vertex_room(uint64_t box_voxels, int32_t max_vertices) {
+  const int64_t most = 7 * (int64_t)box_voxels;
+  return max_vertices < most ? max_vertices : most;
+}
+inline int64_t mesh_triangle_room(uint64_t box_voxels, int32_t max_triangles) {
+  const int64_t most = 12 * (int64_t)box_voxels;
+  return max_triangles < most ? max_triangles : most;
+}
+struct VolumeMeshLayout {
+  // the cube counters' partial sets | the scan's totals | 3 * room floats | 3 * room floats | 3 * room int32.  The counters are always
+  // there; the arrays take room only with copy_out, the normals only if wanted.
+  size_t counts, totals, vertices, normals, triangles, total;
+};
+inline VolumeMeshLayout volume_mesh_layout(int64_t vertex_room, int64_t triangle_room, bool want_normals, bool copy_out) {
+  const size_t vb = copy_out ? 3 * sizeof(float) * (size_t)vertex_room : 0;
+  VolumeMeshLayout m;
+  m.counts = 0;
+  m.totals = up16(kCountSetsBytes);
+  m.vertices = m.totals + up16(kMeshTotalsBytes);
+  m.normals = m.vertices + up16(vb);
+  m.triangles = m.normals + up16(want_normals ? vb : 0);
+  m.total = m.triangles + up16(copy_out ? 3 * sizeof(int32_t) * (size_t)triangle_room : 0) + 16;
+  return m;
 }
 
 // Every index of T triangles names one of V vertices.

@@ -309,6 +309,31 @@ class _RaycastView(C.Structure):
                 ("map", _FP), ("map_device", C.c_void_p)]
 
 
+class VolumeMeshParams(C.Structure):
+    """== flame_nltgv2_volume_mesh_params (same defaults): the box lo <= index < hi (all-zero hi: the whole volume), the capacities, and
+    whether normals are made and the arrays travel to the host."""
+
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("max_vertices", C.c_int32), ("max_triangles", C.c_int32),
+                ("want_normals", C.c_int32), ("copy_out", C.c_int32)]
+
+    def __init__(self, lo=(0, 0, 0), hi=(0, 0, 0), max_vertices=0, max_triangles=0, want_normals=True, copy_out=True):
+        super().__init__((C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]), int(max_vertices), int(max_triangles),
+                         int(bool(want_normals)), int(bool(copy_out)))
+
+
+class VolumeMeshCounts(C.Structure):
+    """== flame_nltgv2_volume_mesh_counts: 8 words."""
+
+    _fields_ = [("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("live_cubes", C.c_int32), ("surface_cubes", C.c_int32),
+                ("overflow", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class _VolumeMeshView(C.Structure):
+    _fields_ = [("counts", VolumeMeshCounts), ("device_ms", C.c_float), ("pass_ms", C.c_float * 4), ("reserved", C.c_int32 * 3),
+                ("vertices", _FP), ("vertices_device", C.c_void_p), ("normals", _FP), ("normals_device", C.c_void_p),
+                ("triangles", C.POINTER(C.c_int32)), ("triangles_device", C.c_void_p)]
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -407,6 +432,7 @@ ABI_SYMBOLS = (
     "flame_nltgv2_volume_create", "flame_nltgv2_volume_reset", "flame_nltgv2_volume_destroy", "flame_nltgv2_volume_info",
     "flame_nltgv2_volume_download", "flame_nltgv2_volume_upload", "flame_nltgv2_volume_integrate_begin", "flame_nltgv2_volume_integrate_end",
     "flame_nltgv2_volume_integrate", "flame_nltgv2_volume_raycast_begin", "flame_nltgv2_volume_raycast_end", "flame_nltgv2_volume_raycast",
+    "flame_nltgv2_default_volume_mesh_params", "flame_nltgv2_volume_mesh_begin", "flame_nltgv2_volume_mesh_end", "flame_nltgv2_volume_mesh",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -530,6 +556,10 @@ def load_library():
         "flame_nltgv2_volume_raycast_begin": (C.c_int, [ctx, _FP, _FP, C.POINTER(RaycastParams), C.c_int, C.c_int]),
         "flame_nltgv2_volume_raycast_end": (C.c_int, [ctx, C.POINTER(_RaycastView)]),
         "flame_nltgv2_volume_raycast": (C.c_int, [ctx, _FP, _FP, C.POINTER(RaycastParams), C.c_int, C.c_int, _FP, C.POINTER(RaycastCounts)]),
+        "flame_nltgv2_default_volume_mesh_params": (None, [C.POINTER(VolumeMeshParams)]),
+        "flame_nltgv2_volume_mesh_begin": (C.c_int, [ctx, C.POINTER(VolumeMeshParams)]),
+        "flame_nltgv2_volume_mesh_end": (C.c_int, [ctx, C.POINTER(_VolumeMeshView)]),
+        "flame_nltgv2_volume_mesh": (C.c_int, [ctx, C.POINTER(VolumeMeshParams), _FP, _FP, C.POINTER(C.c_int32), C.POINTER(VolumeMeshCounts)]),
         "flame_nltgv2_default_debug_image_params": (None, [C.POINTER(DebugImageParams)]),
         "flame_nltgv2_debug_images_begin": (C.c_int, [ctx, C.c_void_p, C.c_void_p, C.c_int, _FP, C.POINTER(DebugImageParams), C.c_int,
                                                       C.c_int]),
@@ -1185,6 +1215,42 @@ class Regularizer:
         """volume_raycast_begin; volume_raycast_end."""
         self.volume_raycast_begin(Kinv, T_world_cam, rows, cols, params)
         return self.volume_raycast_end()
+
+    def volume_mesh_begin(self, params: VolumeMeshParams = None):
+        """Enqueues the surface extraction of a box of the volume (marching tetrahedra, flame_nltgv2.h) on the side stream and returns."""
+        p = params if params is not None else VolumeMeshParams()
+        self._chk(self._L.flame_nltgv2_volume_mesh_begin(self._ctx, C.byref(p)), "volume_mesh_begin")
+
+    def volume_mesh_end(self, copy=True) -> dict:
+        """Waits for the side stream; dict(counts (8 i32), n_vertices, n_triangles, live_cubes, surface_cubes, overflow, device_ms,
+        pass_ms (4 f32: classify, count, scan, emit), device = {"vertices", "normals", "triangles": addresses} and, with copy_out and no
+        overflow, vertices (n, 3) f32, normals (n, 3) f32 (if wanted), triangles (m, 3) i32).  copy=False: views of the context's pinned
+        memory, valid until the next begin."""
+        v = _VolumeMeshView()
+        self._chk(self._L.flame_nltgv2_volume_mesh_end(self._ctx, C.byref(v)), "volume_mesh_end")
+        c = v.counts
+        out = dict(counts=np.frombuffer(bytes(c), np.int32).copy(), n_vertices=int(c.n_vertices), n_triangles=int(c.n_triangles),
+                   live_cubes=int(c.live_cubes), surface_cubes=int(c.surface_cubes), overflow=int(c.overflow), device_ms=float(v.device_ms),
+                   pass_ms=np.array(list(v.pass_ms), np.float32), device={})
+        for name, dev in (("vertices", v.vertices_device), ("normals", v.normals_device), ("triangles", v.triangles_device)):
+            if dev:
+                out["device"][name] = int(dev)
+        for name, ptr, n, dt in (("vertices", v.vertices, c.n_vertices, np.float32), ("normals", v.normals, c.n_vertices, np.float32),
+                                 ("triangles", v.triangles, c.n_triangles, np.int32)):
+            if ptr:
+                a = np.ctypeslib.as_array(ptr, shape=(n, 3)) if n > 0 else np.zeros((0, 3), dt)
+                out[name] = a.copy() if copy else a
+        return out
+
+    def volume_mesh(self, params: VolumeMeshParams = None, lo=(0, 0, 0), hi=(0, 0, 0), want_normals=True) -> dict:
+        """volume_mesh_begin; volume_mesh_end.  Without params: a count query (max_* = 0, nothing but the counters travels), then the call
+        with exactly the counts it gave."""
+        if params is None:
+            self.volume_mesh_begin(VolumeMeshParams(lo, hi, 0, 0, False, False))
+            q = self.volume_mesh_end()
+            params = VolumeMeshParams(lo, hi, q["n_vertices"], q["n_triangles"], want_normals, True)
+        self.volume_mesh_begin(params)
+        return self.volume_mesh_end()
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

@@ -322,6 +322,24 @@ struct RaycastView {
   const float* idepthmap = nullptr;    const void* idepthmap_device = nullptr;  // [rows * cols]
 };
 
+// The surface extraction's parameters (flame_nltgv2_volume_mesh_params with its defaults: the whole volume, capacities 0 -- a count query).
+struct VolumeMeshParams : flame_nltgv2_volume_mesh_params {
+  VolumeMeshParams() { flame_nltgv2_default_volume_mesh_params(this); }
+};
+
+// The volume's surface as a triangle mesh (flame_nltgv2_volume_mesh_view): vertices in the world frame, unit normals into free space,
+// triangles counter-clockwise seen from there, and the counters.  Host pointers into pinned memory of the DeviceGraph (nullptr with
+// copy_out == 0 and on overflow; the normals also without want_normals) and the device pointers of the same arrays; all valid until its
+// next volumeMeshBegin().  On overflow ask again with counts.n_vertices / counts.n_triangles as the capacities.
+struct VolumeMesh {
+  flame_nltgv2_volume_mesh_counts counts;
+  float device_ms = 0.0f;
+  const float* vertices = nullptr;     const void* vertices_device = nullptr;   // [3 * counts.n_vertices]
+  const float* normals = nullptr;      const void* normals_device = nullptr;    // [3 * counts.n_vertices]
+  const int32_t* triangles = nullptr;  const void* triangles_device = nullptr;  // [3 * counts.n_triangles]
+  VolumeMesh() { std::memset(&counts, 0, sizeof(counts)); }
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -614,6 +632,19 @@ class DeviceGraph {
     r.rows = v.rows, r.cols = v.cols, r.counts = v.counts;
     r.idepthmap = v.map, r.idepthmap_device = v.map_device;
     return r;
+  }
+  // The surface of a box of the volume as a triangle mesh, on the side stream (flame_nltgv2_volume_mesh_begin / _end): for example every
+  // N frames, or when a pose-frame is pruned and what it saw lives on in the volume alone.
+  void volumeMeshBegin(const VolumeMeshParams& params) { check(flame_nltgv2_volume_mesh_begin(ctx_, &params), "volume_mesh_begin"); }
+  VolumeMesh volumeMeshEnd() {
+    flame_nltgv2_volume_mesh_view v;
+    check(flame_nltgv2_volume_mesh_end(ctx_, &v), "volume_mesh_end");
+    VolumeMesh m;
+    m.counts = v.counts, m.device_ms = v.device_ms;
+    m.vertices = v.vertices, m.vertices_device = v.vertices_device;
+    m.normals = v.normals, m.normals_device = v.normals_device;
+    m.triangles = v.triangles, m.triangles_device = v.triangles_device;
+    return m;
   }
 
   // drawInverseDepthMap (flame.cc:2699-2719) and interpolateMesh(w1), interpolateMesh(w2), drawNormals (flame.cc:497-506, 2667-2697) over

@@ -862,7 +862,8 @@ int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_param
  * end    waits for the side stream and fills *out.
  * flame_nltgv2_volume_integrate / flame_nltgv2_volume_raycast == begin (the raycast with copy_out forced to 1); end; copies into the
  *        caller's arrays (each may be NULL).
- * Not done: normals, colour, surface extraction, a sparse or hashed volume, a volume that moves with the camera. */
+ * (The surface as a triangle mesh with normals: flame_nltgv2_volume_mesh_begin, below this block.)
+ * Not done: colour, a sparse or hashed volume, a volume that moves with the camera. */
 typedef struct flame_nltgv2_volume_params {
   int32_t nx, ny, nz;      /* 64, 64, 64 */
   float   voxel_size;      /* 0.05       metres */
@@ -935,6 +936,89 @@ int flame_nltgv2_volume_raycast_end(flame_nltgv2_ctx* ctx, flame_nltgv2_raycast_
 int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const float* T_world_cam,
                                 const flame_nltgv2_raycast_params* params, int rows, int cols, float* map_out,
                                 flame_nltgv2_raycast_counts* counts_out);
+
+/* ---- Volumetric map: the surface as a triangle mesh --------------------------------------------------------------------------------------
+ * flame_nltgv2_volume_mesh_begin turns a box of the volume into a triangle mesh with vertex normals on the device, on the side stream
+ * beside a running solver; the volume is read only.  The reference has no counterpart: the rules are stated here in full (UNPINNED);
+ * tests/volume_mesh_ref.py restates them in numpy float32 and is the checker: device and checker agree bit for bit.  All arithmetic is
+ * float32 without FMA, with correctly rounded division and sqrtf.  Marching TETRAHEDRA, not marching cubes: no 256-case table, no
+ * ambiguous faces, a surface that is watertight by construction.
+ *
+ * THE BOX.  A call works on the voxels lo[a] <= index < hi[a] per axis; all-zero hi means the whole volume.  0 <= lo < hi <= n_axis, and
+ *   a box holds at most 2^26 voxels, so that 7 vertices and 12 triangles per voxel never pass int32.  A larger volume is meshed in several
+ *   calls: boxes that overlap by one voxel layer tile it -- their triangles are disjoint, their union is the whole extraction, and a
+ *   vertex both have has the same key, position and normal in both.
+ * CUBES.  Cube (i, j, k) has its lower corner at voxel (i, j, k) and all eight corners inside the box.  It is LIVE iff all eight weights
+ *   are > 0 (the raycast's rule).  A box with an axis of one voxel has no cube.
+ * INSIDE.  A voxel is inside iff tsdf <= 0.0f: a NaN is outside, -0.0f inside (the raycast's "ends at the first sample <= 0").
+ * TETS.  Each live cube is cut into six tetrahedra, one per permutation (a, b, c) of the axes, in the order xyz, xzy, yxz, yzx, zxy, zyx,
+ *   with the corners A = c, B = c + e_a, C = c + e_a + e_b, D = c + (1, 1, 1) (Kuhn's decomposition: the face diagonals of neighbouring
+ *   cubes agree, which closes the surface).
+ * EDGES AND KEYS.  Every tet edge runs from a voxel, its owner, to the voxel at offset E[e],
+ *   E = [(1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1)].  Its key is voxel_linear_index * 7 + e (64 bits) with the volume's
+ *   linear index (k * ny + j) * nx + i: boxes agree on keys.
+ * TRIANGLES OF A TET.  From the 4-bit mask of inside corners, bit 0 = A .. bit 3 = D.  Masks 0 and 15: none.  One corner P alone on its
+ *   side, the others Q < R < S by letter: the triangle (PQ, PR, PS).  Two inside P < Q and two outside R < S: the quad PR, PS, QS, QR, split
+ *   along PR - QS into (PR, PS, QS) and (PR, QS, QR).  The second and third corners are swapped where needed so that
+ *   det(b - a, c - a, O - a) > 0, with a, b, c the midpoints of the three edges and O the lowest-lettered outside corner (everything doubled:
+ *   exact integers): counter-clockwise seen from the outside (positive tsdf, free space).  The 6 x 16 table is generated from this rule by
+ *   the checker; the device reads flame_amd/csrc/volume_mesh_table.h, written by that generator.
+ * VERTICES.  One for exactly the keys that at least one triangle names: an edge with a sign change but no live cube of the box around it
+ *   has none.  t = f0 / (f0 - f1) with f0 the owner's tsdf and f1 the far end's, whichever is inside; position p0 + t * (p1 - p0) per
+ *   axis with p = origin + (float)index * voxel_size as in integration rule 1.  f1 == 0 puts a vertex on a corner and may give zero-area
+ *   triangles: they are kept.  Non-finite tsdf values go through the arithmetic as they are.
+ * NORMALS (want_normals).  The gradient at a voxel, per axis, over the neighbours inside the VOLUME (not the box) with weight > 0: both:
+ *   (f+ - f-) * 0.5f; one: f+ - f0 or f0 - f-; none: 0.0f.  At a vertex n = g0 + t * (g1 - g0) per component,
+ *   len = sqrtf((nx * nx + ny * ny) + nz * nz), n / len per component where len > 0, else (0, 0, 0).  It points where tsdf grows: into free
+ *   space, the side the triangles face.
+ * ORDER.  Vertices in ascending key order; triangles by (the cube's linear index in the volume, tet 0 .. 5, triangle 0 .. 1); a triangle's
+ *   corner is the rank of its key among the vertices.  Count, scan, scatter with every element placed by rank: no counter is raced for,
+ *   no floating-point atomics, two calls give the same bytes.
+ * CAPACITY.  max_vertices and max_triangles, both >= 0.  The counts are always returned; the arrays are written only if BOTH fit,
+ *   otherwise overflow = 1, nothing is promised about the arrays, and the caller asks again with the counts it was given
+ *   (max_* = 0 is a pure count query).  The device arrays, and with copy_out the pinned ones, take room for
+ *   min(max_vertices, 7 * box voxels) vertices and min(max_triangles, 12 * box voxels) triangles; between the passes the stage keeps
+ *   6 bytes per voxel of the box.
+ *
+ * begin  checks every argument -- no volume; NULL params; a box out of range, empty or over 2^26 voxels; a negative capacity: reported
+ *        before anything is enqueued, leaving the volume, an earlier view and a pending _end as they are --, then enqueues everything on
+ *        the side stream.
+ * end    waits, reads the counts and, with copy_out and no overflow, fetches exactly n_vertices / n_triangles elements.  The host
+ *        pointers (NULL with copy_out == 0, on overflow, the normals without want_normals) and the device pointers beside them are valid
+ *        until the next flame_nltgv2_volume_mesh_begin.  With copy_out == 0 only the counters travel.
+ * flame_nltgv2_volume_mesh == begin with copy_out forced to 1 and want_normals = (normals_out != NULL); end; copies into the caller's
+ *        arrays (each may be NULL), which hold max_vertices / max_triangles elements; nothing is copied on overflow.
+ * Not done: colour, vertex welding across calls, decimation, a sparse or hashed volume, a volume that moves with the camera. */
+typedef struct flame_nltgv2_volume_mesh_params {
+  int32_t lo[3];           /* 0, 0, 0 */
+  int32_t hi[3];           /* 0, 0, 0    all zero: the whole volume */
+  int32_t max_vertices;    /* 0 */
+  int32_t max_triangles;   /* 0 */
+  int32_t want_normals;    /* 1 */
+  int32_t copy_out;        /* 1  0: the arrays stay on the device; only the counters travel */
+} flame_nltgv2_volume_mesh_params;
+void flame_nltgv2_default_volume_mesh_params(flame_nltgv2_volume_mesh_params* p);
+
+/* 8 words.  surface_cubes: live cubes with at least one triangle. */
+typedef struct flame_nltgv2_volume_mesh_counts {
+  int32_t n_vertices, n_triangles, live_cubes, surface_cubes, overflow;
+  int32_t reserved[3];
+} flame_nltgv2_volume_mesh_counts;
+
+typedef struct flame_nltgv2_volume_mesh_view {
+  flame_nltgv2_volume_mesh_counts counts;
+  float   device_ms;       /* measurement aid: HIP-event time of what begin enqueued on the side stream */
+  float   pass_ms[4];      /* ... of its passes: classify, count, scan, emit (with the copies out of the counters) */
+  int32_t reserved[3];
+  const float*   vertices;   const void* vertices_device;    /* [3 * n_vertices] world frame */
+  const float*   normals;    const void* normals_device;     /* [3 * n_vertices] */
+  const int32_t* triangles;  const void* triangles_device;   /* [3 * n_triangles] */
+} flame_nltgv2_volume_mesh_view;
+
+int flame_nltgv2_volume_mesh_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_mesh_params* params);
+int flame_nltgv2_volume_mesh_end(flame_nltgv2_ctx* ctx, flame_nltgv2_volume_mesh_view* out);
+int flame_nltgv2_volume_mesh(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_mesh_params* params, float* vertices_out, float* normals_out,
+                             int32_t* triangles_out, flame_nltgv2_volume_mesh_counts* counts_out);
 
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
