@@ -111,7 +111,21 @@ void flame_stereo_destroy(flame_stereo_ctx* ctx);
 int flame_stereo_set_stream(flame_stereo_ctx* ctx, void* hip_stream);
 
 /* Camera and image geometry (Flame::Flame, flame.cc:48-60: K_, Kinv_, width_, height_).  K, Kinv row-major.
- * `border` is the padding Frame::create gets (flame.cc:149-150: params.fparams.win_size = 5).  Drops all frames. */
+ * `border` is the padding Frame::create gets (flame.cc:149-150: params.fparams.win_size = 5).  Drops all frames.
+ *
+ * Which entries are read.  Both matrices are stored whole and nothing about their form is checked here.  The stages read them as the
+ * reference's EpipolarGeometry does (epipolar_geometry.h), which is written for a pinhole camera -- K = [fx 0 cx; 0 fy cy; 0 0 1]
+ * and its inverse -- and mixes two kinds of expression:
+ *   - the shortcuts read K[0], K[2], K[4], K[5] and Kinv[0], Kinv[2], Kinv[4], Kinv[5] only: project(), the epipole, the epipolar line
+ *     of a pixel and minDepthProjection (epipolar_geometry.h:97-99, 165-172, 242-259, 317-320), hence the epipolar search, the
+ *     prediction of a feature in the new frame, projectFeatures and prunePoseFrames; flame_stereo_align_frame reads the same four of
+ *     K divided by the level's scale, and REFUSES a K whose [1], [3], [6] or [7] is not 0 or whose [8] is not 1;
+ *   - the full 3x3 products: KRKinv = (K * R) * Kinv and Kt = K * t (epipolar_geometry.h:91-93), read by the disparity-to-depth
+ *     conversion and by the projection at infinity; the height rule of flame_stereo_select_graph_features (xyz = Kinv * pix, all nine
+ *     entries); and flame_stereo_add_raw_frame, which reads Kinv[0..5], the first two rows, in full.
+ * For a pinhole K the two kinds agree.  For a K with a skew, or a last row other than 0 0 1, they describe different cameras and the
+ * stereo update is not meaningful (the reference has the same property and checks it no more than this call does); the selection's
+ * height and the raw-frame map are well defined for any Kinv and are tested with a general one. */
 int flame_stereo_set_camera(flame_stereo_ctx* ctx, const float K[9], const float Kinv[9], int width, int height,
                             int border);
 

@@ -20,17 +20,21 @@ def build_program(tmp_path):
     return exe
 
 
-def write_fixture(path):
+def write_fixture(path, general=False):
     from oracle import stereo_capi as so
     from tests import input_ref as ir
     from tests import raw_frame_cases as rc
     from tests.test_feature_frontend import PAD
 
     cases = [(rc.EXACT_SHIFT, ir.GREY8, 0), ("pincushion", ir.BGR8, 5)]
+    if general:  # a working camera whose K and Kinv are no pinhole's and a raw camera with a skew (tests/test_general_cameras_ref.py)
+        from tests import test_general_cameras_ref as general_cases
+
+        cases = [("general", ir.BGR8, 5)]
     with open(path, "wb") as f:
         np.int32([len(cases)]).tofile(f)
         for case, fmt, pad in cases:
-            w, h, K, Kinv, p = rc.setup(case)
+            w, h, K, Kinv, p = general_cases.input_case() if general else rc.setup(case)
             raw = rc.raw_bytes(p["raw_width"], p["raw_height"], fmt, pad)
             grey, n_outside = ir.rectify(raw, fmt, p, K, Kinv, w, h)
             if case is rc.EXACT_SHIFT:
@@ -57,3 +61,13 @@ def test_raw_frame_facade_round_trip(built, tmp_path):
     r = subprocess.run([build_program(tmp_path), str(tmp_path / "fixture.bin")], capture_output=True, text=True, timeout=300)
     print(r.stdout, r.stderr)
     assert r.returncode == 0 and r.stdout.count(": ok") == 3 and "FAIL" not in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_raw_frame_facade_round_trip_with_a_general_camera(built, tmp_path):
+    """The constructor copies K(r, c) and Kinv(r, c) element by element: with matrices that differ from their transposes, and with K_raw[1]
+    set, the frame is still the checker's."""
+    write_fixture(str(tmp_path / "general.bin"), general=True)
+    r = subprocess.run([build_program(tmp_path), str(tmp_path / "general.bin")], capture_output=True, text=True, timeout=300)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and r.stdout.count(": ok") == 2 and "FAIL" not in r.stdout, r.stdout + r.stderr

@@ -35,13 +35,26 @@ def test_render_view_facade_compiles_and_fails_loudly_without_a_device(built, tm
 
 @pytest.mark.gpu
 def test_render_view_facade_round_trip(built, tmp_path):
+    rows, cols = 75, 100
+    c = tg.mesh_case(21, K_dst=cases.camera(90.0, 50.0, 37.5)[0], R=cases.rotation_y(12.0), t=np.array([-0.4, 0.05, 0.1], F), near_depth=0.25,
+                     rows=rows, cols=cols)
+    round_trip(tmp_path, c, rows, cols)
+
+
+@pytest.mark.gpu
+def test_render_view_facade_round_trip_with_general_cameras(built, tmp_path):
+    """Kinv_src, K_dst and R without a zero (tests/test_general_cameras_ref.py): what ViewParams carries through the facade, entry by entry."""
+    from tests import test_general_cameras_ref as general_cases
+
+    c = dict(general_cases.general_view(), near_depth=0.25)
+    round_trip(tmp_path, c, c["rows"], c["cols"])
+
+
+def round_trip(tmp_path, c, rows, cols):
     import torch  # noqa: F401
 
     import flame_amd
 
-    rows, cols = 75, 100
-    c = tg.mesh_case(21, K_dst=cases.camera(90.0, 50.0, 37.5)[0], R=cases.rotation_y(12.0), t=np.array([-0.4, 0.05, 0.1], F), near_depth=0.25,
-                     rows=rows, cols=cols)
     tris = c["tris"]
     mask = (np.arange(len(tris)) % 4 != 1).astype(np.uint8)
     g = tg.graph_of(c["pos"], c["idepth"], tris)
