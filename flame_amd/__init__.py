@@ -11,6 +11,8 @@ from .regularizer import (  # noqa: F401
     MAP_ERROR_PHOTO,
     MAP_ERROR_TRUTH,
     DebugImageParams,
+    FollowParams,
+    FollowPlan,
     FuseCounts,
     FuseParams,
     FuseSource,
@@ -25,6 +27,7 @@ from .regularizer import (  # noqa: F401
     RaycastCounts,
     RaycastParams,
     Regularizer,
+    ShiftCounts,
     ViewCounts,
     ViewParams,
     VolumeMeshCounts,

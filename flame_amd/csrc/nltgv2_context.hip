@@ -535,7 +535,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
   ok = ok && hipEventCreateWithFlags(&ctx->ev_snap, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_raster_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_topo_ready, hipEventDisableTiming) == hipSuccess;
-  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire, &ctx->metric, &ctx->merr, &ctx->view, &ctx->fuse, &ctx->vint, &ctx->vray, &ctx->vmesh})
+  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire, &ctx->metric, &ctx->merr, &ctx->view, &ctx->fuse, &ctx->vint, &ctx->vray, &ctx->vmesh, &ctx->vshift})
     ok = ok && hipEventCreate(&st->ev0) == hipSuccess && hipEventCreate(&st->ev1) == hipSuccess;
   for (hipEvent_t& e : ctx->z_pass) ok = ok && hipEventCreate(&e) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ev_expanded, hipEventDisableTiming) == hipSuccess;
@@ -596,7 +596,7 @@ int flame_nltgv2_create(flame_nltgv2_ctx** out, int device) {
     ctx->all.push_back(b);
   for (DevBuf* b : {&ctx->f_vtx, &ctx->f_keys, &ctx->f_counts, &ctx->f_big, &ctx->f_fused, &ctx->f_pmask, &ctx->f_imask, &ctx->f_spread, &ctx->f_layers})
     ctx->all.push_back(b);
-  for (DevBuf* b : {&ctx->vol, &ctx->vi_counts, &ctx->y_map, &ctx->y_counts}) ctx->all.push_back(b);
+  for (DevBuf* b : {&ctx->vol, &ctx->vol2, &ctx->vs_counts, &ctx->vi_counts, &ctx->y_map, &ctx->y_counts}) ctx->all.push_back(b);
   for (DevBuf* b : {&ctx->z_cls, &ctx->z_emask, &ctx->z_vloc, &ctx->z_tloc, &ctx->z_bv, &ctx->z_bt, &ctx->z_counts, &ctx->z_totals, &ctx->z_verts,
                     &ctx->z_norms, &ctx->z_tris})
     ctx->all.push_back(b);
@@ -637,7 +637,7 @@ int flame_nltgv2_destroy(flame_nltgv2_ctx* ctx) {
   for (hipEvent_t e : ctx->ev_run)
     if (e) (void)hipEventDestroy(e);
   if (ctx->h_img.p) (void)hipHostFree(ctx->h_img.p);
-  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire, &ctx->metric, &ctx->merr, &ctx->view, &ctx->fuse, &ctx->vint, &ctx->vray, &ctx->vmesh}) {
+  for (SideStage* st : {&ctx->mesh, &ctx->dbg, &ctx->wire, &ctx->metric, &ctx->merr, &ctx->view, &ctx->fuse, &ctx->vint, &ctx->vray, &ctx->vmesh, &ctx->vshift}) {
     if (st->h.p) (void)hipHostFree(st->h.p);
     if (st->ev0) (void)hipEventDestroy(st->ev0);
     if (st->ev1) (void)hipEventDestroy(st->ev1);

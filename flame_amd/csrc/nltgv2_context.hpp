@@ -416,6 +416,17 @@ struct flame_nltgv2_ctx {
     bool copy_out = false;
     VolumeLayout at{};
   } vray_pending;
+  // flame_nltgv2_volume_shift_* (volume_shift_kernels.hip): the window's base on the global grid, and the second buffer the shift writes,
+  // allocated at the first shift that moves anything; _begin swaps vol and vol2 behind its enqueue, and every later stage follows on
+  // the same stream.  Pinned: integrate_layout (the counters alone).
+  int32_t vol_base[3] = {0, 0, 0};
+  DevBuf vol2, vs_counts;
+  SideStage vshift;
+  struct ShiftPending {
+    int32_t shift[3] = {0, 0, 0}, base[3] = {0, 0, 0};
+    int record_bytes = 0;
+    VolumeLayout at{};
+  } vshift_pending;
   // flame_nltgv2_volume_mesh_* (volume_mesh_kernels.hip): the passes' scratch (6 bytes per voxel of the box, 8 per workgroup), the cube
   // counters and the scan's totals, and the mesh, which stays in z_verts / z_norms / z_tris until the next call.  Pinned:
   // volume_mesh_layout; z_pass: the events between the four passes.

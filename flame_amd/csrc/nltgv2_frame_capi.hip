@@ -10,7 +10,8 @@
 //   the fusion of views       fuse_views_begin / _end: up to eight kept or live meshes in one camera, a vote per pixel
 //   the volumetric map        volume_create / _reset / _destroy / _info / _download / _upload; volume_integrate_begin / _end: a depth map folded
 //                             into the truncated-signed-distance volume; volume_raycast_begin / _end: the volume seen from a camera;
-//                             volume_mesh_begin / _end: its surface as a triangle mesh with normals
+//                             volume_mesh_begin / _end: its surface as a triangle mesh with normals; volume_shift_begin / _end,
+//                             volume_window, volume_follow: the window that follows the camera
 //   the photometric residual  photo_set_images, photo_residual, photo_fuse, photo_residual_last
 // The eleven begin / end pairs are stages on the side stream (raster_stream) and share one skeleton: every argument is checked before the
 // stream or a buffer is touched, so an error leaves what an earlier begin put into the stage's pinned outputs, and its pending _end, as
@@ -167,6 +168,10 @@ static_assert(sizeof(flame_hip::IntegrateCounts) == sizeof(flame_nltgv2_integrat
               "the counters on the device, in the header and in integrate_layout are one struct");
 static_assert(sizeof(flame_hip::RaycastCounts) == sizeof(flame_nltgv2_raycast_counts) && sizeof(flame_nltgv2_raycast_counts) == kRaycastCountBytes,
               "the counters on the device, in the header and in raycast_layout are one struct");
+static_assert(sizeof(flame_hip::ShiftCounts) == sizeof(flame_nltgv2_shift_counts) && sizeof(flame_nltgv2_shift_counts) == kShiftCountBytes,
+              "the counters on the device, in the header and in side_stage.hpp are one struct");
+static_assert(sizeof(WindowPlan) == sizeof(flame_nltgv2_follow_plan) && offsetof(WindowPlan, leaving_hi) == offsetof(flame_nltgv2_follow_plan, leaving_hi),
+              "the plan in side_stage.hpp and in the header are one struct");
 static_assert(flame_hip::kVolumeCountsBytes == kCountSetsBytes && flame_hip::kVolumeCountSlots == kCountSets &&
               flame_hip::kVolumeCountSlotWords == kCountSetWords, "the kernels' and the layouts' partial sets of counters");
 static_assert(sizeof(flame_nltgv2_volume_mesh_counts) == kMeshCountBytes && sizeof(flame_hip::MeshTotals) == kMeshTotalsBytes,
@@ -1236,6 +1241,7 @@ static flame_hip::VolumeGrid volume_grid(const flame_nltgv2_ctx* ctx) {
   g.voxel_size = p.voxel_size;
   std::memcpy(g.origin, p.origin, sizeof(g.origin));
   g.trunc = p.trunc, g.max_weight = p.max_weight;
+  for (int a = 0; a < 3; ++a) g.base[a] = ctx->vol_base[a];
   return g;
 }
 static size_t volume_count(const flame_nltgv2_ctx* ctx) {
@@ -1252,6 +1258,11 @@ static int volume_release(flame_nltgv2_ctx* ctx) {
   HIPCHK(ctx, hipFree(ctx->vol.p));
   ctx->device_bytes -= ctx->vol.cap;
   ctx->vol.p = nullptr, ctx->vol.cap = 0;
+  if (ctx->vol2.p) {  // the shift's second buffer goes with it
+    HIPCHK(ctx, hipFree(ctx->vol2.p));
+    ctx->device_bytes -= ctx->vol2.cap;
+    ctx->vol2.p = nullptr, ctx->vol2.cap = 0;
+  }
   return FLAME_NLTGV2_OK;
 }
 
@@ -1279,6 +1290,7 @@ int flame_nltgv2_volume_create(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_
     ctx->device_bytes += bytes;
   }
   ctx->vol_params = *params;
+  ctx->vol_base[0] = ctx->vol_base[1] = ctx->vol_base[2] = 0;
   ctx->have_volume = true;
   LAUNCHCHK(ctx, flame_hip::launch_volume_fill(volume_grid(ctx), (flame_hip::Voxel*)ctx->vol.p, ctx->raster_stream));
   return FLAME_NLTGV2_OK;
@@ -1306,7 +1318,7 @@ int flame_nltgv2_volume_info(flame_nltgv2_ctx* ctx, flame_nltgv2_volume_params* 
   if (rc) return rc;
   if (!ctx->have_volume) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
   if (params_out) *params_out = ctx->vol_params;
-  if (device_bytes_out) *device_bytes_out = (int64_t)ctx->vol.cap;
+  if (device_bytes_out) *device_bytes_out = (int64_t)(ctx->vol.cap + ctx->vol2.cap);
   return FLAME_NLTGV2_OK;
 }
 
@@ -1470,6 +1482,108 @@ int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const 
   if (rc) return rc;
   if (map_out) std::memcpy(map_out, v.map, sizeof(float) * (size_t)v.rows * (size_t)v.cols);
   if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
+}
+
+// ---- the window that follows the camera (see flame_nltgv2.h) ---------------------------------------------------------------------------
+void flame_nltgv2_default_follow_params(flame_nltgv2_follow_params* p) {
+  if (!p) return;
+  p->focus_depth = 0.0f;
+  p->step = 8;
+}
+
+int flame_nltgv2_volume_window(flame_nltgv2_ctx* ctx, int32_t base_out[3]) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume || !base_out) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  std::memcpy(base_out, ctx->vol_base, sizeof(ctx->vol_base));
+  return FLAME_NLTGV2_OK;
+}
+
+// The shift on the side stream: out of place from vol into vol2, then the two change names.  Whatever was enqueued before reads or
+// writes the old vol ahead of the kernel, whatever comes later the new one behind it: the stream's order is the whole synchronisation.
+int flame_nltgv2_volume_shift_begin(flame_nltgv2_ctx* ctx, const int32_t shift[3]) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_shift_begin");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume || !shift) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const int32_t dims[3] = {ctx->vol_params.nx, ctx->vol_params.ny, ctx->vol_params.nz};
+  flame_nltgv2_ctx::ShiftPending sp;
+  if (!shifted_base(ctx->vol_base, shift, sp.base)) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  std::memcpy(sp.shift, shift, sizeof(sp.shift));
+  int s[3];
+  const bool moves = clamped_shift(dims, shift, s);
+  if (moves && !ctx->vol2.p) {  // exactly the bytes of the volume, as flame_nltgv2_volume_create takes them
+    const hipError_t e = hipMalloc(&ctx->vol2.p, ctx->vol.cap);
+    if (e != hipSuccess) {
+      ctx->last_hip = (int)e;
+      ctx->vol2.p = nullptr;
+      (void)hipGetLastError();
+      return fail(ctx, e == hipErrorOutOfMemory ? FLAME_NLTGV2_ERR_OOM : FLAME_NLTGV2_ERR_HIP);
+    }
+    ctx->vol2.cap = ctx->vol.cap;
+    ctx->device_bytes += ctx->vol2.cap;
+  }
+  hipStream_t rs = ctx->raster_stream;
+  sp.at = integrate_layout();
+  rc = open_stage(ctx, ctx->vshift, sp.at.total);
+  if (rc) return rc;
+  rc = ensure(ctx, ctx->vs_counts, kCountSetsBytes);
+  if (rc) return rc;
+  ctx->vshift.active = false;  // (from here on the pinned outputs are being rewritten)
+  int* counts = (int*)ctx->vs_counts.p;
+  HIPCHK(ctx, hipEventRecord(ctx->vshift.ev0, rs));
+  LAUNCHCHK(ctx, flame_hip::launch_volume_shift(volume_grid(ctx), s, (const flame_hip::Voxel*)ctx->vol.p, moves ? (flame_hip::Voxel*)ctx->vol2.p : nullptr,
+                                                counts, &sp.record_bytes, rs));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->vshift.h.p + sp.at.counts, counts, kCountSetsBytes, hipMemcpyDeviceToHost, rs));
+  if (moves) {
+    std::swap(ctx->vol.p, ctx->vol2.p);
+    std::memcpy(ctx->vol_base, sp.base, sizeof(ctx->vol_base));
+  } else {
+    sp.record_bytes = 0;
+  }
+  ctx->vshift_pending = sp;
+  return close_stage(ctx, ctx->vshift);
+}
+
+int flame_nltgv2_volume_shift_end(flame_nltgv2_ctx* ctx, flame_nltgv2_shift_view* out) {
+  flame_hip::RoctxRange roctx_range_("flame_nltgv2_volume_shift_end");
+  int rc = enter(ctx);
+  if (rc) return rc;
+  const flame_nltgv2_ctx::ShiftPending& sp = ctx->vshift_pending;
+  if (!out || !ctx->vshift.h.p || !ctx->vshift.active) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->raster_stream));
+  std::memcpy(out->shift, sp.shift, sizeof(out->shift));
+  std::memcpy(out->base, sp.base, sizeof(out->base));
+  out->device_ms = stage_ms(ctx->vshift);
+  out->record_bytes = sp.record_bytes;
+  sum_count_slots((const int32_t*)(ctx->vshift.h.p + sp.at.counts), (int)(sizeof(out->counts) / sizeof(int32_t)), (int32_t*)&out->counts);
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_shift(flame_nltgv2_ctx* ctx, const int32_t shift[3], flame_nltgv2_shift_counts* counts_out) {
+  int rc = flame_nltgv2_volume_shift_begin(ctx, shift);
+  if (rc) return rc;
+  flame_nltgv2_shift_view v;
+  rc = flame_nltgv2_volume_shift_end(ctx, &v);
+  if (rc) return rc;
+  if (counts_out) *counts_out = v.counts;
+  return FLAME_NLTGV2_OK;
+}
+
+int flame_nltgv2_volume_follow(flame_nltgv2_ctx* ctx, const float* T_world_cam, const flame_nltgv2_follow_params* params,
+                               flame_nltgv2_follow_plan* plan_out) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (!ctx->have_volume || !T_world_cam || !params || !plan_out) return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  const flame_nltgv2_volume_params& vp = ctx->vol_params;
+  const int32_t dims[3] = {vp.nx, vp.ny, vp.nz};
+  int32_t shift[3];
+  if (!follow_shift(T_world_cam, params->focus_depth, params->step, vp.origin, vp.voxel_size, ctx->vol_base, dims, shift))
+    return fail(ctx, FLAME_NLTGV2_ERR_INVALID_ARG);
+  WindowPlan plan;
+  window_plan(dims, shift, &plan);
+  std::memcpy(plan_out, &plan, sizeof(plan));
   return FLAME_NLTGV2_OK;
 }
 

@@ -5,6 +5,7 @@
 #ifndef FLAME_AMD_SIDE_STAGE_HPP_
 #define FLAME_AMD_SIDE_STAGE_HPP_
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -243,6 +244,82 @@ inline uint64_t volume_voxels(int nx, int ny, int nz) {
   if (nx < 1 || ny < 1 || nz < 1 || nx > kVolumeMaxAxis || ny > kVolumeMaxAxis || nz > kVolumeMaxAxis) return 0;
   const uint64_t n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
   return n <= kVolumeMaxVoxels ? n : 0;
+}
+
+// The window that follows the camera (flame_nltgv2_volume_shift_begin, flame_nltgv2_volume_follow): tests/cpp/volume_window_layout_test.cc.
+constexpr size_t kShiftCountBytes = 8 * sizeof(int32_t);  // flame_nltgv2_shift_counts
+constexpr int32_t kVolumeMaxBase = 1 << 22;
+// base + shift, per axis; false where it passes the limit (out is then untouched).
+inline bool shifted_base(const int32_t base[3], const int32_t shift[3], int32_t out[3]) {
+  int64_t b[3];
+  for (int a = 0; a < 3; ++a) {
+    b[a] = (int64_t)base[a] + (int64_t)shift[a];
+    if (b[a] < -(int64_t)kVolumeMaxBase || b[a] > (int64_t)kVolumeMaxBase) return false;
+  }
+  for (int a = 0; a < 3; ++a) out[a] = (int32_t)b[a];
+  return true;
+}
+// The shift as the kernel takes it: each component clamped to +-n_axis (nothing is kept from there on); true if anything moves.
+inline bool clamped_shift(const int32_t dims[3], const int32_t shift[3], int clamped[3]) {
+  bool moves = false;
+  for (int a = 0; a < 3; ++a) {
+    clamped[a] = shift[a] > dims[a] ? dims[a] : shift[a] < -dims[a] ? -dims[a] : shift[a];
+    moves = moves || shift[a] != 0;
+  }
+  return moves;
+}
+// FOLLOW's arithmetic (float32, no FMA: this header is built with -ffp-contract=off); false for an invalid argument.
+inline bool follow_shift(const float* T_world_cam, float focus_depth, int32_t step, const float origin[3], float voxel_size,
+                         const int32_t base[3], const int32_t dims[3], int32_t shift[3]) {
+  if (step < 1 || !std::isfinite(focus_depth)) return false;
+  int32_t s[3];
+  for (int a = 0; a < 3; ++a) {
+    const float c = T_world_cam[4 * a + 3] + focus_depth * T_world_cam[4 * a + 2];
+    if (!std::isfinite(c)) return false;
+    const float g = (c - origin[a]) / voxel_size;
+    const int32_t m = base[a] + dims[a] / 2;
+    const float q = truncf((g - (float)m) / (float)step);
+    if (!(q >= -(float)kVolumeMaxBase && q <= (float)kVolumeMaxBase)) return false;
+    const int64_t prod = (int64_t)(int32_t)q * (int64_t)step;
+    if (prod < INT32_MIN || prod > INT32_MAX) return false;
+    s[a] = (int32_t)prod;
+  }
+  for (int a = 0; a < 3; ++a) shift[a] = s[a];
+  return true;
+}
+// THE PLAN of a shift (flame_nltgv2_follow_plan, word for word).
+struct WindowPlan {
+  int32_t shift[3], n_leaving, has_kept, kept_lo[3], kept_hi[3], leaving_lo[3][3], leaving_hi[3][3], reserved[3];
+};
+inline void window_plan(const int32_t dims[3], const int32_t shift[3], WindowPlan* p) {
+  *p = WindowPlan{};
+  bool all_leave = false;
+  for (int a = 0; a < 3; ++a) {
+    p->shift[a] = shift[a];
+    all_leave = all_leave || (int64_t)shift[a] >= dims[a] || (int64_t)shift[a] <= -(int64_t)dims[a];
+  }
+  if (all_leave) {
+    p->n_leaving = 1;
+    for (int a = 0; a < 3; ++a) p->leaving_hi[0][a] = dims[a];
+    return;
+  }
+  p->has_kept = 1;
+  for (int a = 0; a < 3; ++a) {
+    p->kept_lo[a] = shift[a] > 0 ? shift[a] : 0;
+    p->kept_hi[a] = shift[a] < 0 ? dims[a] + shift[a] : dims[a];
+  }
+  for (int a = 0; a < 3; ++a) {
+    if (shift[a] == 0) continue;
+    int32_t* lo = p->leaving_lo[p->n_leaving];
+    int32_t* hi = p->leaving_hi[p->n_leaving];
+    for (int b = 0; b < 3; ++b) {
+      if (b < a) lo[b] = p->kept_lo[b], hi[b] = p->kept_hi[b];  // the axes whose slabs came before: their kept range
+      else if (b > a) lo[b] = 0, hi[b] = dims[b];
+      else if (shift[a] > 0) lo[b] = 0, hi[b] = shift[a] + 1;   // one layer towards the kept side
+      else lo[b] = dims[a] + shift[a] - 1, hi[b] = dims[a];
+    }
+    ++p->n_leaving;
+  }
 }
 
 // The volume's surface extraction (flame_nltgv2_volume_mesh_begin).

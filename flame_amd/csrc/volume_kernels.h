@@ -1,5 +1,6 @@
 // volume_kernels.h -- launch wrappers of volume_kernels.hip: the truncated-signed-distance volume of a context (include/flame_nltgv2.h,
-// flame_nltgv2_volume_create): fill, fold one inverse-depth map into it, render it into a pinhole camera.
+// flame_nltgv2_volume_create): fill, fold one inverse-depth map into it, render it into a pinhole camera; and of
+// volume_shift_kernels.hip: move the window over the grid (flame_nltgv2_volume_shift_begin).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,8 +24,9 @@ struct Voxel {
 struct VolumeGrid {
   int nx, ny, nz;
   float voxel_size;
-  float origin[3];  // the world position of the centre of voxel (0, 0, 0)
+  float origin[3];  // the world position of the centre of GLOBAL voxel (0, 0, 0)
   float trunc, max_weight;
+  int base[3];      // local voxel (i, j, k) is global voxel base + (i, j, k): the window (flame_nltgv2_volume_shift_begin)
 };
 
 // Per integration call, prepared on the host.
@@ -55,6 +57,12 @@ struct RaycastCounts {
   int hits, back, empty, reserved;
 };
 
+// flame_nltgv2_shift_counts.
+struct ShiftCounts {
+  int kept, kept_seen, lost_seen, entered, reserved[4];
+};
+constexpr int kShiftCounters = 4;
+
 inline long volume_blocks(long n) { return (n + kVolumeBlock - 1) / kVolumeBlock; }
 
 // Every voxel {1.0f, 0.0f}.
@@ -67,5 +75,12 @@ int launch_volume_integrate(const VolumeGrid& g, const IntegrateArgs& a, const f
 // The volume seen from a.pose as an inverse-depth map ([rows * cols], holes the quiet NaN); counts: kVolumeCountsBytes, cleared first,
 // the partial sets of RaycastCounts.
 int launch_volume_raycast(const VolumeGrid& g, const RaycastArgs& a, const Voxel* vol, float* out, int* counts, hipStream_t s);
+
+// The window moved by `shift` voxels (each |shift[a]| <= n_axis; == n_axis: nothing is kept), out of place: dst[(i, j, k)] =
+// src[(i, j, k) + shift] where that lies in the volume, else {1.0f, 0.0f}; src and dst are two buffers of the volume's size, 16-byte
+// aligned.  dst == nullptr: nothing is written, only the counters are made (a zero shift).  counts: kVolumeCountsBytes, cleared first,
+// the partial sets of ShiftCounts.  -> the bytes per access of the path taken (16 where nx and the linear displacement are even, else 8)
+// in *record_bytes.
+int launch_volume_shift(const VolumeGrid& g, const int shift[3], const Voxel* src, Voxel* dst, int* counts, int* record_bytes, hipStream_t s);
 
 }  // namespace flame_hip

@@ -66,9 +66,10 @@ k_volume_integrate(const VolumeGrid g, const IntegrateArgs a, const float* __res
     if (idx < n) {
       const uint32_t row_idx = idx / (uint32_t)g.nx, i = idx - row_idx * (uint32_t)g.nx;
       const uint32_t k = row_idx / (uint32_t)g.ny, j = row_idx - k * (uint32_t)g.ny;
-      const float px = g.origin[0] + (float)i * g.voxel_size;
-      const float py = g.origin[1] + (float)j * g.voxel_size;
-      const float pz = g.origin[2] + (float)k * g.voxel_size;
+      // (the global index: the sum in integers, then the conversion)
+      const float px = g.origin[0] + (float)(g.base[0] + (int)i) * g.voxel_size;
+      const float py = g.origin[1] + (float)(g.base[1] + (int)j) * g.voxel_size;
+      const float pz = g.origin[2] + (float)(g.base[2] + (int)k) * g.voxel_size;
       float Px, Py;
       pose_point(a.pose, px, py, pz, Px, Py, Pz);
       front = Pz > a.near_depth;
@@ -111,12 +112,14 @@ k_volume_integrate(const VolumeGrid g, const IntegrateArgs a, const float* __res
 
 __device__ __forceinline__ float lerp1(float a, float b, float t) { return a + t * (b - a); }
 
-// One axis of a sample: g in [0, n_axis - 1] (a NaN is not), the lower voxel and the fraction.
-__device__ __forceinline__ bool axis_cell(float gv, int n_axis, int& i0, float& f) {
-  if (!(gv >= 0.0f && gv <= (float)(n_axis - 1))) return false;
+// One axis of a sample: the global coordinate g in [base, base + n_axis - 1] (a NaN is not), the lower voxel's LOCAL index and the
+// fraction above the lower GLOBAL voxel.
+__device__ __forceinline__ bool axis_cell(float gv, int base, int n_axis, int& i0, float& f) {
+  if (!(gv >= (float)base && gv <= (float)(base + n_axis - 1))) return false;
   const int fl = (int)floorf(gv);
-  i0 = fl < n_axis - 2 ? fl : n_axis - 2;
-  f = gv - (float)i0;
+  const int ig = fl < base + n_axis - 2 ? fl : base + n_axis - 2;
+  i0 = ig - base;
+  f = gv - (float)ig;
   return true;
 }
 
@@ -147,7 +150,8 @@ k_volume_raycast(const VolumeGrid g, const RaycastArgs a, const Voxel* __restric
       const float gz = (wz - g.origin[2]) / g.voxel_size;
       int ix = 0, iy = 0, iz = 0;
       float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-      bool ok = has_cells && axis_cell(gx, g.nx, ix, fx) && axis_cell(gy, g.ny, iy, fy) && axis_cell(gz, g.nz, iz, fz);
+      bool ok = has_cells && axis_cell(gx, g.base[0], g.nx, ix, fx) && axis_cell(gy, g.base[1], g.ny, iy, fy) &&
+                axis_cell(gz, g.base[2], g.nz, iz, fz);
       float val = 0.0f;
       if (ok) {
         const Voxel* b = vol + ((size_t)iz * sz + (size_t)iy * sy + (size_t)ix);

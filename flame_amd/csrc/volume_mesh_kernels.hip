@@ -232,8 +232,9 @@ k_mesh_emit(const VolumeGrid g, const MeshBox box, uint32_t n_box, const Voxel* 
     const size_t at = 3 * (vbase + lv);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const float pos0 = g.origin[a] + (float)idx[a] * g.voxel_size;
-      const float pos1 = g.origin[a] + (float)(idx[a] + d[a]) * g.voxel_size;
+      const int at0 = g.base[a] + (int)idx[a];  // the global index: integration rule 1
+      const float pos0 = g.origin[a] + (float)at0 * g.voxel_size;
+      const float pos1 = g.origin[a] + (float)(at0 + (int)d[a]) * g.voxel_size;
       vertices[at + a] = pos0 + t * (pos1 - pos0);
     }
     if (normals) {

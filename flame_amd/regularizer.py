@@ -334,6 +334,33 @@ class _VolumeMeshView(C.Structure):
                 ("triangles", C.POINTER(C.c_int32)), ("triangles_device", C.c_void_p)]
 
 
+class ShiftCounts(C.Structure):
+    """== flame_nltgv2_shift_counts: 8 words."""
+
+    _fields_ = [("kept", C.c_int32), ("kept_seen", C.c_int32), ("lost_seen", C.c_int32), ("entered", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class _ShiftView(C.Structure):
+    _fields_ = [("shift", C.c_int32 * 3), ("device_ms", C.c_float), ("base", C.c_int32 * 3), ("record_bytes", C.c_int32), ("counts", ShiftCounts)]
+
+
+class FollowParams(C.Structure):
+    """== flame_nltgv2_follow_params (same defaults): the point the window follows lies focus_depth along the optical axis (0: the camera
+    centre); the window moves in whole steps of `step` voxels."""
+
+    _fields_ = [("focus_depth", C.c_float), ("step", C.c_int32)]
+
+    def __init__(self, focus_depth=0.0, step=8):
+        super().__init__(focus_depth, int(step))
+
+
+class FollowPlan(C.Structure):
+    """== flame_nltgv2_follow_plan: 32 words; boxes as VolumeMeshParams takes them, pre-shift local indices."""
+
+    _fields_ = [("shift", C.c_int32 * 3), ("n_leaving", C.c_int32), ("has_kept", C.c_int32), ("kept_lo", C.c_int32 * 3), ("kept_hi", C.c_int32 * 3),
+                ("leaving_lo", (C.c_int32 * 3) * 3), ("leaving_hi", (C.c_int32 * 3) * 3), ("reserved", C.c_int32 * 3)]
+
+
 class DebugImageParams(C.Structure):
     """== flame_nltgv2_debug_image_params (same defaults): scene_color_scale params.h:109, debug_flip_images, and which of
     drawInverseDepthMap / drawNormals are wanted."""
@@ -433,6 +460,8 @@ ABI_SYMBOLS = (
     "flame_nltgv2_volume_download", "flame_nltgv2_volume_upload", "flame_nltgv2_volume_integrate_begin", "flame_nltgv2_volume_integrate_end",
     "flame_nltgv2_volume_integrate", "flame_nltgv2_volume_raycast_begin", "flame_nltgv2_volume_raycast_end", "flame_nltgv2_volume_raycast",
     "flame_nltgv2_default_volume_mesh_params", "flame_nltgv2_volume_mesh_begin", "flame_nltgv2_volume_mesh_end", "flame_nltgv2_volume_mesh",
+    "flame_nltgv2_default_follow_params", "flame_nltgv2_volume_window", "flame_nltgv2_volume_shift_begin", "flame_nltgv2_volume_shift_end",
+    "flame_nltgv2_volume_shift", "flame_nltgv2_volume_follow",
     "flame_nltgv2_default_debug_image_params", "flame_nltgv2_debug_images_begin", "flame_nltgv2_debug_images_end",
     "flame_nltgv2_debug_images",
     "flame_nltgv2_default_wireframe_params", "flame_nltgv2_debug_wireframe_begin", "flame_nltgv2_debug_wireframe_end",
@@ -556,6 +585,12 @@ def load_library():
         "flame_nltgv2_volume_raycast_begin": (C.c_int, [ctx, _FP, _FP, C.POINTER(RaycastParams), C.c_int, C.c_int]),
         "flame_nltgv2_volume_raycast_end": (C.c_int, [ctx, C.POINTER(_RaycastView)]),
         "flame_nltgv2_volume_raycast": (C.c_int, [ctx, _FP, _FP, C.POINTER(RaycastParams), C.c_int, C.c_int, _FP, C.POINTER(RaycastCounts)]),
+        "flame_nltgv2_default_follow_params": (None, [C.POINTER(FollowParams)]),
+        "flame_nltgv2_volume_window": (C.c_int, [ctx, C.POINTER(C.c_int32)]),
+        "flame_nltgv2_volume_shift_begin": (C.c_int, [ctx, C.POINTER(C.c_int32)]),
+        "flame_nltgv2_volume_shift_end": (C.c_int, [ctx, C.POINTER(_ShiftView)]),
+        "flame_nltgv2_volume_shift": (C.c_int, [ctx, C.POINTER(C.c_int32), C.POINTER(ShiftCounts)]),
+        "flame_nltgv2_volume_follow": (C.c_int, [ctx, _FP, C.POINTER(FollowParams), C.POINTER(FollowPlan)]),
         "flame_nltgv2_default_volume_mesh_params": (None, [C.POINTER(VolumeMeshParams)]),
         "flame_nltgv2_volume_mesh_begin": (C.c_int, [ctx, C.POINTER(VolumeMeshParams)]),
         "flame_nltgv2_volume_mesh_end": (C.c_int, [ctx, C.POINTER(_VolumeMeshView)]),
@@ -1251,6 +1286,45 @@ class Regularizer:
             params = VolumeMeshParams(lo, hi, q["n_vertices"], q["n_triangles"], want_normals, True)
         self.volume_mesh_begin(params)
         return self.volume_mesh_end()
+
+    # -- the window that follows the camera (flame_nltgv2_volume_shift*, flame_nltgv2_volume_window, flame_nltgv2_volume_follow) --------
+    def volume_window(self) -> np.ndarray:
+        """-> base (3,) i32: local voxel (i, j, k) is global voxel base + (i, j, k)."""
+        b = (C.c_int32 * 3)()
+        self._chk(self._L.flame_nltgv2_volume_window(self._ctx, b), "volume_window")
+        return np.array(list(b), np.int32)
+
+    def volume_shift_begin(self, shift):
+        """Enqueues the move of the window by shift (3 ints, voxels) on the side stream and returns: destination voxel (i, j, k) gets the
+        record of (i, j, k) + shift where that lies in the window, else a fresh one."""
+        s = (C.c_int32 * 3)(*[int(v) for v in shift])
+        self._chk(self._L.flame_nltgv2_volume_shift_begin(self._ctx, s), "volume_shift_begin")
+
+    def volume_shift_end(self) -> dict:
+        """Waits for the side stream; dict(shift (3,), base (3,), device_ms, record_bytes (16, 8 or 0), counts (8 i32), kept, kept_seen,
+        lost_seen, entered)."""
+        v = _ShiftView()
+        self._chk(self._L.flame_nltgv2_volume_shift_end(self._ctx, C.byref(v)), "volume_shift_end")
+        out = dict(shift=np.array(list(v.shift), np.int32), base=np.array(list(v.base), np.int32), device_ms=float(v.device_ms),
+                   record_bytes=int(v.record_bytes), counts=np.frombuffer(bytes(v.counts), np.int32).copy())
+        out.update({k: int(getattr(v.counts, k)) for k, _ in ShiftCounts._fields_ if k != "reserved"})
+        return out
+
+    def volume_shift(self, shift) -> dict:
+        """volume_shift_begin; volume_shift_end."""
+        self.volume_shift_begin(shift)
+        return self.volume_shift_end()
+
+    def volume_follow(self, T_world_cam, params: FollowParams = None) -> dict:
+        """Where the window should move for a camera at T_world_cam (12 floats, row-major [R | t]); host arithmetic, nothing shifts.
+        -> dict(shift (3,) i32, kept: (lo, hi) or None, leaving: [(lo, hi), ...] in pre-shift local indices, plan: the FollowPlan)."""
+        t = self._pose12(T_world_cam, "T_world_cam")
+        p = params if params is not None else FollowParams()
+        plan = FollowPlan()
+        self._chk(self._L.flame_nltgv2_volume_follow(self._ctx, t.ctypes.data_as(_FP), C.byref(p), C.byref(plan)), "volume_follow")
+        kept = (list(plan.kept_lo), list(plan.kept_hi)) if plan.has_kept else None
+        leaving = [(list(plan.leaving_lo[b]), list(plan.leaving_hi[b])) for b in range(plan.n_leaving)]
+        return dict(shift=np.array(list(plan.shift), np.int32), kept=kept, leaving=leaving, plan=plan)
 
     # -- the debug images of Flame::update()'s "Draw stuff", flame.cc:490-511 (flame_nltgv2_debug_images*) ----------------------------
     def debug_images_begin(self, img, K, rows, cols, params=None, img_device=None, step_bytes=None):

@@ -340,6 +340,22 @@ struct VolumeMesh {
   VolumeMesh() { std::memset(&counts, 0, sizeof(counts)); }
 };
 
+// The window that follows the camera (flame_nltgv2_volume_shift_begin, flame_nltgv2_volume_follow; the header states every rule).
+struct FollowParams : flame_nltgv2_follow_params {
+  FollowParams() { flame_nltgv2_default_follow_params(this); }
+};
+// Where the window should move: the shift, the box that stays and the up to three boxes that leave, in pre-shift local indices, as
+// VolumeMeshParams::lo / hi take them.
+typedef flame_nltgv2_follow_plan FollowPlan;
+// What one shift did (flame_nltgv2_shift_view): the window afterwards, the four counters, and the bytes per access of the kernel's path.
+struct ShiftedWindow {
+  int32_t shift[3] = {0, 0, 0}, base[3] = {0, 0, 0};
+  int record_bytes = 0;
+  float device_ms = 0.0f;
+  flame_nltgv2_shift_counts counts;
+  ShiftedWindow() { std::memset(&counts, 0, sizeof(counts)); }
+};
+
 // == the members of flame::Params the debug images read (params.h:109, debug_flip_images, debug_draw_idepthmap, debug_draw_normals):
 // layout-identical to flame_nltgv2_debug_image_params, same defaults.  debug_draw_text_overlay is treated as false.
 struct DebugImageParams {
@@ -645,6 +661,26 @@ class DeviceGraph {
     m.normals = v.normals, m.normals_device = v.normals_device;
     m.triangles = v.triangles, m.triangles_device = v.triangles_device;
     return m;
+  }
+
+  // The window that follows the camera: the volume is a window on one infinite grid, volumeShiftBegin moves it by whole voxels on the
+  // side stream (the records that stay keep their bytes and their world positions), volumeFollow says by how much for a camera pose.
+  // Per frame: volumeFollow; volumeMeshBegin / End of each leaving box; volumeShiftBegin / End; volumeIntegrateBegin; volumeRaycastBegin.
+  void volumeWindow(int32_t base[3]) { check(flame_nltgv2_volume_window(ctx_, base), "volume_window"); }
+  void volumeShiftBegin(const int32_t shift[3]) { check(flame_nltgv2_volume_shift_begin(ctx_, shift), "volume_shift_begin"); }
+  ShiftedWindow volumeShiftEnd() {
+    flame_nltgv2_shift_view v;
+    check(flame_nltgv2_volume_shift_end(ctx_, &v), "volume_shift_end");
+    ShiftedWindow w;
+    std::memcpy(w.shift, v.shift, sizeof(w.shift));
+    std::memcpy(w.base, v.base, sizeof(w.base));
+    w.record_bytes = v.record_bytes, w.device_ms = v.device_ms, w.counts = v.counts;
+    return w;
+  }
+  FollowPlan volumeFollow(const float T_world_cam[12], const FollowParams& params) {
+    FollowPlan plan;
+    check(flame_nltgv2_volume_follow(ctx_, T_world_cam, &params, &plan), "volume_follow");
+    return plan;
   }
 
   // drawInverseDepthMap (flame.cc:2699-2719) and interpolateMesh(w1), interpolateMesh(w2), drawNormals (flame.cc:497-506, 2667-2697) over

@@ -813,9 +813,17 @@ int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_param
  *   flame_nltgv2_volume_upload    synchronous, both arrays required: it exists so that a raycast can be tested on voxel values an
  *                                 integration would never produce, and checks weight >= 0 for every voxel (a NaN is not) and nothing else.
  *   Every call but create on a context without a volume answers FLAME_NLTGV2_ERR_INVALID_ARG.
+ * THE WINDOW.  The volume is a window of nx x ny x nz voxels on one infinite grid: it has an int32 base[3], (0, 0, 0) after
+ *   flame_nltgv2_volume_create, which flame_nltgv2_volume_reset and _upload leave unchanged, and LOCAL voxel (i, j, k) -- the index of
+ *   the store, of _download / _upload and of the mesh's boxes -- is GLOBAL voxel (base.x + i, base.y + j, base.z + k).  origin is the
+ *   world position of the centre of GLOBAL voxel (0, 0, 0) and never changes: flame_nltgv2_volume_shift_begin (below this block) moves
+ *   base, not origin, so a voxel's centre keeps its float32 bits for as long as the voxel stays in the window, integration into a moving
+ *   window equals, bit for bit, a crop of integration into a larger fixed volume, and a mesh vertex of a kept cube keeps its bytes
+ *   across a shift.  With base == (0, 0, 0) every rule below is what it was before the window existed, bit for bit.  After any shift
+ *   |base[a]| <= 2^22 on every axis.  flame_nltgv2_volume_window returns the base.
  *
  * INTEGRATION, per voxel (i, j, k), with K (9 floats row-major) and T_cam_world (12 floats, row-major [R | t]):
- *   1 centre     p = origin + (float)index * voxel_size, per axis; P = ((r0 * p.x + r1 * p.y) + r2 * p.z) + t, row by row.
+ *   1 centre     p = origin + (float)(base + index) * voxel_size, per axis, the sum taken in integers before the conversion; P = ((r0 * p.x + r1 * p.y) + r2 * p.z) + t, row by row.
  *   2 front      the voxel is skipped unless P.z > near_depth.                                               counter `front`
  *   3 projection q = K * P, the full 3x3 product; u = q.x / q.z, v = q.y / q.z.
  *   4 in image   iff u >= -0.5f && u < (float)cols - 0.5f && v >= -0.5f && v < (float)rows - 0.5f.  The test comes first, so that no
@@ -843,10 +851,11 @@ int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_param
  * n_steps in 1 .. 4096:
  *   q = Kinv * (col, row, 1), as in the metric outputs.  For n = 0 .. n_steps - 1:
  *     z_n = z_near + (float)n * dz: a product, not a running sum;  Pc = q * z_n, componentwise;  p = T_world_cam applied as in rule 1;
- *     g = (p - origin) / voxel_size, per axis;
- *     the sample is VALID iff every g lies in [0, n_axis - 1] and all eight voxels around it have weight > 0; an axis with
- *     n_axis == 1 has no valid sample;
- *     i0 = min((int)floorf(g), n_axis - 2), f = g - (float)i0, so g == n_axis - 1 gives f == 1;
+ *     g = (p - origin) / voxel_size, per axis: a GLOBAL coordinate;
+ *     the sample is VALID iff, per axis, g >= (float)base && g <= (float)(base + n_axis - 1), and all eight voxels around it have
+ *     weight > 0; an axis with n_axis == 1 has no valid sample;
+ *     ig = min((int)floorf(g), base + n_axis - 2), the local cell index is ig - base, f = g - (float)ig, so g == base + n_axis - 1
+ *     gives f == 1;
  *     the value is trilinear with lerp(a, b, t) = a + t * (b - a), along x, then y, then z.
  *   The ray ENDS at the first valid sample with value <= 0.  It is a HIT iff the sample of step n - 1 was valid and > 0: then
  *   z* = z_{n-1} + dz * (f_prev / (f_prev - f_cur)) with the two values, and the pixel is 1.0f / (z* * q.z).  Otherwise the surface was
@@ -863,11 +872,12 @@ int flame_nltgv2_fuse_views(flame_nltgv2_ctx* ctx, const flame_nltgv2_fuse_param
  * flame_nltgv2_volume_integrate / flame_nltgv2_volume_raycast == begin (the raycast with copy_out forced to 1); end; copies into the
  *        caller's arrays (each may be NULL).
  * (The surface as a triangle mesh with normals: flame_nltgv2_volume_mesh_begin, below this block.)
- * Not done: colour, a sparse or hashed volume, a volume that moves with the camera. */
+ * (The window that follows the camera: flame_nltgv2_volume_shift_begin and flame_nltgv2_volume_follow, below the mesh.)
+ * Not done: colour, a sparse or hashed volume. */
 typedef struct flame_nltgv2_volume_params {
   int32_t nx, ny, nz;      /* 64, 64, 64 */
   float   voxel_size;      /* 0.05       metres */
-  float   origin[3];       /* 0          the world position of the centre of voxel (0, 0, 0) */
+  float   origin[3];       /* 0          the world position of the centre of GLOBAL voxel (0, 0, 0): THE WINDOW */
   float   trunc;           /* 0.15       metres */
   float   max_weight;      /* 64.0 */
 } flame_nltgv2_volume_params;
@@ -956,7 +966,8 @@ int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const 
  *   cubes agree, which closes the surface).
  * EDGES AND KEYS.  Every tet edge runs from a voxel, its owner, to the voxel at offset E[e],
  *   E = [(1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1)].  Its key is voxel_linear_index * 7 + e (64 bits) with the volume's
- *   linear index (k * ny + j) * nx + i: boxes agree on keys.
+ *   linear index (k * ny + j) * nx + i: boxes agree on keys.  Keys are LOCAL to the window: they are not stable across a
+ *   flame_nltgv2_volume_shift, but positions are (THE WINDOW); welding across shifts is left to the caller.
  * TRIANGLES OF A TET.  From the 4-bit mask of inside corners, bit 0 = A .. bit 3 = D.  Masks 0 and 15: none.  One corner P alone on its
  *   side, the others Q < R < S by letter: the triangle (PQ, PR, PS).  Two inside P < Q and two outside R < S: the quad PR, PS, QS, QR, split
  *   along PR - QS into (PR, PS, QS) and (PR, QS, QR).  The second and third corners are swapped where needed so that
@@ -965,7 +976,7 @@ int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const 
  *   the checker; the device reads flame_amd/csrc/volume_mesh_table.h, written by that generator.
  * VERTICES.  One for exactly the keys that at least one triangle names: an edge with a sign change but no live cube of the box around it
  *   has none.  t = f0 / (f0 - f1) with f0 the owner's tsdf and f1 the far end's, whichever is inside; position p0 + t * (p1 - p0) per
- *   axis with p = origin + (float)index * voxel_size as in integration rule 1.  f1 == 0 puts a vertex on a corner and may give zero-area
+ *   axis with p = origin + (float)(base + index) * voxel_size as in integration rule 1.  f1 == 0 puts a vertex on a corner and may give zero-area
  *   triangles: they are kept.  Non-finite tsdf values go through the arithmetic as they are.
  * NORMALS (want_normals).  The gradient at a voxel, per axis, over the neighbours inside the VOLUME (not the box) with weight > 0: both:
  *   (f+ - f-) * 0.5f; one: f+ - f0 or f0 - f-; none: 0.0f.  At a vertex n = g0 + t * (g1 - g0) per component,
@@ -988,7 +999,7 @@ int flame_nltgv2_volume_raycast(flame_nltgv2_ctx* ctx, const float* Kinv, const 
  *        until the next flame_nltgv2_volume_mesh_begin.  With copy_out == 0 only the counters travel.
  * flame_nltgv2_volume_mesh == begin with copy_out forced to 1 and want_normals = (normals_out != NULL); end; copies into the caller's
  *        arrays (each may be NULL), which hold max_vertices / max_triangles elements; nothing is copied on overflow.
- * Not done: colour, vertex welding across calls, decimation, a sparse or hashed volume, a volume that moves with the camera. */
+ * Not done: colour, vertex welding across calls or shifts, decimation, a sparse or hashed volume. */
 typedef struct flame_nltgv2_volume_mesh_params {
   int32_t lo[3];           /* 0, 0, 0 */
   int32_t hi[3];           /* 0, 0, 0    all zero: the whole volume */
@@ -1019,6 +1030,82 @@ int flame_nltgv2_volume_mesh_begin(flame_nltgv2_ctx* ctx, const flame_nltgv2_vol
 int flame_nltgv2_volume_mesh_end(flame_nltgv2_ctx* ctx, flame_nltgv2_volume_mesh_view* out);
 int flame_nltgv2_volume_mesh(flame_nltgv2_ctx* ctx, const flame_nltgv2_volume_mesh_params* params, float* vertices_out, float* normals_out,
                              int32_t* triangles_out, flame_nltgv2_volume_mesh_counts* counts_out);
+
+/* ---- Volumetric map: a window that follows the camera ------------------------------------------------------------------------------------
+ * flame_nltgv2_volume_shift_begin moves THE WINDOW (above) by shift[3] voxels, any int32 triple, on the side stream beside a running
+ * solver; flame_nltgv2_volume_follow says by how much, from a camera pose.  The reference has no counterpart: the rules are stated here
+ * in full (UNPINNED); tests/volume_window_ref.py restates them in numpy and is the checker: device and checker agree bit for bit.
+ *
+ * THE SHIFT.  base' = base + shift.  Destination local voxel (i, j, k) receives the record of source local voxel
+ *   (i + s.x, j + s.y, k + s.z) if that lies inside the window -- copied as 8 bytes: NaNs, -0 and payloads survive --, otherwise the
+ *   fresh record {1.0f, 0.0f}.  |s_a| >= n_a on any axis clears everything: that is also how a caller jumps the window far away.
+ *   |base'[a]| > 2^22 on any axis is FLAME_NLTGV2_ERR_INVALID_ARG and nothing changes.
+ *   Out of place: the context keeps a second buffer of the volume's size, allocated at the first shift that moves anything (from then on
+ *   flame_nltgv2_volume_info reports both buffers), writes it from the first and swaps the two behind the enqueue; every later stage is
+ *   enqueued on the same side stream, so stream order covers the hazard.  Every source record is read exactly once and every destination
+ *   record has exactly one writer; no floating-point atomics, no counter raced for a place: two calls give the same bytes.  The kernel
+ *   moves two records per access (16 bytes) where nx and the linear displacement (s.z * ny + s.y) * nx + s.x are even and one (8 bytes)
+ *   otherwise; both give the same bytes, and record_bytes says which ran.
+ *   A zero shift moves nothing, allocates nothing and swaps nothing (record_bytes == 0): only the read-only count behind kept_seen is
+ *   enqueued.
+ * COUNTERS (8 words, summed in _end from sixteen partial sets as in the other volume stages; integer adds only).  kept: records moved;
+ *   kept_seen: records moved with weight > 0; lost_seen: records with weight > 0 that left; entered: fresh records.
+ *   kept + entered == nx * ny * nz, and kept_seen + lost_seen == the voxels with weight > 0 before the call.
+ * begin  checks the arguments -- no volume; NULL shift; a base past the limit; no memory for the second buffer (FLAME_NLTGV2_ERR_OOM):
+ *        reported before anything is enqueued, leaving the volume, the window, an earlier view and a pending _end as they are --, then
+ *        enqueues everything on the side stream; the window has moved when it returns: a later begin of any volume stage sees base'.
+ * end    waits for the side stream and fills *out.
+ * flame_nltgv2_volume_shift == begin; end; copies the counters (counts_out may be NULL).
+ *
+ * FOLLOW (host arithmetic only, float32, no FMA; nothing is enqueued and nothing shifts).  With T_world_cam (12 floats, row-major
+ *   [R | t]), focus_depth (the point followed lies that far along the optical axis; 0: the camera centre) and step >= 1, per axis a:
+ *     c_a = t_a + focus_depth * R[a][2];  g_a = (c_a - origin_a) / voxel_size;  m_a = base_a + n_a / 2 (integer division);
+ *     q_a = (int)truncf((g_a - (float)m_a) / (float)step);  shift_a = q_a * step.
+ *   So the window moves in whole steps and only once the point is a whole step off the middle voxel: hysteresis.  A non-finite c_a, a
+ *   quotient outside +-2^22 or a product outside int32 is FLAME_NLTGV2_ERR_INVALID_ARG, as are no volume, a NULL argument, a non-finite
+ *   focus_depth and step < 1.  The base limit is flame_nltgv2_volume_shift_begin's to answer.
+ *   THE PLAN.  shift[3]; the KEPT box: the voxels that stay, max(0, s_a) <= index < min(n_a, n_a + s_a) in pre-shift local indices
+ *   (has_kept == 0 and all zeros if nothing stays); and n_leaving <= 3 LEAVING boxes, pre-shift local indices, the slabs in this order:
+ *   the leaving x-slab over all j, k; the leaving y-slab over the kept i range and all k; the leaving z-slab over the kept i and j ranges
+ *   -- each extended by one voxel layer towards the kept side.  Together with the kept box they tile the window in the sense of THE BOX:
+ *   flame_nltgv2_volume_mesh of each gives disjoint triangles whose union is the whole extraction.  If anything leaves entirely
+ *   (|s_a| >= n_a on an axis) the plan is one leaving box, the whole window.  The intended loop per frame: follow; volume_mesh of each
+ *   leaving box (the map streamed out); volume_shift; integrate; raycast. */
+typedef struct flame_nltgv2_shift_counts {
+  int32_t kept, kept_seen, lost_seen, entered;
+  int32_t reserved[4];
+} flame_nltgv2_shift_counts;
+
+typedef struct flame_nltgv2_shift_view {
+  int32_t shift[3];        /* what begin was given */
+  float   device_ms;       /* measurement aid: HIP-event time of what begin enqueued on the side stream */
+  int32_t base[3];         /* the window after the shift */
+  int32_t record_bytes;    /* 16 or 8: the path the kernel took; 0: a zero shift, nothing moved */
+  flame_nltgv2_shift_counts counts;
+} flame_nltgv2_shift_view;
+
+typedef struct flame_nltgv2_follow_params {
+  float   focus_depth;     /* 0.0   metres along the optical axis; 0: the camera centre */
+  int32_t step;            /* 8     voxels, >= 1 */
+} flame_nltgv2_follow_params;
+void flame_nltgv2_default_follow_params(flame_nltgv2_follow_params* p);
+
+/* 32 words.  Boxes as flame_nltgv2_volume_mesh_params takes them: lo <= index < hi, pre-shift local indices. */
+typedef struct flame_nltgv2_follow_plan {
+  int32_t shift[3];
+  int32_t n_leaving;       /* 0 .. 3 */
+  int32_t has_kept;        /* 1: kept_lo / kept_hi name a box; 0: nothing stays */
+  int32_t kept_lo[3], kept_hi[3];
+  int32_t leaving_lo[3][3], leaving_hi[3][3];   /* [box][axis] */
+  int32_t reserved[3];
+} flame_nltgv2_follow_plan;
+
+int flame_nltgv2_volume_window(flame_nltgv2_ctx* ctx, int32_t base_out[3]);
+int flame_nltgv2_volume_shift_begin(flame_nltgv2_ctx* ctx, const int32_t shift[3]);
+int flame_nltgv2_volume_shift_end(flame_nltgv2_ctx* ctx, flame_nltgv2_shift_view* out);
+int flame_nltgv2_volume_shift(flame_nltgv2_ctx* ctx, const int32_t shift[3], flame_nltgv2_shift_counts* counts_out);
+int flame_nltgv2_volume_follow(flame_nltgv2_ctx* ctx, const float* T_world_cam, const flame_nltgv2_follow_params* params,
+                               flame_nltgv2_follow_plan* plan_out);
 
 /* ---- The debug images of Flame::update()'s last block, "Draw stuff" (flame.cc:490-511) -------------------------------------------------
  * getDebugImageInverseDepthMap and getDebugImageNormals (flame.h:294-306) from what already stands on the device: the resident dense map,
